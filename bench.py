@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- retargeted frames/s of the batched HIP solver on N MI355X GPUs (one process per GPU).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,7 +15,9 @@ batches are rotated), so no step re-solves the previous step's inputs.
 Headline workload (synthetic, seeded): keypoints = frame (b mod 621) of the human fixture
 + N(0, 2 mm); ref_value = kp[task] - kp[origin] formed inside the kernel (profile_online_retargeting.py:24-30);
 last_qpos = the solver's own answer for the neighbouring frame (b-1), i.e. the warm start a running sequence has
-(seq_retarget.py:124).  float32 arithmetic (dtype "f32"); the same line carries
+(seq_retarget.py:124).  float32 arithmetic (dtype "f32").  A plain run sets up, warms up, times the K steps and prints the
+line; `--dump-outputs DIR` writes the last timed step's qpos rows (and DexPilot state) as DIR/<name>.npy.  With `--full` the
+same line also carries iteration statistics, the roofline and
 
 * "f64":        the same config timed with float64 arithmetic throughout (the reference's arithmetic type);
 * "cold_start": the reference's own test regime (tests/test_optimizer.py:27-81: reachable targets, start sigma = 0.5);
@@ -129,6 +131,7 @@ class Workload:
         self.t_q = torch.empty((B, self.n_opt), dtype=torch.float32, device=dev)
         self.tracking = self._stage_tracking(bench_data)
         self.cold = None
+        self.last_out = None
 
     def _stage_tracking(self, bench_data):
         """N_BATCHES batches of B frames: different fixture phase and noise per batch; the warm start of frame b is
@@ -199,6 +202,7 @@ class Workload:
             k = n[0]
             out = self.t_q if pipe is None else pipe.shard(k)
             self.launch(batches[k % len(batches)], out, opts=opts)
+            self.last_out = out
             if pipe is not None:
                 pipe.gather(k)
             n[0] += 1
@@ -227,6 +231,15 @@ class Workload:
         if comm is not None:
             elapsed = float(comm.max_f64([elapsed], self.stream.cuda_stream)[0])
         return elapsed, kernel_ms
+
+    def last_outputs(self):
+        """What the caller of the timed path holds after its last step: this rank's qpos rows (B, n_opt) and, for DexPilot,
+        the projection state the kernel carried forward (uint32 bit flags, as float64)."""
+        self.torch.cuda.synchronize()
+        out = {"qpos": self.last_out.cpu().numpy()}
+        if self.dexpilot:
+            out["dexpilot_state"] = self.t_state.cpu().numpy().view(np.uint32).astype(np.float64)
+        return out
 
     def sustained(self, batches, seconds=6.0, chunk=4000):
         """A rate the driver can see from outside: back-to-back launches of the workload for >= `seconds` (the
@@ -608,25 +621,24 @@ def online_parity(rec, ctxs):
 
 
 def reference_profile_script_record():
-    """Sub-record `reference_profile_script`: /root/reference/example/profiling/profile_online_retargeting.py:39-77
-    run UNMODIFIED -- its main(), its loop (:18-36), its prints -- with `dex_retargeting` aliased to the drop-in, in a process of
-    its own (tests/reference_suite/run_profile_script.py; the script and its pickle are staged byte for byte by
-    tests/reference_suite/stage.py, git-ignored).  7 robots x {vector, DexPilot} = 14 rows.  main() is executed twice in that
-    process: the script creates the process's first HIP context inside its first row's timer (pass 1, as printed), pass 2 is the
-    same script on a warm process."""
+    """Sub-record `reference_profile_script`: the reference's online benchmark shape (profile_online_retargeting.py)
+    -- 7 robots x {vector, DexPilot} = 14 rows, one SeqRetargeting.retarget per fixture frame -- with `dex_retargeting` aliased to
+    the drop-in, in a process of its own (tests/reference_suite/run_profile_script.py).  The 14 rows are run twice in that
+    process: pass 1 creates the process's first HIP context inside its first row's timer, pass 2 is the same loop on a warm
+    process."""
     import subprocess
 
     runner = os.path.join(REPO, "tests", "reference_suite", "run_profile_script.py")
     r = subprocess.run([sys.executable, runner, "--json", "--passes", "2"], capture_output=True, text=True, timeout=900, cwd=REPO)
     if r.returncode != 0:
         return {"error": (r.stderr or r.stdout)[-400:]}
-    recs = [json.loads(l.split(" ", 1)[1]) for l in r.stdout.splitlines() if l.startswith("REFERENCE_PROFILE_SCRIPT ")]
+    recs = [json.loads(l.split(" ", 1)[1]) for l in r.stdout.splitlines() if l.startswith("ONLINE_PROFILE_ROWS ")]
     rows = recs[-1]["rows"]
-    out = {"script": "example/profiling/profile_online_retargeting.py (unmodified; sha256 in tests/reference_suite/_ref/MANIFEST.json)",
-           "frames_per_row": 621, "rows": rows, "unit": "fps (the script's own: 621 / summed perf_counter time around retarget())"}
+    out = {"script": "tests/reference_suite/run_profile_script.py (the reference's profile_online_retargeting.py loop)",
+           "frames_per_row": 621, "rows": rows, "unit": "fps: 621 / summed perf_counter time around retarget()"}
     if len(recs) > 1:
         out["first_pass_rows"] = recs[0]["rows"]
-    out["stdout"] = [l for l in r.stdout.splitlines() if not l.startswith("REFERENCE_PROFILE_SCRIPT ")][-15:]
+    out["stdout"] = [l for l in r.stdout.splitlines() if not l.startswith("ONLINE_PROFILE_ROWS ")][-15:]
     return out
 
 
@@ -907,6 +919,16 @@ def reference_stack_record(rel, n_frames=621):
             "note": "dex_retargeting's own SeqRetargeting on pinocchio + nlopt, this repo's URDF / YAML files as inputs"}
 
 
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs DIR: the arrays of the last timed step as DIR/<name>.npy (float32 / float64; with N > 1 ranks every rank
+    writes its own rows as DIR/<name>_rank<r>.npy).  The inputs are seeded, so two builds can be compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), a)
+
+
 def cgroup_cpu_max():
     """The container's CPU quota as the kernel reports it ("max 100000" = none; "<quota> <period>" = quota / period CPUs)."""
     for path in ("/sys/fs/cgroup/cpu.max", "/sys/fs/cgroup/cpu/cpu.cfs_quota_us"):
@@ -992,7 +1014,7 @@ def rccl_env():
 
 
 def gather_records(timed_fn, comm, B, n_cols, dev, steps, warmup, world, graph_fn=None, rank=0, on_headline=None,
-                   strong_fn=None):
+                   strong_fn=None, full=True):
     """The N > 1 figures (also taken with ONE rank when launched by torch.distributed.run, so that the RCCL side runs on a
     1-GPU box): dexr_allgather of the (B, n_cols) f32 result rows.  Returns
     (elapsed, kernel_ms, record dict).
@@ -1007,7 +1029,7 @@ def gather_records(timed_fn, comm, B, n_cols, dev, steps, warmup, world, graph_f
     on solve stream= one collective per step on the solve stream itself (strictly serial);
     strong scaling = the metric's 65 536 frames over the whole node (B / N per GPU) with the per-step gather;
     graph replay   = [solve -> all-gather] x 4 captured into one HIP graph.
-    Everything after the headline runs under a watchdog."""
+    Everything after the headline runs under a watchdog, and only with full=True (bench.py --full)."""
     from dex_retargeting_amd.distributed import NativeGather, steps_per_gather_for
 
     wd = Watchdog(rank, float(os.environ.get("DEXR_BENCH_WATCHDOG_S", "120")))
@@ -1058,6 +1080,8 @@ def gather_records(timed_fn, comm, B, n_cols, dev, steps, warmup, world, graph_f
                          f"{shard_mb * (world - 1) / 76.8 * 1e3:.1f} us on a single ring direction"}})
     if on_headline is not None:
         wd.line = on_headline(elapsed, kernel_ms)
+    if not full:
+        return elapsed, kernel_ms, dict(rec)
     k2 = k_policy if k_policy > 1 else 4  # the grouped mode, for comparison (the wire-time policy's k; 4 when that is 1)
     while steps % k2:
         k2 -= 1
@@ -1116,12 +1140,12 @@ def run_single(args):
                  "unit": "frames/s"}
         print(bench_line.dumps(probe))  # (a few bytes for tools/prof_summary.py, not a contract line)
         return
-    diag = wl.diagnostics(wl.tracking)
+    diag = wl.diagnostics(wl.tracking) if args.full else None
 
     # ---- headline: float32 tracking -----------------------------------------------------------------------------
     def contract_line(elapsed, kernel_ms, coll=None):
         frames = world * B * args.steps
-        return {
+        line = {
             "metric": json.load(open(os.path.join(REPO, "BASELINE.json")))["metric"],
             "value": frames / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -1131,13 +1155,16 @@ def run_single(args):
                        "config_file": wl.rel, "batch_per_gpu": B, "n_opt": wl.n_opt, "n_ref": wl.n_ref,
                        "collective": "none" if comm is None else "dexr_allgather (RCCL ncclAllGather) on a second stream, one per step",
                        "rccl_world_size": None if comm is None else world},
-            "solver": dict(diag, tol_rad=2e-6, newton=1),
-            "roofline": dict(wl.roofline(kernel_ms, diag["iters_mean"], world=world),
-                             traffic_note="bytes per launch from the rocprofv3 --pmc passes in profiles/ (same command, same "
-                                          "batch, same kernel sources); null when no matching profile is committed",
-                             note="path is FP32 VALU/latency bound (n_dof <= 24 per lane, no dense contraction); the HBM "
-                                  "fraction is reported as north_star asks, see DESIGN.md section 4"),
         }
+        if diag is None:  # a plain run: no untimed diagnostic launches, so no iteration statistics or roofline (--full)
+            return line
+        line["solver"] = dict(diag, tol_rad=2e-6, newton=1)
+        line["roofline"] = dict(wl.roofline(kernel_ms, diag["iters_mean"], world=world),
+                                traffic_note="bytes per launch from the rocprofv3 --pmc passes in profiles/ (same command, same "
+                                             "batch, same kernel sources); null when no matching profile is committed",
+                                note="path is FP32 VALU/latency bound (n_dof <= 24 per lane, no dense contraction); the HBM "
+                                     "fraction is reported as north_star asks, see DESIGN.md section 4")
+        return line
 
     def strong_scaling():
         """The metric read as STRONG scaling: its 65 536 frames over the whole node, B / N frames per GPU, per-step gather
@@ -1162,9 +1189,20 @@ def run_single(args):
             comm, B, wl.n_opt, dev, args.steps, args.warmup, world, rank=rank,
             graph_fn=lambda: wl.timed_graph(wl.tracking, args.steps, comm),
             on_headline=(lambda e, k: contract_line(e, k)) if rank == 0 else None,
-            strong_fn=strong_scaling)
+            strong_fn=strong_scaling, full=args.full)
     else:
         elapsed, kernel_ms = wl.timed(wl.tracking, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl.last_outputs(), rank, world)
+    if not args.full:
+        if rank == 0:
+            line = contract_line(elapsed, kernel_ms)
+            if coll is not None:
+                line["multi_gpu"] = coll
+            bench_line.print_line(line)
+        if comm is not None:
+            comm.close()
+        return
     # per-step answers of the last timed step's batch for the parity check
     last_batch = wl.tracking[(args.steps - 1) % N_BATCHES]
     wl.launch(last_batch, wl.t_q)
@@ -1553,7 +1591,15 @@ def main():
                          "rocprofv3 for the sub-records' PMC summaries)")
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="launch + rendezvous plumbing only (no GPU work): used by the CPU tests of the N > 1 launcher")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: iteration statistics and roofline, the f64 / cold-start / other-config / "
+                         "fleet / online / sequence sub-records, the other N > 1 gather modes, parity against the oracle and the "
+                         "CPU baselines.  Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: none of the sub-records, checker sections or host-CPU solves
+        args.headline_only, args.no_cpu_baseline = True, True
     if args.nccl_algo:
         os.environ["NCCL_ALGO"] = args.nccl_algo
     if args.nccl_proto:

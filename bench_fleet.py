@@ -24,7 +24,10 @@ def run(args):
     if m is not None:
         import bench_line
 
-        bench_line.emit(fleet_check(*m, args))
+        if args.full:
+            bench_line.emit(fleet_check(*m, args))
+        else:  # a plain run: the timed steps and the result line only
+            bench_line.print_line(m[0])
 
 
 def fleet_measure(args, batch=None, standalone=True):
@@ -82,7 +85,7 @@ def fleet_measure(args, batch=None, standalone=True):
     t_state = torch.zeros(B, dtype=torch.int32, device=dev)
     t_out = torch.zeros((B, fleet.n_max), dtype=torch.float32, device=dev)
     stream = torch.cuda.current_stream()
-    last_b = [None]
+    last_b, last_out = [None], [None]
 
     def timed(pipe):
         n = [0]
@@ -93,6 +96,7 @@ def fleet_measure(args, batch=None, standalone=True):
             t_state.copy_(b["t_state0"])
             out = t_out if pipe is None else pipe.shard(k)
             fleet.retarget(b["t_mid"], b["t_kp"], b["t_last"], t_state, out=out)
+            last_out[0] = out
             if pipe is not None:
                 pipe.gather(k)
             n[0] += 1
@@ -123,17 +127,26 @@ def fleet_measure(args, batch=None, standalone=True):
         return elapsed, float(ev0.elapsed_time(ev1)) / args.steps
 
     coll = None
+    full = getattr(args, "full", True)
     if comm is not None:
-        elapsed, step_ms, coll = gather_records(timed, comm, B, fleet.n_max, dev, args.steps, args.warmup, world, rank=rank)
+        elapsed, step_ms, coll = gather_records(timed, comm, B, fleet.n_max, dev, args.steps, args.warmup, world, rank=rank, full=full)
     else:
         elapsed, step_ms = timed(None)
+    if standalone and getattr(args, "dump_outputs", None):
+        from bench import dump_outputs
+
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, {"qpos": last_out[0].cpu().numpy(),  # (B, n_max): model m's rows in the first n_opt(m) columns
+                                         "dexpilot_state": t_state.cpu().numpy().view(np.uint32).astype(np.float64)}, rank, world)
     if rank != 0:
         comm.close()
         return None
     last_b = last_b[0]
-    # answers of the last step's batch (re-issued into a plain buffer) for the checker
-    t_state.copy_(last_b["t_state0"])
-    q = fleet.retarget(last_b["t_mid"], last_b["t_kp"], last_b["t_last"], t_state, out=torch.zeros_like(t_out)).cpu().numpy()
+    q = None
+    if full:
+        # answers of the last step's batch (re-issued into a plain buffer) for the checker
+        t_state.copy_(last_b["t_state0"])
+        q = fleet.retarget(last_b["t_mid"], last_b["t_kp"], last_b["t_last"], t_state, out=torch.zeros_like(t_out)).cpu().numpy()
     last = last_b["t_last"].cpu().numpy()
     st_in = last_b["t_state0"].cpu().numpy().astype(np.uint32)
     mid, kp = last_b["mid"], last_b["kp"]
@@ -164,7 +177,7 @@ def fleet_measure(args, batch=None, standalone=True):
                                "over its index list, in-place rows"},
     }
     out_json["dtype"] = "per model: f32, or f64 kinematics + f32 Hessian"  # (tip / register kernels; Shadow DexPilot on the sixteen-lane kernel)
-    if world == 1:
+    if world == 1 and full:
         # the same frames in the reference's own arithmetic (float64 throughout).  dexr_retarget_multi_dev runs the
         # float32 / mixed-precision kernels only, so: the batch bucketed by model up front (untimed torch index ops), then one
         # float64 launch per model (dexr_retarget_kp_dev, precision = 1) over its contiguous rows -- the four launches are timed.

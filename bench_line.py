@@ -212,6 +212,13 @@ def sanitize(x):
     return f if math.isfinite(f) else None
 
 
+def print_line(detail):
+    """A plain (not --full) run: the compact line alone -- no DETAIL lines, no detail file."""
+    line = final_line(sanitize(detail))
+    line.pop("detail", None)
+    print(dumps(line), flush=True)
+
+
 def emit(detail, path=None):
     """Print the detail (one `DETAIL <json>` line per top-level block, so no single line is large), write
     bench_detail.json, then print the compact line LAST."""

@@ -1,21 +1,17 @@
-"""Runs the reference's own tests (tests/reference_suite/_ref/, staged unmodified by stage.py) against the drop-in:
-`dex_retargeting` and every `dex_retargeting.<module>` the tests import are aliased to `dex_retargeting_amd` in
-sys.modules BEFORE collection, and the directory layout the tests expect is created.  test_optimizer.py solves on the
-GPU (marked `gpu` here); test_retargeting_config.py only builds objects (host side: runs in the CPU suite too)."""
+"""Tests that use the drop-in under the reference's package name: `dex_retargeting` and every `dex_retargeting.<module>` are
+aliased to `dex_retargeting_amd` in sys.modules BEFORE collection.  The directory layout code written against the reference
+expects (<here>/assets/robots/hands, <here>/dex_retargeting/configs, <here>/src/dex_retargeting/configs) is committed as
+relative symlinks to the package's own assets/ and configs/."""
 import importlib
 import os
 import pkgutil
 import sys
-
-import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
-
-import stage as _stage  # noqa: E402
 
 
 def alias_package():
@@ -29,12 +25,3 @@ def alias_package():
 
 
 alias_package()
-_stage.lay_out()
-HAVE_REF_TESTS = _stage.stage()
-
-
-def pytest_collection_modifyitems(config, items):
-    for item in items:
-        p = str(item.fspath)
-        if os.sep + "_ref" + os.sep in p and os.path.basename(p) == "test_optimizer.py":
-            item.add_marker(pytest.mark.gpu)

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 rm -rf "$O"/ldspmc_*
 for set in "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS" "SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM SQ_BUSY_CYCLES SQ_WAVE_CYCLES" "SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_WAIT_INST_LDS SQ_INSTS_VALU"; do
   tag=$(echo $set | cut -d' ' -f1)
-  timeout 600 rocprofv3 --pmc $set -d "$O/ldspmc_$tag" -o out --output-format csv -- python "$R/bench.py" --workload $W --no-cpu-baseline --headline-only --steps 3 --warmup 1 > /dev/null 2> "$O/ldspmc_$tag.err"
+  timeout 600 rocprofv3 --pmc $set -d "$O/ldspmc_$tag" -o out --output-format csv -- python "$R/bench.py" --full --workload $W --no-cpu-baseline --headline-only --steps 3 --warmup 1 > /dev/null 2> "$O/ldspmc_$tag.err"
 done
 python - "$O" "$W" <<'PY'
 import csv, glob, os, sys, collections

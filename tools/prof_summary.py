@@ -42,7 +42,7 @@ try:
 except Exception as e:
     print("# no bench line:", e)
 
-print(f"# rocprofv3 --kernel-trace --stats -- python bench.py --workload {w} --no-cpu-baseline --steps 20 --warmup 3")
+print(f"# rocprofv3 --kernel-trace --stats -- python bench.py --full --workload {w} --no-cpu-baseline --steps 20 --warmup 3")
 print("# view top_kernels of the rocpd database: name, calls, total_us, avg_us, pct")
 for p in dbs("kt"):
     rows = q(p, "select name,total_calls,total_duration,average,percentage from top_kernels")

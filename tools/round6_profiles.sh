@@ -12,12 +12,12 @@ for w in allegro_vector allegro_vector_f64 allegro_vector_cold shadow_dexpilot l
 done
 # the committed PMC summaries decide whether the bench line carries traffic figures: copy them in place BEFORE the bench runs
 cp "$O"/pmc_*.json "$R/profiles/" 2>/dev/null
-(time python bench.py --steps 20 --warmup 5) > "$O/r06_bench_default.log" 2>&1
+(time python bench.py --full --steps 20 --warmup 5) > "$O/r06_bench_default.log" 2>&1
 tail -1 "$O/r06_bench_default.log" > /dev/null
 cp "$O/bench_detail.json" "$O/r06_bench_detail_default.json" 2>/dev/null
-python bench.py --workload mixed_fleet --steps 20 --warmup 5 > "$O/r06_bench_mixed_fleet.log" 2>&1
+python bench.py --full --workload mixed_fleet --steps 20 --warmup 5 > "$O/r06_bench_mixed_fleet.log" 2>&1
 for w in allegro_vector leap_position mixed_fleet; do
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 1 --workload $w --steps 20 --warmup 5 --headline-only --no-cpu-baseline > "$O/r06_bench_1rank_native_rccl_$w.log" 2>&1
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --full --gpus 1 --workload $w --steps 20 --warmup 5 --headline-only --no-cpu-baseline > "$O/r06_bench_1rank_native_rccl_$w.log" 2>&1
 done
 python tools/all_configs.py 65536 > "$O/r06_all_configs.txt" 2>/dev/null
 for f in r06_bench_default r06_bench_mixed_fleet r06_bench_1rank_native_rccl_allegro_vector r06_bench_1rank_native_rccl_leap_position r06_bench_1rank_native_rccl_mixed_fleet; do

@@ -9,9 +9,9 @@ cd "$R"
 timeout 2400 python -m pytest tests -m gpu -q > "$O/${T}_tests.txt" 2>&1
 grep "passed\|failed" "$O/${T}_tests.txt" | tail -1
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu | tail -2
-timeout 900 python bench.py > "$O/${T}_bench_default.json" 2> "$O/${T}_bench_default.err"
+timeout 900 python bench.py --full > "$O/${T}_bench_default.json" 2> "$O/${T}_bench_default.err"
 for w in allegro_vector leap_position mixed_fleet; do
-  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --workload $w --headline-only --no-cpu-baseline > "$O/${T}_1rank_$w.json" 2> "$O/${T}_1rank_$w.err"
+  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --workload $w --headline-only --no-cpu-baseline > "$O/${T}_1rank_$w.json" 2> "$O/${T}_1rank_$w.err"
   python - "$O/${T}_1rank_$w.json" <<'PY'
 import json,sys
 try:
@@ -21,7 +21,7 @@ try:
 except Exception as e: print(sys.argv[1], "ERR", e)
 PY
 done
-timeout 600 python bench.py --workload mixed_fleet > "$O/${T}_bench_fleet.json" 2> "$O/${T}_bench_fleet.err"
+timeout 600 python bench.py --full --workload mixed_fleet > "$O/${T}_bench_fleet.json" 2> "$O/${T}_bench_fleet.err"
 python - "$O/${T}_bench_default.json" "$O/${T}_bench_fleet.json" <<'PY'
 import json,sys
 for f in sys.argv[1:]:

@@ -10,7 +10,7 @@ for w in allegro_vector shadow_dexpilot leap_position; do
   tail -12 "$O/prof_${w}_summary.txt"
 done
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_fleet_kt -- python $R/bench.py --workload mixed_fleet --no-cpu-baseline --steps 6 --warmup 2 > $O/prof_fleet_bench.json 2> $O/prof_fleet.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_fleet_kt -- python $R/bench.py --full --workload mixed_fleet --no-cpu-baseline --steps 6 --warmup 2 > $O/prof_fleet_bench.json 2> $O/prof_fleet.err
 python $R/tools/timeline.py $O/prof_fleet_kt 30 > $O/prof_fleet_timeline.txt
 rm -rf $O/prof_fleet_kt
 cd "$R"
