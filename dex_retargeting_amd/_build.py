@@ -159,6 +159,13 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
         objs.append(o)
         if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp"), BIG_HEADER] + HEADERS):
             jobs.append((wide_s, o, NO_SLP + ["-DDEXR_NMAX=16", "-DDEXR_MIMIC=1"] + defs))
+    for tag, defs in (("16", ["-DDEXR_NMAX=16"]), ("24", ["-DDEXR_NMAX=24"]), ("m_16", ["-DDEXR_NMAX=16", "-DDEXR_MIMIC=1"]),
+                      ("mc_16", ["-DDEXR_NMAX=16", "-DDEXR_MIMIC=1", "-DDEXR_MODCHOL=1"])):
+        # ... its float64 instantiation (dexr_tuning.kernel_f64): one wave per SIMD, four frames per wave
+        o = os.path.join(BUILD, f"dexr_wide_d_{tag}.o")
+        objs.append(o)
+        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp"), BIG_HEADER] + HEADERS):
+            jobs.append((wide_s, o, NO_SLP + defs + ["-DDEXR_WIDE_F64=1"]))
     red_s = os.path.join(CSRC, "dexr_red_inst.hip")
     for nvb in (8, 16):  # reduced-variable kernel (mimic models): Hessian of the variables in registers
         o = os.path.join(BUILD, f"dexr_red_{nvb}.o")

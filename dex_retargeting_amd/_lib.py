@@ -32,7 +32,8 @@ class Tuning(C.Structure):
                 ("stall_cap", C.c_float), ("lam_jump", C.c_float), ("lam_fastdec", C.c_float),
                 ("floor_scale", C.c_float), ("step_cap", C.c_float), ("blind_tol_scale", C.c_float),
                 ("pivot_rule", C.c_int32), ("longest_first", C.c_int32), ("lam_recover", C.c_float),
-                ("fork_streams", C.c_int32), ("user_mask", C.c_uint32), ("sprint_max_batch", C.c_int32), ("sprint_ladder", C.c_int32), ("tail_passes", C.c_int32)]
+                ("fork_streams", C.c_int32), ("user_mask", C.c_uint32), ("sprint_max_batch", C.c_int32), ("sprint_ladder", C.c_int32), ("tail_passes", C.c_int32),
+                ("kernel_f64", C.c_int32)]
 
 
 TUNE_LAM_JUMP, TUNE_LAM_FASTDEC = 1, 2
@@ -43,7 +44,7 @@ KERNEL_AUTO, KERNEL_REGISTER, KERNEL_QUAD, KERNEL_LDS, KERNEL_REDUCED, KERNEL_WI
 
 EXPORTS = ["dexr_last_error", "dexr_version", "dexr_device_count", "dexr_default_options", "dexr_model_create",
            "dexr_model_destroy", "dexr_model_info", "dexr_model_get_tuning", "dexr_model_set_tuning", "dexr_model_kernel",
-           "dexr_model_lane_plan", "dexr_model_reserve",
+           "dexr_model_kernel_f64", "dexr_model_lane_plan", "dexr_model_reserve",
            "dexr_retarget_dev", "dexr_retarget_seq_dev", "dexr_seq_compose_dev", "dexr_fleet_workspace_bytes",
            "dexr_retarget_multi_dev", "dexr_retarget_multi", "dexr_retarget", "dexr_retarget_f64",
            "dexr_retarget_kp_dev", "dexr_retarget_kp", "dexr_eval", "dexr_fk", "dexr_mano_keypoints_dev",
@@ -83,6 +84,7 @@ def load() -> C.CDLL:
     lib.dexr_model_get_tuning.argtypes = [vp, C.POINTER(Tuning)]
     lib.dexr_model_set_tuning.argtypes = [vp, C.POINTER(Tuning)]
     lib.dexr_model_kernel.argtypes = [vp, i32p, i32p, i32p]
+    lib.dexr_model_kernel_f64.argtypes = [vp, i32p, i32p]
     lib.dexr_model_reserve.argtypes = [vp, C.c_int64]
     lib.dexr_model_lane_plan.argtypes = [vp, C.c_int32, i32p, i32p, vp, vp]
     lib.dexr_retarget_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, optp, vp]
@@ -188,6 +190,12 @@ class Model:
         f, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         check(load().dexr_model_kernel(self._h, C.byref(f), C.byref(b), C.byref(c)))
         return int(f.value), int(b.value), int(c.value)  # chain: 0, 1 (serial-chain kernel) or 2 (with its tip pass)
+
+    def kernel_f64(self):
+        """(family, bucket) of the kernel a float64 solve launch of this handle runs (dexr_tuning.kernel_f64)."""
+        f, b = C.c_int32(), C.c_int32()
+        check(load().dexr_model_kernel_f64(self._h, C.byref(f), C.byref(b)))
+        return int(f.value), int(b.value)
 
     def lane_plan(self, comp: int = 0):
         """(n_chain, depth, chain (16,16) uint8, anc_rev (32,) uint32) of the sixteen-lane kernel for one component."""

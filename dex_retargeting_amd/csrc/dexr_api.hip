@@ -276,12 +276,24 @@ hipError_t dexr_dexpilot_order_launch(int64_t B, const float* kpts, const float*
 namespace {
 
 // sixteen lanes per frame: four frames per wave, two waves per SIMD resident; persistent rows fed like the quads
-int launch_wide_once(const dexr_model* m, dexr::KernelParams kp, hipStream_t st, bool tail_launch = false) {
-  const size_t per_wave = m->wide_mimic ? dexr::wide_lds_per_wave_m_16() : dexr::wide_lds_per_wave(m->wbucket);
+// modified Cholesky on the variable grid (dexr_tuning.pivot_rule; the float32 selection records it in wide_modchol, the float64
+// launch -- which does not depend on that selection -- applies the same rule)
+bool wide_modchol_rule(const dexr_model* m) {
+  return m->wide_mimic && (m->tune.pivot_rule > 0 || (m->tune.pivot_rule < 0 && m->h.kind == DEXR_KIND_DEXPILOT));
+}
+
+// f64: the float64 instantiation (dexr_tuning.kernel_f64 = DEXR_KERNEL_WIDE) -- four frames per wave at every batch size, one
+// wave per SIMD, every step verified (no blind steps)
+int launch_wide_once(const dexr_model* m, dexr::KernelParams kp, hipStream_t st, bool tail_launch = false, bool f64 = false) {
+  const bool modchol = f64 ? wide_modchol_rule(m) : m->wide_modchol;
+  const size_t per_wave = f64 ? (m->wide_mimic ? (modchol ? dexr::wide_lds_per_wave_d_mc_16() : dexr::wide_lds_per_wave_d_m_16())
+                                               : (m->wbucket == 16 ? dexr::wide_lds_per_wave_d_16() : m->wbucket == 24 ? dexr::wide_lds_per_wave_d_24() : 0))
+                              : m->wide_mimic ? dexr::wide_lds_per_wave_m_16() : dexr::wide_lds_per_wave(m->wbucket);
+  if (per_wave == 0) return fail(DEXR_ERR_UNSUPPORTED, "no float64 sixteen-lane kernel for bucket %d", m->wbucket);
   // (a row copies its frame's input block -- keypoints or ref_value rows -- into the 1 KB term-block area of its LDS slot)
   if (kp.kpts && kp.n_kp > 85) return fail(DEXR_ERR_UNSUPPORTED, "the sixteen-lane kernel takes at most 85 keypoints per frame (%d)", kp.n_kp);
   int wpb = 4;
-  while (wpb > 1 && per_wave * wpb > 80 * 1024) wpb >>= 1;
+  while (wpb > 1 && per_wave * wpb > (f64 ? 160 : 80) * 1024) wpb >>= 1;  // (float64: one block of four waves per CU)
   // ONE FRAME PER WAVE for small plain batches (dexr_wide.hpp SPRINT; dexr_tuning.sprint_max_batch):
   // with fewer frames than the chip has row slots a wave's four rows share one frame's term loop instead of idling
   const int64_t sprint_max = m->tune.sprint_max_batch < 0 ? 2048 : m->tune.sprint_max_batch;  // (measured: it wins up to ~2 048 frames = one wave per frame on every SIMD pair, profiles/r05_sprint_one_frame_per_wave.txt)
@@ -290,7 +302,7 @@ int launch_wide_once(const dexr_model* m, dexr::KernelParams kp, hipStream_t st,
   // recorded hand is exactly "three rows idle")
   // (... and the buckets of a small FLEET batch: kp.B is then the whole batch, an upper bound of the bucket the kernel reads from
   // device memory -- several robots following one hand, hand_robot_viewer.py:134-181, is a batch of a few rows per model)
-  const bool sprint = tail_launch || (kp.B <= sprint_max && !kp.screen && kp.n_comp == 1);
+  const bool sprint = !f64 && (tail_launch || (kp.B <= sprint_max && !kp.screen && kp.n_comp == 1));
   const int fpw = sprint ? 1 : 4;  // frames per wave
   {
     const bool ladder = sprint && (tail_launch || m->tune.sprint_ladder != 0);  // (-1: policy = on; the tail launch always)
@@ -302,7 +314,7 @@ int launch_wide_once(const dexr_model* m, dexr::KernelParams kp, hipStream_t st,
     // the minimum (offline Panda frame 1849 after 2 passes, LEAP DexPilot frame 419 after 5: tools/ladder_probe.py,
     // profiles/r06_ladder_probe.txt; the B = 2 048 parity table's certification caught both).  Every step is verified by a
     // pass at the new point; the pass that confirms convergence costs kinematics + value only (dexr_wide.hpp).
-    if (ladder) kp.blind_tol = 0.f;
+    if (ladder || f64) kp.blind_tol = 0.f;
   }
   const int64_t tiles = (kp.B + fpw - 1) / fpw;
   // waves per SIMD: 2 (256 VGPRs; 15-17 KB of LDS per wave); the 16-row joint grid is built for 3 (168 VGPRs, 11.8 KB):
@@ -310,7 +322,7 @@ int launch_wide_once(const dexr_model* m, dexr::KernelParams kp, hipStream_t st,
   // (the 24-row grid at three waves per SIMD -- 168 VGPRs, 85 registers spilled -- measured 34-40 % SLOWER in round 4, with the
   // LDS slot shrunk to make room for it: DESIGN.md section 4)
   // (one frame per wave: the 32-row grid is built for one wave per SIMD -- dexr_wide_s_* in _build.py -- the others for two)
-  const int occ = sprint ? ((!m->wide_mimic && m->wbucket > 24) ? 1 : 2) : ((!m->wide_mimic && m->wbucket == 16) ? 3 : 2);
+  const int occ = f64 ? 1 : sprint ? ((!m->wide_mimic && m->wbucket > 24) ? 1 : 2) : ((!m->wide_mimic && m->wbucket == 16) ? 3 : 2);
   int64_t resident = (int64_t)m->n_cu * 4 * occ;
   if (m->tune.resident_waves > 0) resident = m->tune.resident_waves;
   int64_t per_comp = (resident + kp.n_comp - 1) / kp.n_comp;
@@ -335,7 +347,9 @@ int launch_wide_once(const dexr_model* m, dexr::KernelParams kp, hipStream_t st,
   (void)hipMemsetAsync(wprof, 0, 12 * sizeof(double), st);
   kp.g64out = wprof;
 #endif
-  dexr::wide_launch_fn fn = m->wide_mimic ? (sprint ? (m->wide_modchol ? dexr::launch_wide_s_mc_16 : dexr::launch_wide_s_m_16)
+  dexr::wide_launch_fn fn = f64 ? (m->wide_mimic ? (modchol ? dexr::launch_wide_d_mc_16 : dexr::launch_wide_d_m_16)
+                                                 : m->wbucket == 16 ? dexr::launch_wide_d_16 : m->wbucket == 24 ? dexr::launch_wide_d_24 : nullptr)
+                          : m->wide_mimic ? (sprint ? (m->wide_modchol ? dexr::launch_wide_s_mc_16 : dexr::launch_wide_s_m_16)
                                                     : (m->wide_modchol ? dexr::launch_wide_mc_16 : dexr::launch_wide_m_16))
                             : sprint      ? dexr::find_wide_sprint_launcher(m->wbucket)
                                           : dexr::find_wide_launcher(m->wbucket);
@@ -430,10 +444,10 @@ int launch_wide_tail(const dexr_model* m, dexr::KernelParams kp, int P, hipStrea
   return rc;
 }
 
-int launch_wide(const dexr_model* m, dexr::KernelParams kp, hipStream_t st) {
+int launch_wide(const dexr_model* m, dexr::KernelParams kp, hipStream_t st, bool f64 = false) {
   const int want = m->tune.longest_first;
   const bool plain = !kp.perm && !kp.bucket && kp.T == 0 && kp.n_comp == 1;
-  {
+  if (!f64) {  // (float64: one launch shape at every batch size -- no tail launch)
     // (policy: OFF.  Measured, 65 536 tracking frames, profiles/r05_tail_launch.txt: LEAP position 1.106 ms in one launch,
     // 1.18-1.29 ms with caps of 16 ... 6 passes; Shadow DexPilot 1.158 (hard frames first) -> 1.24-1.33.  The capped main launch is
     // throughput-bound and gets barely shorter, while the handed-over frames then run at a quarter of the occupancy, after it.)
@@ -449,10 +463,10 @@ int launch_wide(const dexr_model* m, dexr::KernelParams kp, hipStream_t st) {
   const bool by_state = plain && kp.kind == DEXR_KIND_DEXPILOT &&
                         (want == 2 || (want < 0 && kp.n_opt >= 9 && kp.B >= 4 * (int64_t)m->n_cu * 4 * 2 * 4));
   const bool on = plain && (want == 1 || by_state);
-  if (!on) return launch_wide_once(m, kp, st);
+  if (!on) return launch_wide_once(m, kp, st, false, f64);
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-    return launch_wide_once(m, kp, st);  // graph capture: no allocation / cross-stream fencing inside a captured region --
+    return launch_wide_once(m, kp, st, false, f64);  // graph capture: no allocation / cross-stream fencing inside a captured region --
                                          // a captured graph runs the frames in natural order (same answers, the eager
                                          // call's schedule is the faster one for tail-bound batches; documented in dexr.h)
   const size_t B = (size_t)kp.B;
@@ -479,13 +493,13 @@ int launch_wide(const dexr_model* m, dexr::KernelParams kp, hipStream_t st) {
     dexr::KernelParams ks = kp;
     ks.screen = f0;
     ks.screen_sum = sum;
-    rc = launch_wide_once(m, ks, st);
+    rc = launch_wide_once(m, ks, st, false, f64);
     if (rc != DEXR_OK) return rc;
     hipError_t e = dexr_lpt_order_launch(kp.B, f0, sum, 1.3f, key, ws, st);
     if (e != hipSuccess) return fail(DEXR_ERR_HIP, "ordering kernels failed: %s", hipGetErrorString(e));
   }
   kp.perm = ws + dexr_fleet_ws_ints();
-  rc = launch_wide_once(m, kp, st);
+  rc = launch_wide_once(m, kp, st, false, f64);
   HIP_TRY(hipEventRecord(sl.done, st));
   return rc;
 }
@@ -625,9 +639,21 @@ int launch_gen_model(const dexr_model* m, int mode, dexr::KernelParams kp, hipSt
 #ifndef DEXR_RED_SMALL_BATCH
 #define DEXR_RED_SMALL_BATCH 16384
 #endif
-int launch(const dexr_model* m, int mode, int f64, dexr::KernelParams kp, hipStream_t st) {
+// The handle's float64 solve launches run the sixteen-lane kernel's float64 instantiation (dexr_tuning.kernel_f64)
+bool wide_f64_selected(const dexr_model* m) { return !m->gen && m->tune.kernel_f64 == DEXR_KERNEL_WIDE && m->wide_ok; }
+
+// f64_request: a float64 solve the caller asked for (precision = 1, dexr_retarget_f64, float64 sequences) -- the launches that
+// dexr_tuning.kernel_f64 routes; the polish pass (also float64) keeps the register kernel
+int launch(const dexr_model* m, int mode, int f64, dexr::KernelParams kp, hipStream_t st, bool f64_request = false) {
   if (kp.B <= 0) return DEXR_OK;
   if (m->gen) return launch_gen_model(m, mode, kp, st);
+  if (mode == dexr::MODE_SOLVE && f64 && f64_request && wide_f64_selected(m) && !kp.perm && !kp.bucket) {
+    // same damping rules as the float32 launches of the family (modified Cholesky: those of the reduced-variable kernel),
+    // minus the float32 shortcuts (launch_wide_once: no blind steps; the kernel: the float64 rounding floor of F)
+    kp.lam_jump = m->lam_jump_user >= 0.f ? m->lam_jump_user : wide_modchol_rule(m) ? family_lam_jump(m, FAM_REGISTER) : 1.0f;
+    kp.lam_fastdec = family_lam_fastdec(m, FAM_WIDE);
+    return launch_wide(m, kp, st, true);
+  }
   // fleet buckets / frame sequences / padded rows need the kernels with extended addressing (KernelParams)
   const bool ext = kp.perm != nullptr || kp.bucket != nullptr || kp.T > 0 || kp.ld != kp.n_opt;
   if (mode == dexr::MODE_SOLVE && !f64 && selected_family(m) != FAM_REGISTER) {
@@ -790,6 +816,7 @@ void default_tuning(dexr_model* m) {
   t.sprint_max_batch = -1;
   t.sprint_ladder = -1;
   t.tail_passes = -1;
+  t.kernel_f64 = DEXR_KERNEL_AUTO;
 }
 
 // A model in the generic table format (dexr_tables.h): validate every index the general kernel will follow, upload the
@@ -1240,6 +1267,13 @@ int dexr_model_set_tuning(dexr_model* m, const dexr_tuning* tuning) {
   if (t.sprint_max_batch < -1) return fail(DEXR_ERR_INVALID, "sprint_max_batch must be -1 (policy), 0 (off) or a batch size");
   if (t.sprint_ladder < -1 || t.sprint_ladder > 1) return fail(DEXR_ERR_INVALID, "sprint_ladder must be -1, 0 or 1");
   if (t.tail_passes < -1) return fail(DEXR_ERR_INVALID, "tail_passes must be -1 (policy), 0 (off) or a pass count");
+  if (t.kernel_f64 != DEXR_KERNEL_AUTO && t.kernel_f64 != DEXR_KERNEL_REGISTER && t.kernel_f64 != DEXR_KERNEL_WIDE)
+    return fail(DEXR_ERR_INVALID, "kernel_f64 must be DEXR_KERNEL_AUTO, DEXR_KERNEL_REGISTER or DEXR_KERNEL_WIDE (%d)", t.kernel_f64);
+  if (t.kernel_f64 == DEXR_KERNEL_WIDE && m->tune.kernel_f64 != DEXR_KERNEL_WIDE) {
+    if (m->gen || !m->wide_ok) return fail(DEXR_ERR_UNSUPPORTED, "kernel_f64: the model does not fit the sixteen-lane kernel");
+    if (!m->wide_mimic && m->wbucket > 24)
+      return fail(DEXR_ERR_UNSUPPORTED, "kernel_f64: no float64 sixteen-lane kernel for components of more than 24 joints");
+  }
   if (t.persist_from < 0 || t.qchunk < 0 || t.persist_occ < 0 || t.resident_waves < 0 || t.max_blind < 0)
     return fail(DEXR_ERR_INVALID, "negative launch parameter");
   if (!(t.step_cap >= 0) || !(t.lam_jump >= 0) || !(t.lam_fastdec >= 0) || !(t.floor_scale >= 0) || !(t.blind_tol_scale >= 0) || !(t.lam_recover >= 0))
@@ -1266,6 +1300,14 @@ int dexr_model_kernel(const dexr_model* m, int32_t* family, int32_t* bucket, int
   else if (family) *family = m->wide ? DEXR_KERNEL_WIDE : m->red ? DEXR_KERNEL_REDUCED : m->quad ? DEXR_KERNEL_QUAD : m->big ? DEXR_KERNEL_LDS : DEXR_KERNEL_REGISTER;
   if (bucket) *bucket = m->bucket;
   if (chain) *chain = m->tip ? 2 : m->chain ? 1 : 0;
+  return DEXR_OK;
+}
+
+int dexr_model_kernel_f64(const dexr_model* m, int32_t* family, int32_t* bucket) {
+  if (!m) return fail(DEXR_ERR_INVALID, "null argument");
+  const bool wide = wide_f64_selected(m);
+  if (family) *family = m->gen ? DEXR_KERNEL_GENERAL : wide ? DEXR_KERNEL_WIDE : DEXR_KERNEL_REGISTER;
+  if (bucket) *bucket = wide ? (m->wide_mimic ? 16 : m->wbucket) : m->bucket;  // (the variable grid has 16 rows)
   return DEXR_OK;
 }
 
@@ -1315,7 +1357,7 @@ static int retarget_dev_impl(const dexr_model* m, int64_t B, const float* ref, b
   if (status_out) HIP_TRY(hipMemsetAsync(status_out, 0, (size_t)B * sizeof(int32_t), st));
   if (iters_out) HIP_TRY(hipMemsetAsync(iters_out, 0, (size_t)B * sizeof(int32_t), st));
   if (fval_out) HIP_TRY(hipMemsetAsync(fval_out, 0, (size_t)B * sizeof(float), st));
-  int rc = launch(m, dexr::MODE_SOLVE, f64, kp, st);
+  int rc = launch(m, dexr::MODE_SOLVE, f64, kp, st, f64 != 0);
   if (rc != DEXR_OK || f64) return rc;
   return polish_launch(m, kp, opt, st);
 }
@@ -1375,7 +1417,7 @@ static int retarget_host(const dexr_model* m, int64_t B, const float* ref, const
   kp.iters = sg.dev<int32_t>(hc, i_iters);
   kp.fval = sg.dev<float>(hc, i_fval);
   if (verify_every_step) kp.blind_tol = 0.f;  // dexr_retarget_f64 is the validation path: every step it reports has been verified
-  int rc = launch(m, dexr::MODE_SOLVE, f64, kp, hc.st);
+  int rc = launch(m, dexr::MODE_SOLVE, f64, kp, hc.st, f64 != 0);
   if (rc != DEXR_OK) return rc;
   if (!f64) {
     rc = polish_launch(m, kp, opt, hc.st);
@@ -1496,7 +1538,7 @@ int dexr_retarget_seq_dev(const dexr_model* m, int64_t B, int32_t T, const float
   if (status_out) HIP_TRY(hipMemsetAsync(status_out, 0, (size_t)T * (size_t)B * sizeof(int32_t), st));
   // a polish launch cannot be interleaved with the carry: models that need it solve in float64 throughout
   const int f64 = ((opt && opt->precision == 1) || polish_wanted(m, opt)) ? 1 : 0;
-  int rc = launch(m, dexr::MODE_SOLVE, f64, kp, st);
+  int rc = launch(m, dexr::MODE_SOLVE, f64, kp, st, opt && opt->precision == 1);
   if (rc != DEXR_OK) return rc;
   // SeqRetargeting.last_qpos after the last frame = its raw answer (seq_retarget.py:124)
   HIP_TRY(hipMemcpyAsync(last_inout, qpos_raw_out + (size_t)(T - 1) * (size_t)B * m->h.n_opt,

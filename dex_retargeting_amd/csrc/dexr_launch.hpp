@@ -98,6 +98,16 @@ size_t wide_lds_per_wave_mc_16();
 size_t wide_lds_per_wave_16();
 size_t wide_lds_per_wave_24();
 size_t wide_lds_per_wave_32();
+// ... its float64 instantiation (dexr_tuning.kernel_f64 = DEXR_KERNEL_WIDE): four frames per wave, one wave per SIMD; the
+// 16- / 24-row joint grids and the variable grid (the 32-row grid is not built: its float64 registers do not fit without spills)
+hipError_t launch_wide_d_16(const KernelParams&, const WideTable*, dim3, dim3, size_t, hipStream_t);
+hipError_t launch_wide_d_24(const KernelParams&, const WideTable*, dim3, dim3, size_t, hipStream_t);
+hipError_t launch_wide_d_m_16(const KernelParams&, const WideTable*, dim3, dim3, size_t, hipStream_t);
+hipError_t launch_wide_d_mc_16(const KernelParams&, const WideTable*, dim3, dim3, size_t, hipStream_t);
+size_t wide_lds_per_wave_d_16();
+size_t wide_lds_per_wave_d_24();
+size_t wide_lds_per_wave_d_m_16();
+size_t wide_lds_per_wave_d_mc_16();
 static inline wide_launch_fn find_wide_launcher(int bucket) {
   return bucket == 16 ? launch_wide_16 : bucket == 24 ? launch_wide_24 : bucket == 32 ? launch_wide_32 : nullptr;
 }

@@ -29,6 +29,15 @@
 // Damping / termination rules are those of dexr_quad.hpp.
 // SPRINT instantiations (round 5): one frame per wave for small batches and short sequences -- the four rows share the frame's
 // term loop and each tries its own damping value per pass (see the comment at the kernel).
+// F64 instantiations (dexr_tuning.kernel_f64 = DEXR_KERNEL_WIDE; 16- / 24-row joint grids and the variable grid): the same
+// source with the solve stage in float64 -- gradient GV, second-order vectors CF, Jacobian rows JR, trial point XV, target XL,
+// axes / origins AX / OG, the Hessian grid registers, pivots, broadcasts and substitutions (DPP moves and ds_bpermute of a
+// double: two 32-bit ones; v_pk_fma_f32 pairs become two v_fma_f64).  Model constants are the float tables the float64
+// register kernel reads, widened.  One wave per SIMD (512 VGPRs, AGPRs included; one block of four waves and <= 160 KB of LDS
+// per CU); the terms' targets sit in LDS (TGLDS) and the lane's axes / origins are re-read per term, which keeps the register
+// file without spills.  Rules that differ from the float32 instantiation: four frames per wave only (no SPRINT shape, no
+// tail launch); no blind steps (the launch sets blind_tol = 0: every step is verified by a pass at the new point); the
+// rounding floor of F is the float64 register kernel's (16 eps max(|F|, 2e-3)), not floor_scale x |F|.
 #pragma once
 
 #include "dexr_big.hpp"  // sincos_f64
@@ -82,6 +91,50 @@ template <int Q>
 static __device__ __forceinline__ float wquad_bcast(float v) {
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), Q * 0x55, 0xF, 0xF, true));
 }
+// the same exchanges on doubles (float64 instantiation): two 32-bit moves / permutes per value
+static __device__ __forceinline__ double row_sum(double v) { return row_sum64(v); }
+static __device__ __forceinline__ double row_max(double v) {
+  v = fmax(v, wdpp64<0xB1>(v));
+  v = fmax(v, wdpp64<0x4E>(v));
+  v = fmax(v, wdpp64<0x141>(v));
+  v = fmax(v, wdpp64<0x140>(v));
+  return v;
+}
+static __device__ __forceinline__ double stride4_sum(double v) {
+  v += wdpp64<0x128>(v);
+  v += wdpp64<0x124>(v);
+  return v;
+}
+template <int Q>
+static __device__ __forceinline__ double wquad_bcast(double v) {
+  return wdpp64<Q * 0x55>(v);
+}
+static __device__ __forceinline__ float wbperm(int addr, float v) {
+  return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v)));
+}
+static __device__ __forceinline__ double wbperm(int addr, double v) {
+  const int lo = __builtin_amdgcn_ds_bpermute(addr, __double2loint(v));
+  const int hi = __builtin_amdgcn_ds_bpermute(addr, __double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+static __device__ __forceinline__ float wreadlane(float v, int ln) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), ln));
+}
+static __device__ __forceinline__ double wreadlane(double v, int ln) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), ln), __builtin_amdgcn_readlane(__double2loint(v), ln));
+}
+static __device__ __forceinline__ float wmin(float x, float y) { return fminf(x, y); }
+static __device__ __forceinline__ double wmin(double x, double y) { return fmin(x, y); }
+static __device__ __forceinline__ float wmax(float x, float y) { return fmaxf(x, y); }
+static __device__ __forceinline__ double wmax(double x, double y) { return fmax(x, y); }
+static __device__ __forceinline__ float wabs(float x) { return fabsf(x); }
+static __device__ __forceinline__ double wabs(double x) { return fabs(x); }
+static __device__ __forceinline__ float wsqrt(float x) { return __fsqrt_rn(x); }
+static __device__ __forceinline__ float wsqrt_std(float x) { return sqrtf(x); }
+static __device__ __forceinline__ double wsqrt_std(double x) { return sqrt(x); }
+static __device__ __forceinline__ double wsqrt(double x) { return sqrt(x); }
+static __device__ __forceinline__ float wrsqrt(float x) { return __frsqrt_rn(x); }
+static __device__ __forceinline__ double wrsqrt(double x) { return 1.0 / sqrt(x); }
 
 // -DDEXR_WIDE_PROF=1 (tools/prof_wide_stages.sh; never in the shipped library): wave 0 of block 0 accumulates the cycles
 // (s_memtime) of every stage of its passes and adds them to kp.g64out[stage] when it retires.
@@ -109,6 +162,18 @@ static __device__ __forceinline__ float wquad_bcast(float v) {
 #endif
 
 typedef float wv2 __attribute__((ext_vector_type(2)));  // register pair: v_pk_fma_f32 / v_pk_mul_f32 operands
+typedef double wd2 __attribute__((ext_vector_type(2)));  // float64 instantiation: two v_fma_f64
+// real type of the solve stage: float32 (F64 = false) or float64
+template <bool F64> struct WideReal {
+  typedef float R;
+  typedef wv2 R2;
+  typedef float4 R4;
+};
+template <> struct WideReal<true> {
+  typedef double R;
+  typedef wd2 R2;
+  typedef double4 R4;
+};
 
 #ifndef DEXR_WIDE_MINW
 #define DEXR_WIDE_MINW 2
@@ -117,8 +182,10 @@ typedef float wv2 __attribute__((ext_vector_type(2)));  // register pair: v_pk_f
 // blockDim.x = 256 (4 waves x 4 frames); dynamic LDS per wave = wide_lds_bytes(NMAX)
 // NMAX: size of the Hessian grid (joints; with MIMIC: optimised VARIABLES, mimic joints folded into their source's
 // column).  NJ: joints the kinematics can hold.
-template <int NMAX, bool MIMIC>
+// F64: the solve stage's arrays (AX / OG, XV / QJ, GV, CF, the term blocks, JR, XL) hold doubles -- RS bytes per value.
+template <int NMAX, bool MIMIC, bool F64 = false>
 struct WideLds {
+  static constexpr int RS = F64 ? 8 : 4;
   static constexpr int NJ = MIMIC ? 32 : NMAX;
   static constexpr int NR = NMAX / 4;
   static constexpr int NRP = NR <= 4 ? 4 : 8;          // class chunk of a Jacobian row, padded for 16-byte reads
@@ -137,29 +204,34 @@ struct WideLds {
   static constexpr int SLOT0 = TM + (MIMIC ? 128 : 0);
   // per frame slot
   static constexpr int P = 0;                          // 16 frames x 3 doubles
-  static constexpr int AX = P + 384;                   // NJ x 4 floats
-  static constexpr int OG = AX + NJ * 16;              // NJ x 4 floats
-  static constexpr int SC = OG + NJ * 16;              // NJ x 2 doubles: (sin q, cos q) of a revolute joint, (q, -) of a
+  static constexpr int AX = P + 384;                   // NJ x 4 reals
+  static constexpr int OG = AX + NJ * 4 * RS;          // NJ x 4 reals
+  static constexpr int SC = OG + NJ * 4 * RS;          // NJ x 2 doubles: (sin q, cos q) of a revolute joint, (q, -) of a
                                                        // prismatic one, computed by the joint's slot lane
-  static constexpr int XV = SC + NJ * 16;              // NJ floats: joint values of the trial point (MIMIC: variables)
-  static constexpr int QJ = XV + NJ * 4;               // MIMIC: NJ floats, values of the fixed joints of the frame
-  static constexpr int GV = QJ + (MIMIC ? NJ * 4 : 0); // NMAX floats: gradient
-  static constexpr int CF = GV + NMAX * 4;             // NJ x 4 floats: second-order vectors
-  static constexpr int TB = CF + NJ * 16;              // 16 terms x 16 floats (MIMIC: reused for the second-order sums)
-  static constexpr int JR = TB + 1024;                 // 3 rows x 4 classes x NRP floats
-  static constexpr int FS = JR + 3 * 4 * NRP * 4;      // 32 bytes: row of the frame's inputs / of its item, item, frame of
+  static constexpr int XV = SC + NJ * 16;              // NJ reals: joint values of the trial point (MIMIC: variables)
+  static constexpr int QJ = XV + NJ * RS;              // MIMIC: NJ reals, values of the fixed joints of the frame
+  static constexpr int GV = QJ + (MIMIC ? NJ * RS : 0); // NMAX reals: gradient
+  static constexpr int CF = GV + NMAX * RS;            // NJ x 4 reals: second-order vectors
+  static constexpr int TB = CF + NJ * 4 * RS;          // 16 terms x 16 reals (MIMIC: reused for the second-order sums)
+  static constexpr int JR = TB + 256 * RS;             // 3 rows x 4 classes x NRP reals
+  static constexpr int FS = JR + 3 * 4 * NRP * RS;     // 32 bytes: row of the frame's inputs / of its item, item, frame of
                                                        // the sequence, DexPilot bits (registers are the scarce resource)
-  static constexpr int XL = FS + 32;                   // NMAX floats: regularisation target (the frame's start row)
+  static constexpr int XL = FS + 32;                   // NMAX reals: regularisation target (the frame's start row)
   // (TGLDS: the terms' target vectors / weights in 256 B of the frame slot instead of four registers of the term's lane.  It
   // takes the 24-row grid from 2 spilled VGPRs to none -- and 1 KB of LDS per wave, 8 KB per CU, which is what the small-component
   // kernels of a FLEET batch need to sit beside the heavy model's blocks: same box, fleet step 0.750 -> 0.79-0.85 ms
   // (profiles/r05_fleet_ab_tg_lds_same_box.txt).  Off.)
-  static constexpr bool TGLDS = false;
-  static constexpr int TG = XL + NMAX * 4;
-  static constexpr int SLOT = TG + (TGLDS ? 256 : 0);
+  // (float64: on -- the four doubles would be eight more live registers across the pass loop)
+  static constexpr bool TGLDS = F64;
+  static constexpr int TG = XL + NMAX * RS;
+  static constexpr int SLOT = TG + (TGLDS ? 64 * RS : 0);
   // LDS decides the occupancy: two blocks of four waves per CU (160 KB); the 16-row joint grid is built for three
-  static_assert(2 * 4 * (SLOT0 + 4 * SLOT) <= 160 * 1024, "two blocks per CU must fit");
-  static_assert(MIMIC || NMAX != 16 || 3 * (4 * (SLOT0 + 4 * SLOT) + 512) <= 160 * 1024, "three blocks per CU must fit");
+  static_assert(F64 || 2 * 4 * (SLOT0 + 4 * SLOT) <= 160 * 1024, "two blocks per CU must fit");
+  static_assert(F64 || MIMIC || NMAX != 16 || 3 * (4 * (SLOT0 + 4 * SLOT) + 512) <= 160 * 1024, "three blocks per CU must fit");
+  // float64: one block of four waves per CU (one wave per SIMD); the double4 views of the slot need 32-byte alignment
+  static_assert(!F64 || 4 * (SLOT0 + 4 * SLOT) <= 160 * 1024, "one block per CU must fit");
+  static_assert(!F64 || (SLOT0 % 32 == 0 && SLOT % 32 == 0 && AX % 32 == 0 && OG % 32 == 0 && CF % 32 == 0 && TB % 32 == 0 &&
+                         JR % 32 == 0 && TG % 32 == 0), "float64 slot alignment");
   static constexpr int WAVE = SLOT0 + 4 * SLOT;
 };
 
@@ -170,13 +242,22 @@ struct WideLds {
 // row s forms the columns and outer products of terms s, s + 4, ... and the partial Hessians / gradients / second-order vectors
 // are summed across the rows by an xor butterfly (ds_bpermute, lane ^ 16, lane ^ 32: every row ends with the same bits).  Same
 // damping rules, same sequence of trial points up to the summation order of the Hessian; only row 0 writes results.
-template <int NMAX, bool MIMIC, bool MODCHOL, bool SPRINT = false>
-__global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const KernelParams kp, const dexr_comp_table* __restrict__ comps,
-                                                                         const WideTable* __restrict__ wtabs) {
+// F64 (float64 instantiation, see the header comment): one wave per SIMD, 512 VGPRs.
+template <int NMAX, bool MIMIC, bool MODCHOL, bool SPRINT = false, bool F64 = false>
+__global__ void __launch_bounds__(256, F64 ? 1 : DEXR_WIDE_MINW) dexr_wide_kernel(const KernelParams kp, const dexr_comp_table* __restrict__ comps,
+                                                                                   const WideTable* __restrict__ wtabs) {
   static_assert(NMAX == 16 || NMAX == 24 || NMAX == 32, "bucket");
   static_assert(!MIMIC || NMAX == 16, "the variable grid of the mimic kernel has 16 rows");
+  static_assert(!(F64 && SPRINT), "the float64 instantiation holds four frames per wave");
+  typedef typename WideReal<F64>::R wreal;    // real type of the solve stage
+  typedef typename WideReal<F64>::R2 wreal2;  // register pair (float32: v_pk_fma_f32 operands)
+  typedef typename WideReal<F64>::R4 wreal4;  // four reals of an LDS row
+  auto mk4 = [](wreal x, wreal y, wreal z, wreal w) -> wreal4 {
+    if constexpr (F64) return make_double4(x, y, z, w);
+    else return make_float4(x, y, z, w);
+  };
   constexpr int FPW = SPRINT ? 1 : 4;  // frames a wave holds at a time
-  using L = WideLds<NMAX, MIMIC>;
+  using L = WideLds<NMAX, MIMIC, F64>;
   constexpr int NJ = L::NJ;
   constexpr int NR = NMAX / 4;
   constexpr int NRP = L::NRP;
@@ -217,19 +298,19 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   constexpr int TMS = MIMIC ? 2 : XTS;  // words between consecutive terms' mask pairs
   unsigned char* sbase = wbase + L::SLOT0 + (size_t)slot * L::SLOT;
   double* Pl = reinterpret_cast<double*>(sbase + L::P);
-  float* AXl = reinterpret_cast<float*>(sbase + L::AX);
-  float* OGl = reinterpret_cast<float*>(sbase + L::OG);
+  wreal* AXl = reinterpret_cast<wreal*>(sbase + L::AX);
+  wreal* OGl = reinterpret_cast<wreal*>(sbase + L::OG);
   double* SCl = reinterpret_cast<double*>(sbase + L::SC);
-  float* XVl = reinterpret_cast<float*>(sbase + L::XV);
-  float* QJl = reinterpret_cast<float*>(sbase + L::QJ);
-  float* GVl = reinterpret_cast<float*>(sbase + L::GV);
-  float* CFl = reinterpret_cast<float*>(sbase + L::CF);
-  float* TBl = reinterpret_cast<float*>(sbase + L::TB);
-  float* JRl = reinterpret_cast<float*>(sbase + L::JR);
+  wreal* XVl = reinterpret_cast<wreal*>(sbase + L::XV);
+  wreal* QJl = reinterpret_cast<wreal*>(sbase + L::QJ);
+  wreal* GVl = reinterpret_cast<wreal*>(sbase + L::GV);
+  wreal* CFl = reinterpret_cast<wreal*>(sbase + L::CF);
+  wreal* TBl = reinterpret_cast<wreal*>(sbase + L::TB);
+  wreal* JRl = reinterpret_cast<wreal*>(sbase + L::JR);
   int64_t* FS64 = reinterpret_cast<int64_t*>(sbase + L::FS);     // [0] irow, [1] lrow, [2] item
   int32_t* FS32 = reinterpret_cast<int32_t*>(sbase + L::FS) + 6;  // [0] frame of the sequence, [1] DexPilot bits
-  float* XLl = reinterpret_cast<float*>(sbase + L::XL);
-  float* TGl = reinterpret_cast<float*>(sbase + L::TG);
+  wreal* XLl = reinterpret_cast<wreal*>(sbase + L::XL);
+  wreal* TGl = reinterpret_cast<wreal*>(sbase + L::TG);
 
   const dexr_comp_table& tb = comps[comp];
   const WideTable& wt = wtabs[comp];
@@ -237,7 +318,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   const int ng = MIMIC ? tb.n_var : nj;  // rows of the Hessian grid in use
   const int depth = wt.depth;
   const bool fk_rows3 = wt.n_chain <= 5;  // three lanes per kinematic chain (see fk)
-  const float delta = kp.norm_delta;
+  const wreal delta = kp.norm_delta;
   const int64_t nB = kp.bucket ? (int64_t)kp.bucket[1] : kp.B;
   const int64_t pbase = kp.bucket ? (int64_t)kp.bucket[0] : 0;
   auto row_of = [&](int64_t it) -> int64_t { return kp.perm ? (int64_t)kp.perm[pbase + it] : it; };
@@ -327,7 +408,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   // MIMIC: the joints that move with this lane's variable (its own joint first) and their dq/dx; the fixed joints in
   // this lane's joint slots (their values go to LDS once per frame)
   int famk[FAM];
-  float famm[FAM];
+  wreal famm[FAM];
   bool fsfix[NFS];
 
   int fam_max = 0;  // wave-uniform: the largest family of the component
@@ -358,17 +439,17 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   auto f_lrow = [&]() -> int64_t { return FS64[1]; };
   auto f_nst = [&]() -> uint32_t { return (uint32_t)FS32[1]; };
   bool active = false;
-  float xj[NJ2], xacc[NJ2];  // own joints: trial value, accepted value (the regularisation target is in LDS: XLl)
+  wreal xj[NJ2], xacc[NJ2];  // own joints: trial value, accepted value (the regularisation target is in LDS: XLl)
   // (the gradient at the accepted point, incl. regulariser, lives in LDS: GVl)
   constexpr int NP = NR / 2;             // column pairs of the local Hessian block
-  wv2 Ha[NR][NP];                        // Hessian grid entries (4 i + a, 4 j + b), j <= i, at the accepted point;
+  wreal2 Ha[NR][NP];                        // Hessian grid entries (4 i + a, 4 j + b), j <= i, at the accepted point;
                                          // pair jj holds local columns 2 jj, 2 jj + 1 (packed FMAs)
 #pragma unroll
   for (int s = 0; s < NJ2; ++s) { xj[s] = 0; xacc[s] = 0; }
 #pragma unroll
   for (int i = 0; i < NR; ++i)
 #pragma unroll
-    for (int j = 0; j < NP; ++j) Ha[i][j] = wv2{0.f, 0.f};
+    for (int j = 0; j < NP; ++j) Ha[i][j] = wreal2{0.f, 0.f};
 
   // KPLDS (round 6): a row that takes a frame copies the frame's input block -- the 21 raw keypoints (252 B) or its n_ref
   // ready-made rows -- into the (then idle) term-block area of its slot with ONE coalesced round of loads, next to the loads of
@@ -377,14 +458,14 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   // 5-7 k of a pass's ~43 k cycles at 65 536 frames (tools/prof_wide_stages.sh), and the 12-byte reads fetched every line of
   // the block two or three times.  (Not at n = 32, whose terms re-read their targets in every pass -- TGREG.)
   constexpr bool KPLDS = NMAX <= 24;
-  auto ref_row = [&](ColdParams& kp, int row, float (&rv)[3]) {
+  auto ref_row = [&](ColdParams& kp, int row, wreal (&rv)[3]) {
     if (KPLDS) {
-      const float* blk = TBl;
+      const float* blk = reinterpret_cast<const float*>(TBl);  // (the frame's input block: float32 as read)
       if (kp.kpts) {
         const uint32_t hm = (uint32_t)__float_as_int(FO[row * 4 + 3]);
         const int ta = (int)(hm & 0xFFu), o = (int)((hm >> 8) & 0xFFu);
 #pragma unroll
-        for (int i = 0; i < 3; ++i) rv[i] = blk[ta * 3 + i] - (o != 0xFF ? blk[(o != 0xFF ? o : 0) * 3 + i] : 0.f);
+        for (int i = 0; i < 3; ++i) rv[i] = (wreal)blk[ta * 3 + i] - (o != 0xFF ? (wreal)blk[(o != 0xFF ? o : 0) * 3 + i] : (wreal)0);
       } else {
 #pragma unroll
         for (int i = 0; i < 3; ++i) rv[i] = blk[row * 3 + i];
@@ -401,7 +482,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       if (o >= 0) {
         const float* pb = frame + o * 3;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) rv[i] = pa[i] - pb[i];
+        for (int i = 0; i < 3; ++i) rv[i] = (wreal)pa[i] - (wreal)pb[i];
       } else {
 #pragma unroll
         for (int i = 0; i < 3; ++i) rv[i] = pa[i];
@@ -412,13 +493,13 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       for (int i = 0; i < 3; ++i) rv[i] = r[i];
     }
   };
-  auto xl = [&](ColdParams& kp, int s, const float* lastp, int t_seq) -> float {  // regularisation target of own joint s (see dexr_quad.hpp)
-    float v;
+  auto xl = [&](ColdParams& kp, int s, const float* lastp, int t_seq) -> wreal {  // regularisation target of own joint s (see dexr_quad.hpp)
+    wreal v;
     if (seq && t_seq > 0)
       v = __hip_atomic_load(const_cast<float*>(lastp) + tb.api[jsel(s)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else
       v = lastp[tb.api[jsel(s)]];
-    return seq ? fminf(fmaxf(v, BOXw[2 * jo_[s]] + kp.clip_eps), BOXw[2 * jo_[s] + 1] - kp.clip_eps) : v;
+    return seq ? wmin(wmax(v, (wreal)BOXw[2 * jo_[s]] + (wreal)kp.clip_eps), (wreal)BOXw[2 * jo_[s] + 1] - (wreal)kp.clip_eps) : v;
   };
   // Target vector and weight of the lane's own term (lane t evaluates term t in every pass): constant while the row's frame
   // is being solved, so they are formed ONCE when the frame is taken and kept in four registers of that lane -- re-reading
@@ -426,7 +507,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   // traffic and its algorithmic bytes.  (Not at n = 32, where the Hessian grid already spills.)
   constexpr bool TGREG = NMAX <= 24;
   constexpr bool TGLDS = L::TGLDS;  // ... in 16 bytes of the frame slot per term where the grid leaves no registers (n = 24)
-  float tgt[4] = {0.f, 0.f, 0.f, 1.f};
+  wreal tgt[4] = {0.f, 0.f, 0.f, 1.f};
   // frames of the lane's own term (table reads indexed by the lane: taken once, here, where the lane index is still a
   // loop-invariant the compiler may use -- inside the pass loop it is opaque, see the top of the loop)
   const int my_ft = l < nt ? tb.term_task[l] : 0, my_fo = l < nt ? tb.term_origin[l] : -1;
@@ -443,7 +524,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
     FS64[2] = it;
     FS32[0] = t;
     // every global read of the hand-out is issued here, in one round: the input block, last_qpos, the state word
-    float xl_pre[NJ2];
+    wreal xl_pre[NJ2];
 #pragma unroll
     for (int s = 0; s < NJ2; ++s) xl_pre[s] = jopt[s] ? xl(kp, s, lastp, t_seq) : 0.f;
     const uint32_t st_pre = (dexpilot && !(seq && t_seq > 0) && kp.state) ? kp.state[lrow] : 0u;
@@ -455,21 +536,21 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       for (int i = 0; i < 4; ++i) blk[i] = (l + 16 * i < cnt) ? src[l + 16 * i] : 0.f;
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        if (l + 16 * i < cnt) TBl[l + 16 * i] = blk[i];
-      for (int i = l + 64; i < cnt; i += 16) TBl[i] = src[i];  // (more than 21 keypoints per frame)
+        if (l + 16 * i < cnt) reinterpret_cast<float*>(TBl)[l + 16 * i] = blk[i];
+      for (int i = l + 64; i < cnt; i += 16) reinterpret_cast<float*>(TBl)[i] = src[i];  // (more than 21 keypoints per frame)
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int s = 0; s < NJ2; ++s) {
       xj[s] = 0;
-      float xlast = 0;
+      wreal xlast = 0;
       if (jopt[s]) {
         xlast = xl_pre[s];
-        const float v = (kp.x0 && !(seq && t_seq > 0)) ? kp.x0[lrow * ld + tb.api[jsel(s)]] : xlast;
-        xj[s] = fminf(fmaxf(v, BOXw[2 * jo_[s]]), BOXw[2 * jo_[s] + 1]);
+        const wreal v = (kp.x0 && !(seq && t_seq > 0)) ? kp.x0[lrow * ld + tb.api[jsel(s)]] : xlast;
+        xj[s] = wmin(wmax(v, (wreal)BOXw[2 * jo_[s]]), (wreal)BOXw[2 * jo_[s] + 1]);
       } else if (jfix[s]) {
-        xj[s] = tb.mult[jsel(s)] * kp.fixed[irow * kp.ldf + tb.src_idx[jsel(s)]] + tb.off[jsel(s)];
+        xj[s] = (wreal)tb.mult[jsel(s)] * (wreal)kp.fixed[irow * kp.ldf + tb.src_idx[jsel(s)]] + (wreal)tb.off[jsel(s)];
       }
       xacc[s] = xj[s];
       if (jin[s]) XLl[jo_[s]] = xlast;
@@ -479,7 +560,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       for (int s = 0; s < NFS; ++s)
         if (fsfix[s]) {
           const int k = l + 16 * s;
-          QJl[k] = tb.mult[k] * kp.fixed[irow * kp.ldf + tb.src_idx[k]] + tb.off[k];
+          QJl[k] = (wreal)tb.mult[k] * (wreal)kp.fixed[irow * kp.ldf + tb.src_idx[k]] + (wreal)tb.off[k];
         }
     }
     if (dexpilot) {  // projection bits (optimizer.py:466-476)
@@ -489,11 +570,11 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       // for ten dependent load round trips each time a row takes a new frame: tools/prof_wide_stages.sh showed 5 k of a
       // pass's 39 k cycles going to this hand-out at 65 536 frames.
       const uint32_t st = (seq && t_seq > 0) ? nst : st_pre;
-      float dist = 0.f;
+      wreal dist = 0.f;
       if (l < n_pair) {
-        float rv[3];
+        wreal rv[3];
         ref_row(kp, l, rv);
-        dist = sqrtf(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]);
+        dist = wsqrt_std(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]);
       }
       bool bb = false;
       if (l < len_s1) {
@@ -521,27 +602,27 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
     __builtin_amdgcn_wave_barrier();
   };
   // target vector and weight of one term (optimizer.py:246, 479-507)
-  auto term_target = [&](ColdParams& kp, int row, float (&tv)[3], float& wgt) {
-    float rv[3];
+  auto term_target = [&](ColdParams& kp, int row, wreal (&tv)[3], wreal& wgt) {
+    wreal rv[3];
     ref_row(kp, row, rv);
     wgt = 1.f;
     if (dexpilot) {
       if (row < n_pair) {
         if ((f_nst() >> row) & 1u) {
-          const float dist = sqrtf(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]);
-          const float eta = row < len_s1 ? kp.eta1 : kp.eta2;
+          const wreal dist = wsqrt_std(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]);
+          const wreal eta = row < len_s1 ? kp.eta1 : kp.eta2;
 #pragma unroll
           for (int i = 0; i < 3; ++i) tv[i] = (rv[i] / (dist + 1e-6f)) * eta;
           wgt = row < len_s1 ? 200.f : 400.f;
           return;
         }
       } else {
-        wgt = (float)(n_pair + F_);
+        wgt = (wreal)(n_pair + F_);
       }
 #pragma unroll
       for (int i = 0; i < 3; ++i) tv[i] = rv[i] * kp.scaling;
     } else {
-      const float sc = (kp.kind == DEXR_KIND_VECTOR) ? kp.scaling : 1.f;
+      const wreal sc = (kp.kind == DEXR_KIND_VECTOR) ? kp.scaling : 1.f;
 #pragma unroll
       for (int i = 0; i < 3; ++i) tv[i] = rv[i] * sc;
     }
@@ -549,14 +630,14 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
 
   // (called by every lane of a row right after load_frame)
   auto load_target = [&]() {
-    if (TGREG && l < nt) {
-      float tv[3], wgt;
+    if ((TGREG || TGLDS) && l < nt) {
+      wreal tv[3], wgt;
       int row = my_ref;
       asm volatile("" : "+v"(row));  // (opaque: the 64-bit offsets of this row into the keypoint map are formed here, in the
                                      // cold path, not kept -- in scratch -- across the pass loop)
       term_target(cold(), row, tv, wgt);
       if (TGLDS) {
-        *reinterpret_cast<float4*>(TGl + l * 4) = make_float4(tv[0], tv[1], tv[2], wgt);  // (read by the same lane only)
+        *reinterpret_cast<wreal4*>(TGl + l * 4) = mk4(tv[0], tv[1], tv[2], wgt);  // (read by the same lane only)
       } else {
         tgt[0] = tv[0]; tgt[1] = tv[1]; tgt[2] = tv[2]; tgt[3] = wgt;
       }
@@ -571,7 +652,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   FS32[1] = 0;
   if (l < NMAX) XLl[l] = 0.f;
   if (NJ2 > 1 && l + 16 < NMAX) XLl[l + 16] = 0.f;
-  if (TGLDS) *reinterpret_cast<float4*>(TGl + l * 4) = make_float4(0.f, 0.f, 0.f, 1.f);
+  if (TGLDS) *reinterpret_cast<wreal4*>(TGl + l * 4) = mk4(0.f, 0.f, 0.f, 1.f);
   // frames on the fixed base never move
   if (l < tb.n_base_frame) {
 #pragma unroll
@@ -650,8 +731,8 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
             pi += scs * n2;
           }
           if (cb & 0x80u) {  // this chain publishes the joint: each of its lanes its own coordinate
-            AXl[k * 4 + ri] = (float)r2;
-            OGl[k * 4 + ri] = (float)pi;
+            AXl[k * 4 + ri] = (wreal)r2;
+            OGl[k * 4 + ri] = (wreal)pi;
             const int fbe = __float_as_int(x3.x);
             const int fb = fbe & 0xFF, fe = fbe >> 8;
             for (int f = fb; f < fe; ++f) {
@@ -671,7 +752,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pp[3] = {0, 0, 0};
     // the tables of step s + 1 are fetched while step s is computed (two LDS round trips per step off the chain) --
     // except in the three-waves-per-SIMD build of the 16-row grid, where the 20 extra live registers spill
-    constexpr bool PREFETCH = MIMIC || NMAX > 16;
+    constexpr bool PREFETCH = !F64 && (MIMIC || NMAX > 16);  // (float64: not either -- its registers are taken)
     unsigned cb = depth > 0 ? CH[l * 16] : 0xFFu;
     int kf = cb != 0xFFu ? (int)(cb & 0x7Fu) : 0;
     float4 x0 = *reinterpret_cast<const float4*>(XT + kf * XTS);
@@ -722,8 +803,8 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
           for (int i = 0; i < 3; ++i) pp[i] += q * Rn[3 * i + 2];
         }
         if (cb & 0x80u) {  // this lane publishes the joint
-          *reinterpret_cast<float4*>(AXl + k * 4) = make_float4((float)R[2], (float)R[5], (float)R[8], 0.f);
-          *reinterpret_cast<float4*>(OGl + k * 4) = make_float4((float)pp[0], (float)pp[1], (float)pp[2], 0.f);
+          *reinterpret_cast<wreal4*>(AXl + k * 4) = mk4((wreal)R[2], (wreal)R[5], (wreal)R[8], 0.f);
+          *reinterpret_cast<wreal4*>(OGl + k * 4) = mk4((wreal)pp[0], (wreal)pp[1], (wreal)pp[2], 0.f);
           const int fbe = __float_as_int(x3.x);
           const int fb = fbe & 0xFF, fe = fbe >> 8;
           for (int f = fb; f < fe; ++f) {
@@ -744,21 +825,21 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   };
 
   // ---- value / gradient (own joints) / Hessian grid at the kinematic state in LDS ------------------------------------
-  float gnew[NJ2];
-  wv2 Hn[NR][NP];
+  wreal gnew[NJ2];
+  wreal2 Hn[NR][NP];
   // SPRINT assembles a model only at a point it has already decided to keep: the new Hessian is accumulated straight into the
   // accepted one's registers (36 fewer live registers at n = 24 than with a separate Hn; four frames per wave need both, the
   // decision comes after the assembly there)
-  wv2 (&Hx)[NR][NP] = SPRINT ? Ha : Hn;
+  wreal2 (&Hx)[NR][NP] = SPRINT ? Ha : Hn;
   // (1) lane t evaluates term t; returns F (identical in the 16 lanes of the row)
   auto terms = [&]() -> double {
     double Fv = 0;
     if (l < nt) {
       const int ft = my_ft, fo = my_fo;
       double rd[3];
-      float tv[3], wgt;
+      wreal tv[3], wgt;
       if (TGLDS) {
-        const float4 tg = *reinterpret_cast<const float4*>(TGl + l * 4);
+        const wreal4 tg = *reinterpret_cast<const wreal4*>(TGl + l * 4);
         tv[0] = tg.x; tv[1] = tg.y; tv[2] = tg.z; wgt = tg.w;
       } else if (TGREG) {
         tv[0] = tgt[0]; tv[1] = tgt[1]; tv[2] = tgt[2]; wgt = tgt[3];
@@ -767,25 +848,25 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
         asm volatile("" : "+v"(row));
         term_target(cold(), row, tv, wgt);  // (n = 32: every pass)
       }
-      float ptf[3], pof[3] = {0, 0, 0};
+      wreal ptf[3], pof[3] = {0, 0, 0};
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         const double pt = Pl[ft * 3 + i];
         const double po = fo >= 0 ? Pl[fo * 3 + i] : 0.0;
         rd[i] = pt - po - (double)tv[i];
-        ptf[i] = (float)pt;
-        pof[i] = (float)po;
+        ptf[i] = (wreal)pt;
+        pof[i] = (wreal)po;
       }
       const double w = (double)kp.inv_norm * (double)wgt;
-      float fvec[3], hw[3], kap = 0;
+      wreal fvec[3], hw[3], kap = 0;
       if (per_coord) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
           const double ee = rd[i], ae = fabs(ee);
           const bool quad = ae < beta;
           Fv += w * (quad ? 0.5 * ee * ee * ibeta : ae - 0.5 * beta);
-          fvec[i] = (float)(w * (quad ? ee * ibeta : (ee > 0 ? 1.0 : -1.0)));
-          hw[i] = (float)(w * (quad ? ibeta : (newton ? 0.0 : 1.0 / ae)));
+          fvec[i] = (wreal)(w * (quad ? ee * ibeta : (ee > 0 ? 1.0 : -1.0)));
+          hw[i] = (wreal)(w * (quad ? ibeta : (newton ? 0.0 : 1.0 / ae)));
         }
       } else {
         const double d2 = rd[0] * rd[0] + rd[1] * rd[1] + rd[2] * rd[2];
@@ -796,22 +877,22 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
         const double psi = w * id;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          fvec[i] = (float)(psi * rd[i]);
-          hw[i] = (float)psi;
+          fvec[i] = (wreal)(psi * rd[i]);
+          hw[i] = (wreal)psi;
         }
         // (round 6) the Huber curvature psi (I - r r^T / d^2) of the linear regime is psi P with P a PROJECTION (P = P^T P):
         // J^T (psi P) J = (sqrt(psi) P J)^T (sqrt(psi) P J) -- three weighted rows (c_i - r^_i (r^ . c)) instead of three rows plus
         // a fourth, subtracted rank-one row: a quarter fewer outer products in the term loop.  rq = r^ there, 0 in the
         // quadratic regime (P = I).
-        kap = quad ? 0.f : (float)id;
+        kap = quad ? 0.f : (wreal)id;
       }
-      float* T = TBl + l * 16;
+      wreal* T = TBl + l * 16;
       // the Hessian is accumulated as sum_k (sqrt(w_k) J_k) (sqrt(w_k) J_k)^T: the square roots of the row weights travel with
       // the term, and so does rq (the unit residual where the Huber loss is linear, else 0): see above
-      *reinterpret_cast<float4*>(T) = make_float4((float)rd[0] * kap, (float)rd[1] * kap, (float)rd[2] * kap, 0.f);  // rq (kap: 1 / d or 0)
-      *reinterpret_cast<float4*>(T + 4) = make_float4(fvec[0], fvec[1], fvec[2], __fsqrt_rn(hw[0]));
-      *reinterpret_cast<float4*>(T + 8) = make_float4(ptf[0], ptf[1], ptf[2], __fsqrt_rn(hw[1]));
-      *reinterpret_cast<float4*>(T + 12) = make_float4(pof[0], pof[1], pof[2], __fsqrt_rn(hw[2]));
+      *reinterpret_cast<wreal4*>(T) = mk4((wreal)rd[0] * kap, (wreal)rd[1] * kap, (wreal)rd[2] * kap, 0.f);  // rq (kap: 1 / d or 0)
+      *reinterpret_cast<wreal4*>(T + 4) = mk4(fvec[0], fvec[1], fvec[2], wsqrt(hw[0]));
+      *reinterpret_cast<wreal4*>(T + 8) = mk4(ptf[0], ptf[1], ptf[2], wsqrt(hw[1]));
+      *reinterpret_cast<wreal4*>(T + 12) = mk4(pof[0], pof[1], pof[2], wsqrt(hw[2]));
     }
     // regulariser of the own joints
 #pragma unroll
@@ -829,14 +910,17 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   auto model_rest = [&]() {
     // (2) own joints' axes / origins; accumulators of the pass: data-term gradient and second-order vector
     constexpr int NCOL = MIMIC ? FAM : NJ2;  // joints whose columns this lane forms
-    float jax[NCOL][3], jog[NCOL][3], jcf[NCOL][3];
-#pragma unroll
-    for (int s = 0; s < NCOL; ++s) {
+    wreal jax[NCOL][3], jog[NCOL][3], jcf[NCOL][3];
+    auto load_axes = [&](int s) {
       const int kj = MIMIC ? (famk[s] >= 0 ? famk[s] : 0) : (jin[s] ? jo_[s] : 0);
-      const float4 av = *reinterpret_cast<const float4*>(AXl + kj * 4);
-      const float4 ov = *reinterpret_cast<const float4*>(OGl + kj * 4);
+      const wreal4 av = *reinterpret_cast<const wreal4*>(AXl + kj * 4);
+      const wreal4 ov = *reinterpret_cast<const wreal4*>(OGl + kj * 4);
       jax[s][0] = av.x; jax[s][1] = av.y; jax[s][2] = av.z;
       jog[s][0] = ov.x; jog[s][1] = ov.y; jog[s][2] = ov.z;
+    };
+#pragma unroll
+    for (int s = 0; s < NCOL; ++s) {
+      if (!F64) load_axes(s);
       jcf[s][0] = 0; jcf[s][1] = 0; jcf[s][2] = 0;
     }
 #pragma unroll
@@ -844,23 +928,27 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
 #pragma unroll
     for (int i = 0; i < NR; ++i)
 #pragma unroll
-      for (int j = 0; j < NP; ++j) Hx[i][j] = wv2{0.f, 0.f};
+      for (int j = 0; j < NP; ++j) Hx[i][j] = wreal2{0.f, 0.f};
     // packed views of the two joint slots (NJ2 == 2, joint-space grids): axes / origins, accumulators, per-lane masks
     constexpr int S1 = (MIMIC || NJ2 == 2) ? 1 : 0;  // (MIMIC: family joints 0 and 1 of the lane's variable)
-    wv2 jax2[3], jog2[3], jcf2[3], gnew2 = wv2{0.f, 0.f};
+    wreal2 jax2[3], jog2[3], jcf2[3], gnew2 = wreal2{0.f, 0.f};
+    auto pack_axes = [&]() {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      jax2[i] = wv2{jax[0][i], jax[S1][i]};
-      jog2[i] = wv2{jog[0][i], jog[S1][i]};
-      jcf2[i] = wv2{0.f, 0.f};
-    }
-    const wv2 jm2 = wv2{jopt[0] ? 1.f : 0.f, jopt[NJ2 - 1] ? 1.f : 0.f};  // optimised joints only
+      for (int i = 0; i < 3; ++i) {
+        jax2[i] = wreal2{jax[0][i], jax[S1][i]};
+        jog2[i] = wreal2{jog[0][i], jog[S1][i]};
+      }
+    };
+    if (!F64) pack_axes();
+#pragma unroll
+    for (int i = 0; i < 3; ++i) jcf2[i] = wreal2{0.f, 0.f};
+    const wreal2 jm2 = wreal2{jopt[0] ? 1.f : 0.f, jopt[NJ2 - 1] ? 1.f : 0.f};  // optimised joints only
     // MIMIC: family joints 0 / 1 of this lane's variable -- present?, their bit positions, dq/dx, revolute?
     const int fk2x = MIMIC ? (famk[0] >= 0 ? famk[0] : 0) : 0, fk2y = MIMIC ? (famk[FAM > 1 ? 1 : 0] >= 0 ? famk[FAM > 1 ? 1 : 0] : 0) : 0;
-    const wv2 fon2 = MIMIC ? wv2{famk[0] >= 0 ? 1.f : 0.f, (fam_max > 1 && famk[FAM > 1 ? 1 : 0] >= 0) ? 1.f : 0.f} : wv2{0.f, 0.f};
-    const wv2 fm2 = MIMIC ? wv2{famm[0], famm[FAM > 1 ? 1 : 0]} : wv2{0.f, 0.f};
-    const wv2 jr2 = MIMIC ? wv2{(float)((revmask >> fk2x) & 1u), (float)((revmask >> fk2y) & 1u)}
-                          : wv2{jrev[0] ? 1.f : 0.f, jrev[NJ2 - 1] ? 1.f : 0.f};  // revolute joints
+    const wreal2 fon2 = MIMIC ? wreal2{famk[0] >= 0 ? 1.f : 0.f, (fam_max > 1 && famk[FAM > 1 ? 1 : 0] >= 0) ? 1.f : 0.f} : wreal2{0.f, 0.f};
+    const wreal2 fm2 = MIMIC ? wreal2{famm[0], famm[FAM > 1 ? 1 : 0]} : wreal2{0.f, 0.f};
+    const wreal2 jr2 = MIMIC ? wreal2{(wreal)((revmask >> fk2x) & 1u), (wreal)((revmask >> fk2y) & 1u)}
+                          : wreal2{jrev[0] ? 1.f : 0.f, jrev[NJ2 - 1] ? 1.f : 0.f};  // revolute joints
 
     // (3) terms in sequence: lane l forms the Jacobian columns of its joints (l, l + 16), accumulates their gradient
     // entries and second-order vectors and publishes the term's four weighted Jacobian rows; then every lane adds the
@@ -872,25 +960,31 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
     constexpr int nrow = 3;  // weighted rows per term (round 6: the Huber rank-one correction is folded into the three rows)
     // columns of term t -> gradient / second-order accumulators and the term's weighted Jacobian rows in buffer `buf`
     auto publish = [&](int t, bool on) {  // on: SPRINT rows beyond the last term of their share contribute zero columns
-      float* JRw = JRl;
-      const float* T = TBl + t * 16;
-      const float4 t0 = *reinterpret_cast<const float4*>(T);
-      const float4 t1 = *reinterpret_cast<const float4*>(T + 4);
-      const float4 t2 = *reinterpret_cast<const float4*>(T + 8);
-      const float4 t3 = *reinterpret_cast<const float4*>(T + 12);
+      wreal* JRw = JRl;
+      const wreal* T = TBl + t * 16;
+      const wreal4 t0 = *reinterpret_cast<const wreal4*>(T);
+      const wreal4 t1 = *reinterpret_cast<const wreal4*>(T + 4);
+      const wreal4 t2 = *reinterpret_cast<const wreal4*>(T + 8);
+      const wreal4 t3 = *reinterpret_cast<const wreal4*>(T + 12);
       const uint32_t mt = TMw[t * TMS], mo = TMw[t * TMS + 1];
+      if (F64) {  // (float64: the lane's axes / origins are read for every term -- held across the term loop they are 36
+                  // more live registers, and the loop is where the register file runs out)
+#pragma unroll
+        for (int s = 0; s < NCOL; ++s) load_axes(s);
+        pack_axes();
+      }
       if (MIMIC) {
         // the variable's column is the vmul-weighted sum over its joint family (kinematics_adaptor.py:102-113).  The
         // first two family joints (the variable's own joint and its first follower: all of Ability / Inspire, most of
         // SVH) are formed together in packed float32 arithmetic, like the two joint slots of the joint-space grids; a
         // third family joint takes the scalar path.
-        float c0, c1, c2;
+        wreal c0, c1, c2;
         {
-          const wv2 fonv = (SPRINT && !on) ? wv2{0.f, 0.f} : fon2;
-          const wv2 ft = wv2{(float)((mt >> fk2x) & 1u), (float)((mt >> fk2y) & 1u)} * fonv;
-          const wv2 fo = wv2{(float)((mo >> fk2x) & 1u), (float)((mo >> fk2y) & 1u)} * fonv;
-          const wv2 sg = ft - fo;
-          wv2 v[3], d[3];
+          const wreal2 fonv = (SPRINT && !on) ? wreal2{0.f, 0.f} : fon2;
+          const wreal2 ft = wreal2{(wreal)((mt >> fk2x) & 1u), (wreal)((mt >> fk2y) & 1u)} * fonv;
+          const wreal2 fo = wreal2{(wreal)((mo >> fk2x) & 1u), (wreal)((mo >> fk2y) & 1u)} * fonv;
+          const wreal2 sg = ft - fo;
+          wreal2 v[3], d[3];
           v[0] = ft * t2.x - fo * t3.x - sg * jog2[0];
           v[1] = ft * t2.y - fo * t3.y - sg * jog2[1];
           v[2] = ft * t2.z - fo * t3.z - sg * jog2[2];
@@ -898,14 +992,14 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
           d[1] = jax2[2] * v[0] - jax2[0] * v[2];
           d[2] = jax2[0] * v[1] - jax2[1] * v[0];
           if (any_prismatic) {
-            const wv2 w = (wv2{1.f, 1.f} - jr2) * sg;
+            const wreal2 w = (wreal2{1.f, 1.f} - jr2) * sg;
 #pragma unroll
             for (int i = 0; i < 3; ++i) d[i] = d[i] * jr2 + jax2[i] * w;
           }
           jcf2[0] += d[1] * t1.z - d[2] * t1.y;
           jcf2[1] += d[2] * t1.x - d[0] * t1.z;
           jcf2[2] += d[0] * t1.y - d[1] * t1.x;
-          const wv2 m0 = fm2 * d[0], m1 = fm2 * d[1], m2 = fm2 * d[2];
+          const wreal2 m0 = fm2 * d[0], m1 = fm2 * d[1], m2 = fm2 * d[2];
           c0 = m0.x + m0.y;
           c1 = m1.x + m1.y;
           c2 = m2.x + m2.y;
@@ -916,17 +1010,17 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
             const int k = famk[e] >= 0 ? famk[e] : 0;
             const bool fam_on = famk[e] >= 0 && (!SPRINT || on);
             const bool in_t = fam_on && ((mt >> k) & 1u), in_o = fam_on && ((mo >> k) & 1u);
-            float d0 = 0, d1 = 0, d2 = 0;
+            wreal d0 = 0, d1 = 0, d2 = 0;
             if (in_t || in_o) {
               if ((revmask >> k) & 1u) {
-                float v0 = 0, v1 = 0, v2 = 0;
+                wreal v0 = 0, v1 = 0, v2 = 0;
                 if (in_t) { v0 += t2.x - jog[e][0]; v1 += t2.y - jog[e][1]; v2 += t2.z - jog[e][2]; }
                 if (in_o) { v0 -= t3.x - jog[e][0]; v1 -= t3.y - jog[e][1]; v2 -= t3.z - jog[e][2]; }
                 d0 = jax[e][1] * v2 - jax[e][2] * v1;
                 d1 = jax[e][2] * v0 - jax[e][0] * v2;
                 d2 = jax[e][0] * v1 - jax[e][1] * v0;
               } else {
-                const float sg = (in_t ? 1.f : 0.f) - (in_o ? 1.f : 0.f);
+                const wreal sg = (in_t ? 1.f : 0.f) - (in_o ? 1.f : 0.f);
                 d0 = sg * jax[e][0]; d1 = sg * jax[e][1]; d2 = sg * jax[e][2];
               }
               jcf[e][0] += d1 * t1.z - d2 * t1.y;
@@ -940,7 +1034,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
         const int pos = (l & 3) * NRP + (l >> 2);
         if (!per_coord) {
           asm volatile("");
-          const float u = c0 * t0.x + c1 * t0.y + c2 * t0.z;
+          const wreal u = c0 * t0.x + c1 * t0.y + c2 * t0.z;
           c0 -= t0.x * u; c1 -= t0.y * u; c2 -= t0.z * u;
         }
         JRw[0 * 4 * NRP + pos] = c0 * t1.w;
@@ -950,11 +1044,11 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
         // both joint slots of the lane (l, l + 16) at once in packed float32 arithmetic (v_pk_*): the two columns are
         // the same formula on different operands, and a pass is bound by the number of VALU instructions issued.
         //   v = in_t (p_task - o) - in_o (p_origin - o);  column = a x v (revolute)  |  (in_t - in_o) a (prismatic)
-        const wv2 jmv = (SPRINT && !on) ? wv2{0.f, 0.f} : jm2;
-        const wv2 ft = wv2{(float)((mt >> l) & 1u), (float)((mt >> (l + 16)) & 1u)} * jmv;
-        const wv2 fo = wv2{(float)((mo >> l) & 1u), (float)((mo >> (l + 16)) & 1u)} * jmv;
-        const wv2 sg = ft - fo;
-        wv2 v[3], c[3];
+        const wreal2 jmv = (SPRINT && !on) ? wreal2{0.f, 0.f} : jm2;
+        const wreal2 ft = wreal2{(wreal)((mt >> l) & 1u), (wreal)((mt >> (l + 16)) & 1u)} * jmv;
+        const wreal2 fo = wreal2{(wreal)((mo >> l) & 1u), (wreal)((mo >> (l + 16)) & 1u)} * jmv;
+        const wreal2 sg = ft - fo;
+        wreal2 v[3], c[3];
         v[0] = ft * t2.x - fo * t3.x - sg * jog2[0];
         v[1] = ft * t2.y - fo * t3.y - sg * jog2[1];
         v[2] = ft * t2.z - fo * t3.z - sg * jog2[2];
@@ -962,7 +1056,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
         c[1] = jax2[2] * v[0] - jax2[0] * v[2];
         c[2] = jax2[0] * v[1] - jax2[1] * v[0];
         if (any_prismatic) {  // wave-uniform: only models with translation joints (the dummy free base) pay for the blend
-          const wv2 w = (wv2{1.f, 1.f} - jr2) * sg;
+          const wreal2 w = (wreal2{1.f, 1.f} - jr2) * sg;
 #pragma unroll
           for (int i = 0; i < 3; ++i) c[i] = c[i] * jr2 + jax2[i] * w;
         }
@@ -970,11 +1064,11 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
         jcf2[0] += c[1] * t1.z - c[2] * t1.y;
         jcf2[1] += c[2] * t1.x - c[0] * t1.z;
         jcf2[2] += c[0] * t1.y - c[1] * t1.x;
-        wv2 r0 = c[0] * t1.w, r1 = c[1] * t2.w, r2 = c[2] * t3.w;
+        wreal2 r0 = c[0] * t1.w, r1 = c[1] * t2.w, r2 = c[2] * t3.w;
         if (!per_coord) {  // (wave-uniform; the empty asm keeps it a scalar BRANCH: if-converted, the position models paid for
                            // both forms and six selects per term -- LEAP position + 3 % in the same-box A/B)
           asm volatile("");
-          const wv2 u = c[0] * t0.x + c[1] * t0.y + c[2] * t0.z;
+          const wreal2 u = c[0] * t0.x + c[1] * t0.y + c[2] * t0.z;
           r0 = (c[0] - u * t0.x) * t1.w;
           r1 = (c[1] - u * t0.y) * t2.w;
           r2 = (c[2] - u * t0.z) * t3.w;
@@ -989,17 +1083,17 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
         for (int s = 0; s < NJ2; ++s) {
           const int k = jo_[s];
           const bool in_t = (mt >> k) & 1u, in_o = (mo >> k) & 1u;
-          float c0 = 0, c1 = 0, c2 = 0;
+          wreal c0 = 0, c1 = 0, c2 = 0;
           if (jopt[s] && (in_t || in_o) && (!SPRINT || on)) {
             if (jrev[s]) {
-              float v0 = 0, v1 = 0, v2 = 0;
+              wreal v0 = 0, v1 = 0, v2 = 0;
               if (in_t) { v0 += t2.x - jog[s][0]; v1 += t2.y - jog[s][1]; v2 += t2.z - jog[s][2]; }
               if (in_o) { v0 -= t3.x - jog[s][0]; v1 -= t3.y - jog[s][1]; v2 -= t3.z - jog[s][2]; }
               c0 = jax[s][1] * v2 - jax[s][2] * v1;
               c1 = jax[s][2] * v0 - jax[s][0] * v2;
               c2 = jax[s][0] * v1 - jax[s][1] * v0;
             } else {
-              const float sg = (in_t ? 1.f : 0.f) - (in_o ? 1.f : 0.f);
+              const wreal sg = (in_t ? 1.f : 0.f) - (in_o ? 1.f : 0.f);
               c0 = sg * jax[s][0]; c1 = sg * jax[s][1]; c2 = sg * jax[s][2];
             }
             gnew[s] += c0 * t1.x + c1 * t1.y + c2 * t1.z;
@@ -1011,7 +1105,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
           const int pos = (k & 3) * NRP + (k >> 2);
           if (!per_coord) {
             asm volatile("");
-            const float u = c0 * t0.x + c1 * t0.y + c2 * t0.z;
+            const wreal u = c0 * t0.x + c1 * t0.y + c2 * t0.z;
             c0 -= t0.x * u; c1 -= t0.y * u; c2 -= t0.z * u;
           }
           JRw[0 * 4 * NRP + pos] = c0 * t1.w;
@@ -1022,25 +1116,25 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
     };
     // every lane adds the outer products of the rows in buffer `buf` to its Hessian entries
     auto outer = [&]() {
-      const float* JRr = JRl;
+      const wreal* JRr = JRl;
 #pragma unroll
       for (int kk = 0; kk < nrow; ++kk) {
         {
-          float jr[NRP];
-          wv2 jc[NRP / 2];
+          wreal jr[NRP];
+          wreal2 jc[NRP / 2];
 #pragma unroll
           for (int i = 0; i < NRP; i += 4) {
             if (i < NR) {
-              const float4 rv = *reinterpret_cast<const float4*>(JRr + kk * 4 * NRP + a * NRP + i);
-              const float4 cv = *reinterpret_cast<const float4*>(JRr + kk * 4 * NRP + b * NRP + i);
+              const wreal4 rv = *reinterpret_cast<const wreal4*>(JRr + kk * 4 * NRP + a * NRP + i);
+              const wreal4 cv = *reinterpret_cast<const wreal4*>(JRr + kk * 4 * NRP + b * NRP + i);
               jr[i] = rv.x; jr[i + 1] = rv.y; jr[i + 2] = rv.z; jr[i + 3] = rv.w;
-              jc[i / 2] = wv2{cv.x, cv.y};
-              jc[i / 2 + 1] = wv2{cv.z, cv.w};
+              jc[i / 2] = wreal2{cv.x, cv.y};
+              jc[i / 2 + 1] = wreal2{cv.z, cv.w};
             }
           }
 #pragma unroll
           for (int i = 0; i < NR; ++i) {
-            const wv2 rr = wv2{jr[i], jr[i]};
+            const wreal2 rr = wreal2{jr[i], jr[i]};
 #pragma unroll
             for (int jj = 0; jj <= i / 2; ++jj) Hx[i][jj] = __builtin_elementwise_fma(rr, jc[jj], Hx[i][jj]);
           }
@@ -1091,9 +1185,9 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       // the rows' partial sums -> every row: v + v(lane ^ 16), then + (lane ^ 32).  Both partners of an exchange add the same
       // two numbers, so the four rows end with identical bits (the redundant stages after this stay in lockstep).
       const int x16 = (lane ^ 16) << 2, x32 = (lane ^ 32) << 2;
-      auto xsum = [&](float v) -> float {
-        v += __int_as_float(__builtin_amdgcn_ds_bpermute(x16, __float_as_int(v)));
-        v += __int_as_float(__builtin_amdgcn_ds_bpermute(x32, __float_as_int(v)));
+      auto xsum = [&](wreal v) -> wreal {
+        v += wbperm(x16, v);
+        v += wbperm(x32, v);
         return v;
       };
 #pragma unroll
@@ -1119,11 +1213,11 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       // LDS slots, a register file has no run-time index
 #pragma unroll
       for (int e = 0; e < FAM; ++e)
-        if (famk[e] >= 0) *reinterpret_cast<float4*>(CFl + famk[e] * 4) = make_float4(jcf[e][0], jcf[e][1], jcf[e][2], 0.f);
-      float* HBl = TBl + l * 12;  // the term block is free now
-      *reinterpret_cast<float4*>(HBl) = make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(HBl + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(HBl + 8) = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (famk[e] >= 0) *reinterpret_cast<wreal4*>(CFl + famk[e] * 4) = mk4(jcf[e][0], jcf[e][1], jcf[e][2], 0.f);
+      wreal* HBl = TBl + l * 12;  // the term block is free now
+      *reinterpret_cast<wreal4*>(HBl) = mk4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<wreal4*>(HBl + 4) = mk4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<wreal4*>(HBl + 8) = mk4(0.f, 0.f, 0.f, 0.f);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       const int p0 = POFF[l], p1 = POFF[l + 1];
@@ -1134,9 +1228,9 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
         if (pp < p1) {
           const uint32_t w = PLw[pp];
           const int k = (int)(w & 31u), j = (int)((w >> 5) & 31u), e = (int)((w >> 10) & 15u);
-          const float4 aj = *reinterpret_cast<const float4*>(AXl + j * 4);
-          const float4 cf = *reinterpret_cast<const float4*>(CFl + k * 4);
-          float val = XT[k * XTS + 14] * XT[j * XTS + 14] * (aj.x * cf.x + aj.y * cf.y + aj.z * cf.z);
+          const wreal4 aj = *reinterpret_cast<const wreal4*>(AXl + j * 4);
+          const wreal4 cf = *reinterpret_cast<const wreal4*>(CFl + k * 4);
+          wreal val = (wreal)XT[k * XTS + 14] * (wreal)XT[j * XTS + 14] * (aj.x * cf.x + aj.y * cf.y + aj.z * cf.z);
           if ((w >> 14) & 1u) val += val;
           HBl[e] += val;
         }
@@ -1147,26 +1241,26 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       for (int i = 0; i < NR; ++i)
 #pragma unroll
         for (int j = 0; j <= i; ++j) {
-          const float add = HBl[i * (i + 1) / 2 + j];
+          const wreal add = HBl[i * (i + 1) / 2 + j];
           if (j & 1) Hx[i][j / 2].y += add; else Hx[i][j / 2].x += add;
         }
     }
     if (newton && !MIMIC) {
 #pragma unroll
       for (int s = 0; s < NJ2; ++s)
-        if (jin[s]) *reinterpret_cast<float4*>(CFl + jo_[s] * 4) = make_float4(jcf[s][0], jcf[s][1], jcf[s][2], 0.f);
+        if (jin[s]) *reinterpret_cast<wreal4*>(CFl + jo_[s] * 4) = mk4(jcf[s][0], jcf[s][1], jcf[s][2], 0.f);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      float4 axc[NR];
+      wreal4 axc[NR];
 #pragma unroll
-      for (int j = 0; j < NR; ++j) axc[j] = *reinterpret_cast<const float4*>(AXl + (4 * j + b) * 4);
+      for (int j = 0; j < NR; ++j) axc[j] = *reinterpret_cast<const wreal4*>(AXl + (4 * j + b) * 4);
 #pragma unroll
       for (int i = 0; i < NR; ++i) {
-        const float4 cf = *reinterpret_cast<const float4*>(CFl + (4 * i + a) * 4);
+        const wreal4 cf = *reinterpret_cast<const wreal4*>(CFl + (4 * i + a) * 4);
 #pragma unroll
         for (int j = 0; j <= i; ++j) {
-          const float v = axc[j].x * cf.x + axc[j].y * cf.y + axc[j].z * cf.z;
-          const float add = ((ANCw[4 * i + a] >> (4 * j + b)) & 1u) ? v : 0.f;
+          const wreal v = axc[j].x * cf.x + axc[j].y * cf.y + axc[j].z * cf.z;
+          const wreal add = ((ANCw[4 * i + a] >> (4 * j + b)) & 1u) ? v : 0.f;
           if (j & 1) Hx[i][j / 2].y += add; else Hx[i][j / 2].x += add;
         }
       }
@@ -1180,19 +1274,19 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   };
 
   // ---- distributed Cholesky + triangular solves of (H_acc restricted to the free set + damping) d = -g -------------
-  float dstep[NJ2];  // own joints' entries of the step
-  float hdmean = 0.f;  // mean diagonal of the free block of the accepted Hessian (MODCHOL: scale of the damping jump)
-  auto factor_and_solve = [&](uint32_t freemask, float lam) -> bool {
+  wreal dstep[NJ2];  // own joints' entries of the step
+  wreal hdmean = 0.f;  // mean diagonal of the free block of the accepted Hessian (MODCHOL: scale of the damping jump)
+  auto factor_and_solve = [&](uint32_t freemask, wreal lam) -> bool {
     bool ok = true;
     if (MODCHOL) {
-      float hds = 0.f;
+      wreal hds = 0.f;
 #pragma unroll
       for (int i = 0; i < NR; ++i)
         if (a == b && ((freemask >> (4 * i + a)) & 1u)) hds += (i & 1) ? Ha[i][i / 2].y : Ha[i][i / 2].x;
       const int nfree = __popc(freemask);
-      hdmean = row_sum(hds) / (float)(nfree > 0 ? nfree : 1);
+      hdmean = row_sum(hds) / (wreal)(nfree > 0 ? nfree : 1);
     }
-    wv2 Hw[NR][NP];
+    wreal2 Hw[NR][NP];
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
       const int r = 4 * i + a;
@@ -1201,54 +1295,54 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       for (int j = 0; j <= (i | 1); ++j) {
         const int c = 4 * j + b;
         const bool fc = (freemask >> c) & 1u;
-        float v = (fr && fc && j <= i) ? ((j & 1) ? Ha[i][j / 2].y : Ha[i][j / 2].x) : 0.f;
+        wreal v = (fr && fc && j <= i) ? ((j & 1) ? Ha[i][j / 2].y : Ha[i][j / 2].x) : 0.f;
         if (i == j && a == b) v = fr ? v + 2.f * delta + lam : 1.f;
         if (j & 1) Hw[i][j / 2].y = v; else Hw[i][j / 2].x = v;
       }
     }
-    auto hw_get = [&](int i, int j) -> float { return (j & 1) ? Hw[i][j / 2].y : Hw[i][j / 2].x; };
+    auto hw_get = [&](int i, int j) -> wreal { return (j & 1) ? Hw[i][j / 2].y : Hw[i][j / 2].x; };
     // The right-hand side rides along as row NMAX of the matrix (held by quad 0, class a = 0): the factorisation's
     // trailing updates then ARE the forward substitution -- after the last step that row holds y = L^-1 rhs.  Saves a
     // 24-step dependent chain of quad sums and row broadcasts per pass.
-    wv2 Hy[NP];
+    wreal2 Hy[NP];
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
       const int c = 4 * j + b;
-      const float v = (a == 0 && ((freemask >> c) & 1u)) ? -GVl[c] : 0.f;
+      const wreal v = (a == 0 && ((freemask >> c) & 1u)) ? -GVl[c] : 0.f;
       if (j & 1) Hy[j / 2].y = v; else Hy[j / 2].x = v;
     }
-    auto hy_get = [&](int j) -> float { return (j & 1) ? Hy[j / 2].y : Hy[j / 2].x; };
-    float ivc[NR];  // 1 / L[c][c] of column 4 j + b
+    auto hy_get = [&](int j) -> wreal { return (j & 1) ? Hy[j / 2].y : Hy[j / 2].x; };
+    wreal ivc[NR];  // 1 / L[c][c] of column 4 j + b
 #pragma unroll
     for (int i = 0; i < NR; ++i) ivc[i] = 0.f;
 #pragma unroll
     for (int jc = 0; jc < NMAX; ++jc) {
       const int ja = jc & 3, jo = jc >> 2;
       // pivot: lane (ja, ja) -> its quad (DPP) -> the row (mask + stride-4 sum)
-      const float own_d = hw_get(jo, jo);
-      const float qd = ja == 0 ? wquad_bcast<0>(own_d) : ja == 1 ? wquad_bcast<1>(own_d) : ja == 2 ? wquad_bcast<2>(own_d) : wquad_bcast<3>(own_d);
-      float dj = stride4_sum(a == ja ? qd : 0.f);
+      const wreal own_d = hw_get(jo, jo);
+      const wreal qd = ja == 0 ? wquad_bcast<0>(own_d) : ja == 1 ? wquad_bcast<1>(own_d) : ja == 2 ? wquad_bcast<2>(own_d) : wquad_bcast<3>(own_d);
+      wreal dj = stride4_sum(a == ja ? qd : 0.f);
       if (MODCHOL) {
-        if (!(dj > 1e-6f * (2.f * delta + lam))) { ok = false; dj = fmaxf(fabsf(dj), 2.f * delta + lam); }
+        if (!(dj > 1e-6f * (2.f * delta + lam))) { ok = false; dj = wmax(wabs(dj), 2.f * delta + lam); }
       } else {
         if (!(dj > 1e-30f)) { ok = false; dj = 1.f; }
       }
-      const float iv = __frsqrt_rn(dj);
+      const wreal iv = wrsqrt(dj);
       ivc[jo] = (b == ja) ? iv : ivc[jo];
       // scale column jc (lanes of column class ja), rows below the pivot; then send it to the grid: row side from
       // lane (a, ja) (own quad, DPP), column side from lane (b, ja) (ds_bpermute)
-      float Lr[NR];
-      wv2 Lc[NP];
+      wreal Lr[NR];
+      wreal2 Lc[NP];
 #pragma unroll
-      for (int jj = 0; jj < NP; ++jj) Lc[jj] = wv2{0.f, 0.f};
+      for (int jj = 0; jj < NP; ++jj) Lc[jj] = wreal2{0.f, 0.f};
 #pragma unroll
       for (int i = jo; i < NR; ++i) {
         const bool below = (i > jo) || (a > ja);
-        const float cur = hw_get(i, jo);
-        const float own = (b == ja && below) ? cur * iv : cur;
+        const wreal cur = hw_get(i, jo);
+        const wreal own = (b == ja && below) ? cur * iv : cur;
         if (jo & 1) Hw[i][jo / 2].y = own; else Hw[i][jo / 2].x = own;
-        float vr = ja == 0 ? wquad_bcast<0>(own) : ja == 1 ? wquad_bcast<1>(own) : ja == 2 ? wquad_bcast<2>(own) : wquad_bcast<3>(own);
-        float vc = __int_as_float(__builtin_amdgcn_ds_bpermute(rowbase4 + 16 * b + 4 * ja, __float_as_int(own)));
+        wreal vr = ja == 0 ? wquad_bcast<0>(own) : ja == 1 ? wquad_bcast<1>(own) : ja == 2 ? wquad_bcast<2>(own) : wquad_bcast<3>(own);
+        wreal vc = wbperm(rowbase4 + 16 * b + 4 * ja, own);
         if (i == jo) {
           vr = (a > ja) ? vr : 0.f;
           vc = (b > ja) ? vc : 0.f;
@@ -1259,22 +1353,22 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       // the pivot column itself (local column jo on lanes with b == ja) sees Lc[jo] = 0 there: it stays as scaled
 #pragma unroll
       for (int i = jo; i < NR; ++i) {
-        const wv2 rr = wv2{-Lr[i], -Lr[i]};
+        const wreal2 rr = wreal2{-Lr[i], -Lr[i]};
 #pragma unroll
         for (int jj = jo / 2; jj <= i / 2; ++jj) Hw[i][jj] = __builtin_elementwise_fma(rr, Lc[jj], Hw[i][jj]);
       }
       {  // the right-hand-side row
-        const float cur = hy_get(jo);
-        const float own = (b == ja) ? cur * iv : cur;
+        const wreal cur = hy_get(jo);
+        const wreal own = (b == ja) ? cur * iv : cur;
         if (jo & 1) Hy[jo / 2].y = own; else Hy[jo / 2].x = own;
-        const float ly = ja == 0 ? wquad_bcast<0>(own) : ja == 1 ? wquad_bcast<1>(own) : ja == 2 ? wquad_bcast<2>(own) : wquad_bcast<3>(own);
-        const wv2 rr = wv2{-ly, -ly};
+        const wreal ly = ja == 0 ? wquad_bcast<0>(own) : ja == 1 ? wquad_bcast<1>(own) : ja == 2 ? wquad_bcast<2>(own) : wquad_bcast<3>(own);
+        const wreal2 rr = wreal2{-ly, -ly};
 #pragma unroll
         for (int jj = jo / 2; jj < NP; ++jj) Hy[jj] = __builtin_elementwise_fma(rr, Lc[jj], Hy[jj]);
       }
     }
     // y[4 j + b] from quad 0 to the lanes of column class b of every quad
-    float yb[NR], da[NR];
+    wreal yb[NR], da[NR];
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
       yb[j] = stride4_sum(a == 0 ? hy_get(j) : 0.f);
@@ -1286,12 +1380,12 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
 #pragma unroll
     for (int r = NMAX - 1; r >= 0; --r) {
       const int rb = r & 3, ro = r >> 2;
-      float part = 0;
+      wreal part = 0;
 #pragma unroll
       for (int i = ro; i < NR; ++i) part += hw_get(i, ro) * da[i];  // rows at or above r meet da = 0
-      const float sum = stride4_sum(part);                      // valid on lanes of column class rb
-      const float dr_local = (yb[ro] - sum) * ivc[ro];
-      const float dr = rb == 0 ? wquad_bcast<0>(dr_local) : rb == 1 ? wquad_bcast<1>(dr_local)
+      const wreal sum = stride4_sum(part);                      // valid on lanes of column class rb
+      const wreal dr_local = (yb[ro] - sum) * ivc[ro];
+      const wreal dr = rb == 0 ? wquad_bcast<0>(dr_local) : rb == 1 ? wquad_bcast<1>(dr_local)
                      : rb == 2 ? wquad_bcast<2>(dr_local) : wquad_bcast<3>(dr_local);  // lane b = rb of every quad
       da[ro] = (a == rb) ? dr : da[ro];
 #pragma unroll
@@ -1301,12 +1395,12 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   };
 
   // ---- projected Levenberg-Marquardt / Newton ------------------------------------------------------------------------
-  float lam = kp.lam0, nu = 2.f, sprev = 1e30f, keff = 0.f;
+  wreal lam = kp.lam0, nu = 2.f, sprev = 1e30f, keff = 0.f;
   WDIAG(int d_nrej = 0; int d_ncap = 0; int d_nfail = 0;)
   bool done = true, pending = false;
   int status = ST_MAXITER, my_iters = 0, blind = 0, nrej = 0;  // nrej: rejections of this solve (bounds the fast damping decay)
   double F = 0;
-  float smax = 0, pred = 0;
+  wreal smax = 0, pred = 0;
   bool ok = true;
   unsigned pool_next = (unsigned)((tile * FPW < (int64_t)kp.q0 && tile * FPW < nB) ? tile * FPW : 0);
   unsigned pool_end = (unsigned)((tile * FPW < (int64_t)kp.q0 && tile * FPW < nB) ? ((tile * FPW + FPW < nB) ? tile * FPW + FPW : nB) : 0);
@@ -1331,9 +1425,9 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
   };
   float screen_acc = 0.f;  // screening launch: sum of F(x0) over the frames of this wave (lane 0 of each row)
   // SPRINT: the rows' damping multipliers (the ladder; all 1: the rows are copies) -- read once, selected by row where needed
-  const float mu_0 = SPRINT ? kp.sprint_mu[0] : 1.f, mu_1 = SPRINT ? kp.sprint_mu[1] : 1.f, mu_2 = SPRINT ? kp.sprint_mu[2] : 1.f,
+  const wreal mu_0 = SPRINT ? kp.sprint_mu[0] : 1.f, mu_1 = SPRINT ? kp.sprint_mu[1] : 1.f, mu_2 = SPRINT ? kp.sprint_mu[2] : 1.f,
               mu_3 = SPRINT ? kp.sprint_mu[3] : 1.f;
-  const float mu_own = slot == 0 ? mu_0 : slot == 1 ? mu_1 : slot == 2 ? mu_2 : mu_3;
+  const wreal mu_own = slot == 0 ? mu_0 : slot == 1 ? mu_1 : slot == 2 ? mu_2 : mu_3;
   for (;;) {
     // the lane's grid coordinates, made opaque once per pass: predicates on them (a == 2, b <= a, ...) are then recomputed
     // where they are used (one v_cmp) instead of being hoisted out of the loop as 64-bit lane masks -- dozens of SGPR pairs
@@ -1406,7 +1500,8 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
         take = true;
       } else {
         // (float: the float64 product kept (double) floor_scale alive across the pass loop, in scratch; pred is a float anyway)
-        const float noise = kp.floor_scale * fabsf((float)F);
+        // (float64: the rounding floor of F in double arithmetic, that of the float64 register kernel -- dexr_kernel.hpp)
+        const wreal noise = F64 ? (wreal)(16.0 * 1.1102230246251565e-16 * fmax(fabs(F), 2e-3)) : (wreal)(kp.floor_scale * fabsf((float)F));
         // (bitwise, not short-circuit: `&&` / `||` on lane-varying conditions compile to nested exec-mask branches)
         bool finite = (bool)((int)(Fe == Fe) & (int)(smax == smax) & (int)(fabs(Fe) < 1e30));
         bool below_floor = (bool)((int)ok & (int)finite & (int)(pred <= noise) & (int)(smax < 1e-2f));
@@ -1436,13 +1531,13 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
           // below from firing, pass after pass up to max_iter (12 of 512 reachable-target frames of the SVH position model once
           // the ladder stopped taking blind steps).  Same rule as the four-per-wave iteration's "a rejected step below tol ends
           // the solve at the rounding floor".
-          sprint_floor = (bool)((int)all_small & (int)(lam * mu_0 <= fmaxf(2.f * delta, 10.f * kp.lam0)));
+          sprint_floor = (bool)((int)all_small & (int)(lam * mu_0 <= wmax(2.f * delta, (wreal)(10.f * kp.lam0))));
           if (any_ok) {
             const int src = (16 * w + l) << 2;
 #pragma unroll
-            for (int s2 = 0; s2 < NJ2; ++s2) xj[s2] = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(xj[s2])));
-            pred = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(pred)));
-            smax = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(smax)));
+            for (int s2 = 0; s2 < NJ2; ++s2) xj[s2] = wbperm(src, xj[s2]);
+            pred = wbperm(src, pred);
+            smax = wbperm(src, smax);
             const int flags = __builtin_amdgcn_ds_bpermute(src, (int)ok | ((int)below_floor << 1));
             ok = (bool)(flags & 1);
             below_floor = (bool)((flags >> 1) & 1);
@@ -1454,8 +1549,8 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
           } else {
             accept = false;
             lam = lam * mu_3;
-            keff = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(keff), 48));
-            hdmean = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hdmean), 48));
+            keff = wreadlane(keff, 48);
+            hdmean = wreadlane(hdmean, 48);
             ok = all_small;       // (only read by the exit test of the rejection branch below, together with:)
             finite = all_finite;
             smax = all_small ? 0.f : 1e30f;
@@ -1464,31 +1559,31 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
         ++my_iters;
         pending = false;
         if (accept) {
-          const float rho = (float)((F - Fe) / fmax((double)pred, 1e-30));
-          const float tt = 2.f * rho - 1.f;
-          float shrink = below_floor ? (1.f / 3.f) : fmaxf(1.f / 3.f, 1.f - tt * tt * tt);
+          const wreal rho = (wreal)((F - Fe) / fmax((double)pred, 1e-30));
+          const wreal tt = 2.f * rho - 1.f;
+          wreal shrink = below_floor ? (1.f / 3.f) : wmax((wreal)(1.f / 3.f), 1.f - tt * tt * tt);
           // (fast decay: the quick way back after a damping jump -- but only for the first few rejections of a solve: a frame
           // that keeps being rejected is cycling between a too small and a too large lambda, and the 1/3 rule damps that)
           if ((bool)((int)(kp.lam_fastdec > 0) & (int)(rho > 0.9f) & (int)(nrej <= kp.fastdec_max_rej))) shrink = kp.lam_fastdec;
-          lam = fmaxf(lam * shrink, 1e-9f);
+          lam = wmax(lam * shrink, (wreal)1e-9f);
           nu = 2.f;
           F = Fe;
           take = true;
           const bool stalled = (bool)((int)below_floor & (int)(blind >= kp.stall_from) & (int)(smax > kp.stall_ratio * sprev) & (int)(smax < kp.stall_cap * kp.tol));
           blind = below_floor ? blind + 1 : 0;
           sprev = smax;
-          const float lam_ok = fmaxf(2.f * delta, 10.f * kp.lam0);  // see dexr_quad.hpp
+          const wreal lam_ok = wmax(2.f * delta, (wreal)(10.f * kp.lam0));  // see dexr_quad.hpp
           if ((bool)(((int)(smax < kp.tol) & ((int)(lam <= lam_ok) | (int)sprint_floor)) | (int)stalled | (int)(blind >= kp.max_blind))) {
             done = true;
             status = ST_CONVERGED;
           } else if (smax < kp.tol) {
-            lam = fmaxf(0.1f * lam, 0.5f * lam_ok);
+            lam = wmax(0.1f * lam, 0.5f * lam_ok);
           }
         } else {
           WDIAG(++d_nrej; if (!ok) ++d_nfail;)
           ++nrej;
-          lam = fmaxf(lam, 1e-6f) * nu;
-          if (kp.lam_jump > 0) lam = fmaxf(lam, kp.lam_jump * (MODCHOL ? hdmean : keff));
+          lam = wmax(lam, (wreal)1e-6f) * nu;
+          if (kp.lam_jump > 0) lam = wmax(lam, kp.lam_jump * (MODCHOL ? hdmean : keff));
           nu *= 2.f;
 #pragma unroll
           for (int s = 0; s < NJ2; ++s) xj[s] = xacc[s];
@@ -1509,10 +1604,10 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
         // the model at the kept point: its kinematic state and term blocks lie in the frame slot of the row that evaluated it
         const int ws = __builtin_amdgcn_readfirstlane(wrow);
         unsigned char* wb = wbase + L::SLOT0 + (size_t)ws * L::SLOT;
-        float *AXo = AXl, *OGo = OGl, *TBo = TBl;
-        AXl = reinterpret_cast<float*>(wb + L::AX);
-        OGl = reinterpret_cast<float*>(wb + L::OG);
-        TBl = reinterpret_cast<float*>(wb + L::TB);
+        wreal *AXo = AXl, *OGo = OGl, *TBo = TBl;
+        AXl = reinterpret_cast<wreal*>(wb + L::AX);
+        OGl = reinterpret_cast<wreal*>(wb + L::OG);
+        TBl = reinterpret_cast<wreal*>(wb + L::TB);
         model_rest();
         AXl = AXo; OGl = OGo; TBl = TBo;
       }
@@ -1537,7 +1632,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
 #pragma unroll
       for (int s = 0; s < NJ2; ++s) {
         const float2 bx = *reinterpret_cast<const float2*>(BOXw + 2 * (jin[s] ? jo_[s] : 0));
-        const float ga = GVl[jin[s] ? jo_[s] : 0];
+        const wreal ga = GVl[jin[s] ? jo_[s] : 0];
         const bool act = (bool)(((int)(xacc[s] <= bx.x) & (int)(ga > 0)) | ((int)(xacc[s] >= bx.y) & (int)(ga < 0)));
         fr[s] = (bool)((int)jopt[s] & (int)!act);
       }
@@ -1569,25 +1664,25 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       const bool retry = !MODCHOL && NMAX <= 24 && attempt < 3 && !done && (SPRINT ? __ballot(okf) == 0ull : !okf);  // (uniform over the row's 16 lanes)
       if (!__any(retry)) break;
       if (retry) {
-        float gdl = 0.f, ddl = 0.f;
+        wreal gdl = 0.f, ddl = 0.f;
 #pragma unroll
         for (int s = 0; s < NJ2; ++s) {  // (selects, not branches: a joint slot that is not free contributes a zero step)
           const int jg = jin[s] ? jo_[s] : 0;
-          const float ds = (bool)((int)jin[s] & (int)((freemask >> jg) & 1u)) ? dstep[s] : 0.f;
+          const wreal ds = (bool)((int)jin[s] & (int)((freemask >> jg) & 1u)) ? dstep[s] : 0.f;
           gdl -= GVl[jg] * ds;
           ddl += ds * ds;
         }
-        const float gd = row_sum(gdl), dd = row_sum(ddl);
-        keff = gd / fmaxf(dd, 1e-30f);
+        const wreal gd = row_sum(gdl), dd = row_sum(ddl);
+        keff = gd / wmax(dd, (wreal)1e-30f);
         if (SPRINT) {  // (row 3: the largest damping of the ladder)
-          keff = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(keff), 48));
+          keff = wreadlane(keff, 48);
           lam = lam * mu_3;
         }
         ++my_iters;
         WDIAG(++d_nrej; ++d_nfail;)
         ++nrej;
-        lam = fmaxf(lam, 1e-6f) * nu;
-        if (kp.lam_jump > 0) lam = fmaxf(lam, kp.lam_jump * keff);
+        lam = wmax(lam, (wreal)1e-6f) * nu;
+        if (kp.lam_jump > 0) lam = wmax(lam, kp.lam_jump * keff);
         nu *= 2.f;
         if (lam > 1e10f) {
           done = true;
@@ -1600,32 +1695,32 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
     const bool stepping = !done;
     if (stepping) {
       ok = okf;
-      float dmaxl = 0.f, gdl = 0.f, ddl = 0.f;
+      wreal dmaxl = 0.f, gdl = 0.f, ddl = 0.f;
       bool son[NJ2];
       int sjg[NJ2];
 #pragma unroll
       for (int s = 0; s < NJ2; ++s) {
         sjg[s] = jin[s] ? jo_[s] : 0;
         son[s] = (bool)((int)jin[s] & (int)((freemask >> sjg[s]) & 1u));
-        const float ds = son[s] ? dstep[s] : 0.f;
-        dmaxl = fmaxf(dmaxl, fabsf(ds));
+        const wreal ds = son[s] ? dstep[s] : 0.f;
+        dmaxl = wmax(dmaxl, wabs(ds));
         gdl -= GVl[sjg[s]] * ds;
         ddl += ds * ds;
       }
-      const float dmax = row_max(dmaxl), gd = row_sum(gdl), dd = row_sum(ddl);
+      const wreal dmax = row_max(dmaxl), gd = row_sum(gdl), dd = row_sum(ddl);
       // (MODCHOL: a step from a modified factorisation is stretched towards the trust radius, at most 8 x)
-      const float alpha = (bool)((int)(kp.step_cap > 0) & ((int)(dmax > kp.step_cap) | ((int)MODCHOL & (int)!okf & (int)(dmax > 0.f))))
-                              ? fminf(kp.step_cap / dmax, MODCHOL ? 8.f : 1e30f) : 1.f;
+      const wreal alpha = (bool)((int)(kp.step_cap > 0) & ((int)(dmax > kp.step_cap) | ((int)MODCHOL & (int)!okf & (int)(dmax > 0.f))))
+                              ? wmin(kp.step_cap / dmax, (wreal)(MODCHOL ? 8.f : 1e30f)) : (wreal)1.f;
       WDIAG(if (alpha < 1.f) ++d_ncap;)
-      const float lam_row = lam * mu_own;  // (the damping this row's step was computed with)
+      const wreal lam_row = lam * mu_own;  // (the damping this row's step was computed with)
       pred = alpha * (1.f - 0.5f * alpha) * gd + 0.5f * alpha * alpha * lam_row * dd;
-      keff = gd / fmaxf(dd, 1e-30f);
-      float sl = 0.f;
+      keff = gd / wmax(dd, (wreal)1e-30f);
+      wreal sl = 0.f;
 #pragma unroll
       for (int s = 0; s < NJ2; ++s) {
         const float2 bx = *reinterpret_cast<const float2*>(BOXw + 2 * sjg[s]);
-        const float xt = fminf(fmaxf(xacc[s] + alpha * dstep[s], bx.x), bx.y);
-        sl = fmaxf(sl, son[s] ? fabsf(xt - xacc[s]) : 0.f);
+        const wreal xt = wmin(wmax(xacc[s] + alpha * dstep[s], (wreal)bx.x), (wreal)bx.y);
+        sl = wmax(sl, son[s] ? wabs(xt - xacc[s]) : 0.f);
         xj[s] = son[s] ? xt : xj[s];
       }
       smax = row_max(sl);
@@ -1642,15 +1737,15 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
       // (8.7 x the failure's own ratio; lab: +0.9 % passes on Shadow DexPilot, none on LEAP, profiles/r06_blind_step_guard.txt)
       // marks a weakly held variable, and such a frame verifies its last step like any other.
       if (__any(last_step)) {
-        float hdl = 0.f;
+        wreal hdl = 0.f;
 #pragma unroll
         for (int i = 0; i < NR; ++i)
-          if ((bool)((int)(a == b) & (int)((freemask >> (4 * i + a)) & 1u))) hdl = fmaxf(hdl, (i & 1) ? Ha[i][i / 2].y : Ha[i][i / 2].x);
-        const float tau = 0.25f * (float)__popc(freemask) * (row_max(hdl) + 2.f * delta) * smax;
+          if ((bool)((int)(a == b) & (int)((freemask >> (4 * i + a)) & 1u))) hdl = wmax(hdl, (i & 1) ? Ha[i][i / 2].y : Ha[i][i / 2].x);
+        const wreal tau = 0.25f * (wreal)__popc(freemask) * (row_max(hdl) + 2.f * delta) * smax;
         bool weakl = false;
 #pragma unroll
         for (int s = 0; s < NJ2; ++s)
-          weakl = (bool)((int)weakl | ((int)jin[s] & (int)jopt[s] & (int)!son[s] & (int)(fabsf(GVl[sjg[s]]) < tau)));
+          weakl = (bool)((int)weakl | ((int)jin[s] & (int)jopt[s] & (int)!son[s] & (int)(wabs(GVl[sjg[s]]) < tau)));
         last_step = (bool)((int)last_step & (int)!(row_max(weakl ? 1.f : 0.f) > 0.f));
       }
       if (SPRINT) {  // any row's step qualifies: the least damped such row's point is the answer, for every row
@@ -1659,7 +1754,7 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
           const int r = (__ffsll((long long)lb) - 1) >> 4;
           const int src = (16 * r + l) << 2;
 #pragma unroll
-          for (int s2 = 0; s2 < NJ2; ++s2) xj[s2] = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(xj[s2])));
+          for (int s2 = 0; s2 < NJ2; ++s2) xj[s2] = wbperm(src, xj[s2]);
           last_step = true;
         }
       }
@@ -1687,10 +1782,10 @@ __global__ void __launch_bounds__(256, DEXR_WIDE_MINW) dexr_wide_kernel(const Ke
 #pragma unroll
       for (int s = 0; s < NJ2; ++s)
         if (jopt[s] && writer) {
-          const float v = bad ? XLl[jo_[s]] : xacc[s];
+          const wreal v = bad ? XLl[jo_[s]] : xacc[s];
           const int api = tb.api[jsel(s)];
           const int64_t irow = f_irow();
-          kp.qout[irow * ld + api] = v;
+          kp.qout[irow * ld + api] = (float)v;
           if (kp.qout64) kp.qout64[irow * ld + api] = (double)v;
         }
       if (l == 0 && writer) {

@@ -80,6 +80,10 @@ class Optimizer:
         # True: compile to the generic table format even when the model fits the fixed-size records (the general kernel
         # then serves it; used by the tests that cross-check that kernel on the shipped robots)
         self.use_generic_tables = False
+        # kernel of the float64 solves (solve_options["precision"] = 1): None / "register" (default) or "wide" (the
+        # sixteen-lane kernel's float64 instantiation, dexr_tuning.kernel_f64); applied to every handle device_model() builds
+        self.f64_kernel: Optional[str] = None
+        self._f64_applied: Optional[str] = None
         self.solve_options = dict(max_iter=None, tol=None, lambda0=None, newton=None, precision=None, polish=None, strict=None)
         self.last_info: dict = {}
 
@@ -138,6 +142,13 @@ class Optimizer:
         if self._model is None:
             self._compiled = None
             self._model = _lib.Model(self.compiled_model().to_blob())
+            self._f64_applied = None
+        if self.f64_kernel not in (None, "register", "wide"):
+            raise ValueError(f"f64_kernel must be None, 'register' or 'wide', got {self.f64_kernel!r}")
+        want = "wide" if self.f64_kernel == "wide" else None  # (None: the handle's default, the register kernel)
+        if want != self._f64_applied:
+            self._model.tune(kernel_f64=_lib.KERNEL_WIDE if want else _lib.KERNEL_AUTO)
+            self._f64_applied = want
         return self._model
 
     def _options(self) -> Optional[_lib.SolveOptions]:

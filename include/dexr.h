@@ -44,7 +44,9 @@ typedef struct dexr_solve_options {
   float lambda0;      /* initial Levenberg-Marquardt damping (default 1e-4)                */
   int32_t newton;     /* 1: add the second-order kinematic term to the Hessian (default 1) */
   int32_t precision;  /* 0: float32 / mixed-precision kernels (default); 1: float64 arithmetic throughout (the
-                         reference's own arithmetic type; register kernel, no polish pass).  Device-pointer entry
+                         reference's own arithmetic type; no polish pass).  The kernel is the register kernel unless
+                         the handle opts in to the sixteen-lane kernel's float64 instantiation (dexr_tuning.kernel_f64,
+                         dexr_model_kernel_f64 reports which).  Device-pointer entry
                          points accept both; the result rows are float32 either way (optimizer.py:99)            */
   int32_t polish;     /* float64 polishing iterations run after the float32 solve, started at its answer:
                          -1 auto (default: up to 24 for position / DexPilot models, whose float32 rounding floor sits
@@ -141,6 +143,13 @@ typedef struct dexr_tuning {
                            they stood.  0 off, > 0 the cap, -1 measured policy = OFF: at 65 536 frames the capped main launch
                            is throughput-bound and barely shorter, the second launch comes on top (LEAP position 1.11 ->
                            1.18-1.29 ms for caps of 16 ... 6; answers equal to 1e-6 rad either way)                      */
+  int32_t kernel_f64;   /* family of the float64 SOLVE launches (precision = 1, dexr_retarget_f64, float64 sequences; the
+                           polish pass keeps the register kernel).  DEXR_KERNEL_AUTO (default) / DEXR_KERNEL_REGISTER: the
+                           register kernel.  DEXR_KERNEL_WIDE: the sixteen-lane kernel's float64 instantiation, four frames
+                           per wave at every batch size (no one-frame-per-wave shape, no tail launch: a frame's answer does
+                           not depend on the batch or its row); DEXR_ERR_UNSUPPORTED on a handle the sixteen-lane kernel
+                           does not serve (dexr_model_lane_plan), on a generic-table model and on components of more than
+                           24 joints without mimic joints.  Any other value: DEXR_ERR_INVALID.  Fleet batches stay float32. */
 } dexr_tuning;
 #define DEXR_TUNE_LAM_JUMP 1u
 #define DEXR_TUNE_LAM_FASTDEC 2u
@@ -159,8 +168,12 @@ int dexr_model_info(const dexr_model* m, dexr_model_header* header_out);
 int dexr_model_get_tuning(const dexr_model* m, dexr_tuning* out);     /* out->struct_size must be set by the caller */
 int dexr_model_set_tuning(dexr_model* m, const dexr_tuning* tuning);  /* re-runs the kernel selection           */
 /* Which float32 solve kernel the handle launches: DEXR_KERNEL_* in *family, joint bucket in *bucket, 1 in *chain
- * when the serial-chain specialisation is active (2: with its tip pass) (diagnostics for tools/ and tests). */
+ * when the serial-chain specialisation is active (2: with its tip pass) (diagnostics for tools/ and tests).  The float64
+ * solve launches are reported by dexr_model_kernel_f64. */
 int dexr_model_kernel(const dexr_model* m, int32_t* family, int32_t* bucket, int32_t* chain);
+/* [not-in-ref] Which kernel a float64 solve launch of the handle runs (dexr_tuning.kernel_f64): DEXR_KERNEL_REGISTER,
+ * DEXR_KERNEL_WIDE or DEXR_KERNEL_GENERAL in *family, the grid / joint bucket in *bucket. */
+int dexr_model_kernel_f64(const dexr_model* m, int32_t* family, int32_t* bucket);
 /* [not-in-ref] Pre-allocate what the `_dev` entry points would otherwise allocate lazily for batches of up to max_batch frames:
  * the hard-frames-first workspaces of the sixteen-lane kernel (dexr_tuning.longest_first; DexPilot batches of >= 32 768 frames
  * by default).  Without it the FIRST such call does a hipMalloc and a call with a larger batch than any before does
