@@ -49,7 +49,7 @@ EXPORTS = ["dexr_last_error", "dexr_version", "dexr_device_count", "dexr_default
            "dexr_retarget_multi_dev", "dexr_retarget_multi", "dexr_retarget", "dexr_retarget_f64",
            "dexr_retarget_kp_dev", "dexr_retarget_kp", "dexr_eval", "dexr_fk", "dexr_mano_keypoints_dev",
            "dexr_mano_keypoints", "dexr_comm_unique_id", "dexr_comm_create", "dexr_comm_destroy", "dexr_comm_info",
-           "dexr_allgather", "dexr_comm_max_f64", "dexr_comm_barrier"]
+           "dexr_allgather", "dexr_comm_max_f64", "dexr_comm_barrier", "dexr_retarget_vjp_dev", "dexr_retarget_vjp"]
 UNIQUE_ID_BYTES = 128
 
 
@@ -103,6 +103,8 @@ def load() -> C.CDLL:
     lib.dexr_retarget_f64.argtypes = [vp, i64, f32p, f32p, f32p, u32p, f64p, i32p, i32p, optp]
     lib.dexr_eval.argtypes = [vp, i64, f32p, f32p, f32p, f64p, u32p, f64p, f64p]
     lib.dexr_fk.argtypes = [vp, i64, f64p, f64p]
+    lib.dexr_retarget_vjp_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.dexr_retarget_vjp.argtypes = [vp, i64, f32p, f32p, f32p, u32p, f32p, f32p, f32p, f32p, i32p]
     lib.dexr_mano_keypoints_dev.argtypes = [i64, vp, f32p, vp, vp, vp]
     lib.dexr_mano_keypoints.argtypes = [i64, f32p, f32p, f32p, f32p]
     lib.dexr_comm_unique_id.argtypes = [vp]
@@ -293,6 +295,26 @@ class Model:
                             _ptr(x, C.c_double), _ptr(state, C.c_uint32), _ptr(f, C.c_double), _ptr(g, C.c_double)))
         return f, g
 
+    def vjp(self, ref, fixed, last, q, grad_q, state=None):
+        """Host-array twin of vjp_dev: (grad_ref (B,n_ref,3), grad_last (B,n_opt), status (B,)) float32 / int32."""
+        lib = load()
+        ref = np.ascontiguousarray(ref, dtype=np.float32)
+        last = np.ascontiguousarray(last, dtype=np.float32)
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        grad_q = np.ascontiguousarray(grad_q, dtype=np.float32)
+        B = last.shape[0]
+        if q.shape != last.shape or grad_q.shape != last.shape:
+            raise ValueError(f"q and grad_q must have the shape of last_qpos {last.shape}")
+        fixed = None if fixed is None or fixed.size == 0 else np.ascontiguousarray(fixed, dtype=np.float32)
+        state = None if state is None else np.ascontiguousarray(state, dtype=np.uint32)
+        gref = np.zeros(ref.shape, dtype=np.float32)
+        glast = np.zeros(last.shape, dtype=np.float32)
+        status = np.zeros(B, dtype=np.int32)
+        check(lib.dexr_retarget_vjp(self._h, B, _ptr(ref, C.c_float), _ptr(fixed, C.c_float), _ptr(last, C.c_float),
+                                    _ptr(state, C.c_uint32), _ptr(q, C.c_float), _ptr(grad_q, C.c_float),
+                                    _ptr(gref, C.c_float), _ptr(glast, C.c_float), _ptr(status, C.c_int32)))
+        return gref, glast, status
+
     def fk(self, q, n_links: int):
         lib = load()
         q = np.ascontiguousarray(q, dtype=np.float64)
@@ -319,6 +341,14 @@ class Model:
         check(fn(self._h, B, ref_ptr or None, fixed_ptr or None, last_ptr or None,
                  state_ptr or None, q_ptr or None, status_ptr or None, iters_ptr or None,
                  fval_ptr or None, C.byref(opts) if opts is not None else None, stream or None))
+
+    def vjp_dev(self, B: int, ref_ptr: int, fixed_ptr: int, last_ptr: int, state_ptr: int, q_ptr: int, grad_q_ptr: int,
+                grad_ref_ptr: int, grad_last_ptr: int = 0, status_ptr: int = 0, stream: int = 0):
+        """Implicit-function VJP of the solve at q (dexr_retarget_vjp_dev); device addresses of C-contiguous arrays, enqueued
+        on `stream`.  `ref_ptr` addresses (B,n_ref,3) ref_value rows; state / grad_last / status may be 0 (NULL)."""
+        check(load().dexr_retarget_vjp_dev(self._h, B, ref_ptr or None, fixed_ptr or None, last_ptr or None,
+                                           state_ptr or None, q_ptr or None, grad_q_ptr or None, grad_ref_ptr or None,
+                                           grad_last_ptr or None, status_ptr or None, stream or None))
 
 
 def seq_compose_dev(B: int, T: int, dof_kind, dof_idx, dof_mult, dof_off, n_opt: int, n_fixed: int, qraw_ptr: int,

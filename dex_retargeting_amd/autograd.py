@@ -1,0 +1,150 @@
+"""Differentiable retargeting: ``q = retarget(optimizer, ref_value, last_qpos)`` as a torch autograd function.
+
+The forward is the product solve (``optimizer.device_model()``, ``dexr_retarget_dev``: the same kernels and the same answers
+as ``retarget_batch``) enqueued on the current torch stream.  The backward is the implicit-function VJP of the argmin at the
+forward's answer (``dexr_retarget_vjp_dev``, MODE_VJP of the general kernel on ``optimizer.vjp_model()``): one exact Hessian,
+one factorisation, one solve per frame -- no unrolling of the solver.
+
+    v = H_SS^-1 dL/dq_S          H: exact Hessian of F = f + norm_delta |q - last|^2, S: variables not on a bound
+    dL/dlast_qpos = 2 norm_delta v
+    dL/dref_value[r] = (dT_r/dr)^T w_r Hess(SmoothL1)(e_r) (J_r v)
+
+Variables that sit on a joint limit are held (zero gradient through them).  ``fixed_qpos``, the DexPilot ``state`` and the
+config scalars get no gradient; the DexPilot weights and projection bits are piecewise constant in ref_value and are held.
+Frames whose forward solve fell back to last_qpos (non-finite state) and frames whose Hessian is not positive definite at q get
+zero gradients.
+"""
+from __future__ import annotations
+
+STATUS_FALLBACK = 2  # == DEXR_STATUS_FALLBACK
+
+
+def _check(optimizer, ref_value, last_qpos, fixed_qpos, state):
+    """Every argument rule -- types, dtypes, shapes, then the device -- before anything touches the GPU."""
+    import torch
+
+    if not isinstance(ref_value, torch.Tensor) or not isinstance(last_qpos, torch.Tensor):
+        raise ValueError("ref_value and last_qpos must be torch tensors")
+    named = [("ref_value", ref_value), ("last_qpos", last_qpos)]
+    if fixed_qpos is not None:
+        if not isinstance(fixed_qpos, torch.Tensor):
+            raise ValueError("fixed_qpos must be a torch tensor")
+        named.append(("fixed_qpos", fixed_qpos))
+    for name, t in named:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if last_qpos.ndim != 2 or last_qpos.shape[1] != optimizer.opt_dof:
+        raise ValueError(f"last_qpos must have shape (B, {optimizer.opt_dof}), got {tuple(last_qpos.shape)}")
+    B = last_qpos.shape[0]
+    n_ref = int(optimizer.compiled_model().n_ref)
+    if tuple(ref_value.shape) != (B, n_ref, 3):
+        raise ValueError(f"ref_value must have shape ({B}, {n_ref}, 3), got {tuple(ref_value.shape)}")
+    n_fixed = len(optimizer.idx_pin2fixed)
+    if n_fixed > 0 and fixed_qpos is None:
+        raise ValueError(f"the optimizer has {n_fixed} fixed joints: fixed_qpos of shape ({B}, {n_fixed}) is required")
+    if fixed_qpos is not None and tuple(fixed_qpos.shape) != (B, n_fixed):
+        raise ValueError(f"fixed_qpos must have shape ({B}, {n_fixed}), got {tuple(fixed_qpos.shape)}")
+    if state is not None:
+        if not isinstance(state, torch.Tensor) or state.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or \
+                tuple(state.shape) != (B,) or not state.is_contiguous():
+            raise ValueError(f"state must be a contiguous int32 / uint32 torch tensor of shape ({B},)")
+        named.append(("state", state))
+    dev = last_qpos.device
+    if dev.type != "cuda":
+        raise ValueError(f"the tensors must be CUDA (HIP) tensors, got device {dev}")
+    for name, t in named:
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, last_qpos on {dev}: all tensors must be on one CUDA device")
+
+
+def _make_function():
+    import torch
+
+    class _Retarget(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, ref_value, last_qpos, fixed_qpos, state, optimizer):
+            B = last_qpos.shape[0]
+            ref = ref_value.detach().contiguous()
+            last = last_qpos.detach().contiguous()
+            fixed = None if fixed_qpos is None or fixed_qpos.shape[1] == 0 else fixed_qpos.detach().contiguous()
+            # the bits the forward READS: the solve updates `state` in place, the backward needs them as they were
+            state_in = None if state is None else state.clone()
+            q = torch.empty_like(last)
+            status = torch.zeros(B, dtype=torch.int32, device=last.device)
+            stream = torch.cuda.current_stream(last.device).cuda_stream
+            if B > 0:
+                optimizer.device_model().retarget_dev(
+                    B, ref.data_ptr(), 0 if fixed is None else fixed.data_ptr(), last.data_ptr(),
+                    0 if state is None else state.data_ptr(), q.data_ptr(), status.data_ptr(),
+                    opts=optimizer._options(), stream=stream)
+            ctx.optimizer = optimizer
+            ctx.has_fixed = fixed is not None
+            ctx.has_state = state_in is not None
+            saved = [ref, last, q, status] + ([fixed] if fixed is not None else []) + ([state_in] if state_in is not None else [])
+            ctx.save_for_backward(*saved)
+            return q
+
+        @staticmethod
+        def backward(ctx, grad_q):
+            if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+                return None, None, None, None, None
+            saved = list(ctx.saved_tensors)
+            ref, last, q, status = saved[:4]
+            rest = saved[4:]
+            fixed = rest.pop(0) if ctx.has_fixed else None
+            state_in = rest.pop(0) if ctx.has_state else None
+            B = last.shape[0]
+            gq = grad_q.detach().to(torch.float32).contiguous()
+            gref = torch.zeros_like(ref)
+            glast = torch.zeros_like(last)
+            if B > 0:
+                vstatus = torch.zeros(B, dtype=torch.int32, device=last.device)
+                stream = torch.cuda.current_stream(last.device).cuda_stream
+                ctx.optimizer.vjp_model().vjp_dev(
+                    B, ref.data_ptr(), 0 if fixed is None else fixed.data_ptr(), last.data_ptr(),
+                    0 if state_in is None else state_in.data_ptr(), q.data_ptr(), gq.data_ptr(), gref.data_ptr(),
+                    glast.data_ptr(), vstatus.data_ptr(), stream=stream)
+                # a forward that fell back to last_qpos returned no minimiser: no implicit gradient for that frame
+                keep = (status != STATUS_FALLBACK).to(torch.float32)
+                gref = gref * keep[:, None, None]
+                glast = glast * keep[:, None]
+            return (gref if ctx.needs_input_grad[0] else None, glast if ctx.needs_input_grad[1] else None, None, None, None)
+
+    return _Retarget
+
+
+_FN = None
+
+
+def retarget(optimizer, ref_value, last_qpos, fixed_qpos=None, state=None):
+    """Differentiable batched solve: ref_value (B, n_ref, 3), last_qpos (B, n_opt), fixed_qpos (B, n_fixed) or None -- float32
+    CUDA tensors -- and the DexPilot projection bits `state` (B,) int32 (updated in place, as retarget_batch does; None: zero
+    bits, not carried) -> q (B, n_opt) float32.  Gradients flow to ref_value and last_qpos."""
+    global _FN
+    _check(optimizer, ref_value, last_qpos, fixed_qpos, state)
+    if _FN is None:
+        _FN = _make_function()
+    import torch
+
+    with torch.cuda.device(last_qpos.device):
+        return _FN.apply(ref_value, last_qpos, fixed_qpos, state, optimizer)
+
+
+def ref_value_from_keypoints(optimizer, keypoints):
+    """ref_value (B, n_ref, 3) from raw hand keypoints (B, n_keypoints, 3) in torch -- the gather retarget_keypoints_batch does
+    inside the kernel: kp[task] - kp[origin] for vector / DexPilot rows, kp[idx] for position rows -- so that gradients reach
+    the keypoints."""
+    import torch
+
+    hi = optimizer.target_link_human_indices
+    if hi is None:
+        raise ValueError("this optimizer carries no target_link_human_indices")
+    if not isinstance(keypoints, torch.Tensor) or keypoints.ndim != 3 or keypoints.shape[2] != 3:
+        raise ValueError("keypoints must be a (B, n_keypoints, 3) torch tensor")
+    idx = torch.as_tensor(hi, dtype=torch.long, device=keypoints.device)
+    if idx.ndim == 1:
+        return keypoints[:, idx]
+    return keypoints[:, idx[1]] - keypoints[:, idx[0]]
+
+
+__all__ = ["retarget", "ref_value_from_keypoints"]

@@ -603,7 +603,7 @@ bool build_wide_tables(dexr_model* m) {
 #ifndef DEXR_GEN_LAM_JUMP
 #define DEXR_GEN_LAM_JUMP 0.03f  // (measured, 16 384 tracking frames: arm + hand 10.3 -> 7.2 passes, -11 % time; Shadow DexPilot on generic tables 9.8 -> 8.2, -15 %; LEAP position -3 %; larger jumps leave frames over-damped up to max_iter -- profiles/r06_general_kernel_damping_jump.txt)
 #endif
-int launch_gen_model(const dexr_model* m, int mode, dexr::KernelParams kp, hipStream_t st) {
+int launch_gen_model(const dexr_model* m, int mode, dexr::KernelParams kp, hipStream_t st, const dexr::GenVjp* vj = nullptr) {
   const size_t lds = dexr::gen_lds_bytes(m->gen_tab);
   if (lds > 160 * 1024) return fail(DEXR_ERR_UNSUPPORTED, "model needs %zu B of LDS per frame", lds);
   // one wave per frame; as many resident waves as the LDS allows (at most 8 per CU), persistent over the batch
@@ -620,7 +620,7 @@ int launch_gen_model(const dexr_model* m, int mode, dexr::KernelParams kp, hipSt
   }
 #endif
   kp.lam_jump = m->lam_jump_user >= 0.f ? m->lam_jump_user : DEXR_GEN_LAM_JUMP;  // (x mean diag of the free block, dexr_gen.hpp)
-  hipError_t e = dexr::launch_gen(mode, kp, m->gen_tab, dim3((unsigned)blocks), lds, st);
+  hipError_t e = dexr::launch_gen(mode, kp, m->gen_tab, dim3((unsigned)blocks), lds, st, vj);
   if (e != hipSuccess) return fail(DEXR_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
 #ifdef DEXR_GEN_PROF
   if (mode == dexr::MODE_SOLVE) {
@@ -1480,6 +1480,77 @@ int dexr_eval(const dexr_model* m, int64_t B, const float* ref, const float* fix
   kp.f64out = sg.dev<double>(hc, i_f);
   kp.g64out = sg.dev<double>(hc, i_g);
   int rc = launch(m, dexr::MODE_EVAL, 1, kp, hc.st);
+  if (rc != DEXR_OK) return rc;
+  HIP_TRY(sg.download(hc));
+  return DEXR_OK;
+}
+
+// [not-in-ref] implicit-function VJP of the argmin (MODE_VJP of the general kernel, dexr_gen.hpp): generic-table handles only
+static int vjp_check(const dexr_model* m, int64_t B, const float* ref, const float* fixed, const float* last, const float* q,
+                     const float* grad_q, const float* grad_ref_out) {
+  if (!m || !ref || !last || !q || !grad_q || !grad_ref_out) return fail(DEXR_ERR_INVALID, "null argument");
+  if (m->h.kind == DEXR_KIND_FKONLY) return fail(DEXR_ERR_INVALID, "model is an FK-only table");
+  if (!m->gen)
+    return fail(DEXR_ERR_UNSUPPORTED, "the VJP runs on the general kernel only: build the handle from generic tables "
+                                      "(Optimizer.vjp_model(), or compile the model with force_generic=True)");
+  if (m->h.n_fixed > 0 && !fixed) return fail(DEXR_ERR_INVALID, "model has %d fixed joints but fixed_qpos is NULL", m->h.n_fixed);
+  if (B < 0) return fail(DEXR_ERR_INVALID, "negative batch");
+  return DEXR_OK;
+}
+
+static void vjp_params(const dexr_model* m, dexr::KernelParams& kp, int64_t B) {
+  fill_params(m, kp, B);
+  apply_options(m, kp, nullptr);
+  kp.newton = 1;  // the exact Hessian: the second-order kinematic term is part of it
+}
+
+int dexr_retarget_vjp_dev(const dexr_model* m, int64_t B, const float* ref, const float* fixed, const float* last,
+                          const uint32_t* state_in, const float* q, const float* grad_q, float* grad_ref_out,
+                          float* grad_last_out, int32_t* status_out, void* stream) {
+  int rc = vjp_check(m, B, ref, fixed, last, q, grad_q, grad_ref_out);
+  if (rc != DEXR_OK || B == 0) return rc;
+  dexr::KernelParams kp;
+  vjp_params(m, kp, B);
+  kp.ref = ref;
+  kp.fixed = fixed;
+  kp.last = last;
+  kp.state = const_cast<uint32_t*>(state_in);  // (read, never written, in this mode)
+  kp.status = status_out;
+  const dexr::GenVjp vj{q, grad_q, grad_ref_out, grad_last_out};
+  return launch_gen_model(m, dexr::MODE_VJP, kp, static_cast<hipStream_t>(stream), &vj);
+}
+
+int dexr_retarget_vjp(const dexr_model* m, int64_t B, const float* ref, const float* fixed, const float* last,
+                      const uint32_t* state_in, const float* q, const float* grad_q, float* grad_ref_out,
+                      float* grad_last_out, int32_t* status_out) {
+  int rc = vjp_check(m, B, ref, fixed, last, q, grad_q, grad_ref_out);
+  if (rc != DEXR_OK || B == 0) return rc;
+  const size_t nb = (size_t)B;
+  const size_t ref_b = nb * m->h.n_ref * 3 * sizeof(float), fix_b = nb * m->h.n_fixed * sizeof(float);
+  const size_t q_b = nb * m->h.n_opt * sizeof(float);
+  std::lock_guard<std::mutex> lock(m->host.mu);
+  dexr::HostCtx& hc = m->host;
+  dexr::Staging sg;
+  const int i_ref = sg.add(dexr::Staging::IN, ref, nullptr, ref_b);
+  const int i_fix = sg.add(dexr::Staging::IN, fixed, nullptr, fix_b);
+  const int i_last = sg.add(dexr::Staging::IN, last, nullptr, q_b);
+  const int i_state = sg.add(dexr::Staging::IN, state_in, nullptr, state_in ? nb * sizeof(uint32_t) : 0);
+  const int i_q = sg.add(dexr::Staging::IN, q, nullptr, q_b);
+  const int i_gq = sg.add(dexr::Staging::IN, grad_q, nullptr, q_b);
+  const int i_gref = sg.add(dexr::Staging::OUT, nullptr, grad_ref_out, ref_b);
+  const int i_glast = sg.add(dexr::Staging::OUT, nullptr, grad_last_out, grad_last_out ? q_b : 0);
+  const int i_status = sg.add(dexr::Staging::OUT, nullptr, status_out, status_out ? nb * sizeof(int32_t) : 0);
+  HIP_TRY(sg.upload(hc));
+  dexr::KernelParams kp;
+  vjp_params(m, kp, B);
+  kp.ref = sg.dev<float>(hc, i_ref);
+  kp.fixed = sg.dev<float>(hc, i_fix);
+  kp.last = sg.dev<float>(hc, i_last);
+  kp.state = state_in ? sg.dev<uint32_t>(hc, i_state) : nullptr;
+  kp.status = status_out ? sg.dev<int32_t>(hc, i_status) : nullptr;
+  const dexr::GenVjp vj{sg.dev<float>(hc, i_q), sg.dev<float>(hc, i_gq), sg.dev<float>(hc, i_gref),
+                        grad_last_out ? sg.dev<float>(hc, i_glast) : nullptr};
+  rc = launch_gen_model(m, dexr::MODE_VJP, kp, hc.st, &vj);
   if (rc != DEXR_OK) return rc;
   HIP_TRY(sg.download(hc));
   return DEXR_OK;

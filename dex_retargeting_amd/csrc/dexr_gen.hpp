@@ -46,6 +46,15 @@ struct GenTab {  // device pointers into the uploaded generic table
       *term_ref, *row_ho, *row_ht;
 };
 
+// MODE_VJP's own arrays: a kernel argument of their own (unused by the other modes), so that KernelParams -- and with it
+// the code generated for every other kernel -- stays as it is
+struct GenVjp {
+  const float* q;   // B x n_opt: the point (the forward's answer)
+  const float* gq;  // B x n_opt: dL/dq
+  float* gref;      // B x n_ref x 3: dL/dref
+  float* glast;     // B x n_opt: dL/dlast (NULL: not wanted)
+};
+
 // LDS of one wave, in doubles.  [scratch | live | tables]: "scratch" is everything an evaluation / model assembly
 // produces and the factorisation no longer needs -- world transforms, frame positions, term records, column buffers --
 // and the row-major copy of the Cholesky factor (gen_factor_solve) lies over it.
@@ -267,7 +276,7 @@ template <int MODE, int NI>
 #ifndef DEXR_GEN_SMALL_MINW
 #define DEXR_GEN_SMALL_MINW 2
 #endif
-__global__ void __launch_bounds__(64, NI <= GEN_NI_TINY ? 2 : (NI == GEN_NI_SMALL ? DEXR_GEN_SMALL_MINW : 1)) dexr_gen_kernel(KernelParams kp, GenTab tb) {
+__global__ void __launch_bounds__(64, NI <= GEN_NI_TINY ? 2 : (NI == GEN_NI_SMALL ? DEXR_GEN_SMALL_MINW : 1)) dexr_gen_kernel(KernelParams kp, GenTab tb, GenVjp vj) {
   extern __shared__ __align__(16) double gen_lds[];
   constexpr int NSLOT = NI * (NI + 1) / 2;  // entries of the lower triangle a lane of the grid owns: tiles (i, j), j <= i
   constexpr int NV = NI * 8;                // rows the register factorisation holds
@@ -414,6 +423,7 @@ __global__ void __launch_bounds__(64, NI <= GEN_NI_TINY ? 2 : (NI == GEN_NI_SMAL
         const int api = my_api;
         double v, l;
         if (MODE == MODE_EVAL) v = kp.xin[it * kp.n_opt + api];
+        else if (MODE == MODE_VJP) v = (double)vj.q[r0 * ld + api];
         else if (carry) v = (double)(float)x[lane];  // the reference carries the float32 result (optimizer.py:99)
         else if (kp.x0) v = (double)kp.x0[r0 * ld + api];
         else v = (double)kp.last[r0 * ld + api];
@@ -912,6 +922,118 @@ __global__ void __launch_bounds__(64, NI <= GEN_NI_TINY ? 2 : (NI == GEN_NI_SMAL
           if (dexpilot && kp.state) kp.state[r0] = nst;
         }
         if (is_v) kp.g64out[r0 * kp.n_opt + my_api] = g[lane] + 2.0 * delta * (x[lane] - my_xl);
+        gen_sync();
+        continue;
+      }
+
+      if (MODE == MODE_VJP) {
+        // Implicit-function VJP of the argmin at the given x = q: H_SS v = gq_S with H the exact Hessian of F (the solve's
+        // Newton model, undamped) restricted to the free variables S, then dL/dlast = 2 norm_delta v and, per term t,
+        // dL/dref_t = (dT_t/dr_t)^T Hess_e(rho)(e_t) (J_t v).  The DexPilot weights and projection bits are piecewise constant
+        // in ref: the preamble above ran from the caller's state, read-only, and they are held.
+        // lane t: its ref row r and the target's Jacobian dT/dr -- my_dsc I, or that of the DexPilot projection
+        // my_eta r / (|r| + 1e-6) where my_eta > 0 (formed here, not in the pre-amble: the other modes' code stays as it is)
+        double my_rv[3] = {0, 0, 0}, my_dsc = 0.0, my_eta = 0.0;
+        if (is_t) {
+          const int row = tb.term_ref[lane];
+          float rv[3];
+          ref_row(row, rv);
+          for (int i = 0; i < 3; ++i) my_rv[i] = (double)rv[i];
+          my_dsc = kp.kind == DEXR_KIND_POSITION ? 1.0 : (double)kp.scaling;
+          if (dexpilot) {
+            const int F = kp.num_fingers, n_pair = F * (F - 1) / 2;
+            if (row < n_pair && ((nst >> row) & 1u)) {
+              my_eta = (double)(row < F - 1 ? kp.eta1 : kp.eta2);
+              my_dsc = 0.0;
+            }
+          }
+        }
+        double my_gq = 0.0;
+        bool held = false, nonfin = false;
+        if (is_v) {
+          my_gq = (double)vj.gq[r0 * ld + my_api];
+          const double xv = x[lane], lo = my_lo, hi = my_hi;
+          // on its box bound up to float32 rounding of the float64 bound (the kernels clip to the box): 4 ulps
+          held = xv <= lo + 4.0 * 1.1920928955078125e-7 * fabs(lo) || xv >= hi - 4.0 * 1.1920928955078125e-7 * fabs(hi);
+          nonfin = !isfinite(xv) || !isfinite(my_xl) || !isfinite(my_gq);
+        }
+        if (is_t) nonfin = nonfin || !isfinite(my_rv[0]) || !isfinite(my_rv[1]) || !isfinite(my_rv[2]);
+        if (is_j && my_var < 0) nonfin = nonfin || !isfinite(my_qfix);
+        nonfin = __any(nonfin);  // (wave-uniform)
+        int status = nonfin ? 2 : 0;
+        double gr[3] = {0, 0, 0};
+        if (!nonfin) {
+          eval_value(x);
+          assemble_model();  // (kp.newton = 1: the exact Hessian of the data term)
+          if (is_v) {
+            H[GEN_TRI(lane, lane)] += 2.0 * delta;
+            act[lane] = held ? 1.0 : 0.0;
+            g[lane] = held ? 0.0 : -my_gq;  // (gen_factor_solve solves for -g)
+          }
+          gen_sync();
+          const bool chol_ok = gen_factor_solve<NV>(lane, nv, gen_lds_addr(H), gen_lds_addr(g), gen_lds_addr(act), 0.0, gen_lds_addr(Lt),
+                                                    gen_lds_addr(s));
+          gen_sync();
+          if (!chol_ok) status = 1;
+        }
+        if (status == 0) {
+          eval_value(x);  // (the factor's copy lay over the term records: the same point, the same records again)
+          // J_t v for every term: lane k adds joint k's column times its share of v (families folded by the sum over joints)
+          const double my_v = my_var >= 0 ? my_jmul * s[my_var] : 0.0;
+          double my_jv[3] = {0, 0, 0};
+          for (int t = 0; t < nt; ++t) {  // wave-uniform
+            const double* rc = rec + t * 16;
+            const unsigned wt_ = t < 32 ? (unsigned)on_task : (unsigned)(on_task >> 32), wo_ = t < 32 ? (unsigned)on_origin : (unsigned)(on_origin >> 32);
+            const double sT = (double)((wt_ >> (t & 31)) & 1u), sO = (double)((wo_ >> (t & 31)) & 1u);
+            double dv[3], c[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) dv[i] = sT * (rc[i] - my_o[i]) - sO * (rc[3 + i] - my_o[i]);
+            c[0] = my_a[1] * dv[2] - my_a[2] * dv[1];
+            c[1] = my_a[2] * dv[0] - my_a[0] * dv[2];
+            c[2] = my_a[0] * dv[1] - my_a[1] * dv[0];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) c[i] = my_var < 0 ? 0.0 : (my_rev ? c[i] : (sT - sO) * my_a[i]) * my_v;
+            const double j0 = gen_wave_sum(c[0]), j1 = gen_wave_sum(c[1]), j2 = gen_wave_sum(c[2]);
+            if (lane == t) {
+              my_jv[0] = j0;
+              my_jv[1] = j1;
+              my_jv[2] = j2;
+            }
+          }
+          if (is_t) {
+            // y = w Hess_e(rho) J_t v from the term's record: position diag(k); vector kinds c1 I + (c2 - c1) u u^T
+            const double* rc = rec + lane * 16;
+            double y[3];
+            if (pos) {
+#pragma unroll
+              for (int i = 0; i < 3; ++i) y[i] = rc[12 + i] * my_jv[i];
+            } else {
+              const double uj = rc[9] * my_jv[0] + rc[10] * my_jv[1] + rc[11] * my_jv[2];
+#pragma unroll
+              for (int i = 0; i < 3; ++i) y[i] = rc[12] * my_jv[i] + rc[15] * uj * rc[9 + i];
+            }
+            if (my_eta > 0.0) {  // T = eta r / (n + e): dT/dr = eta (I / (n + e) - r r^T / (n (n + e)^2)), symmetric
+              const double n = ::sqrt(my_rv[0] * my_rv[0] + my_rv[1] * my_rv[1] + my_rv[2] * my_rv[2]);
+              const double a = 1.0 / (n + (double)1e-6f);
+              const double ry = my_rv[0] * y[0] + my_rv[1] * y[1] + my_rv[2] * y[2];
+              const double b = n > 0.0 ? ry * a * a / n : 0.0;
+#pragma unroll
+              for (int i = 0; i < 3; ++i) gr[i] = my_eta * (a * y[i] - b * my_rv[i]);
+            } else {
+#pragma unroll
+              for (int i = 0; i < 3; ++i) gr[i] = my_dsc * y[i];
+            }
+          }
+        }
+        // ---- write the frame's gradients (zeros unless status 0) -----------------------------------------------------
+        const bool good = status == 0;
+        if (is_t) {
+          const int row = tb.term_ref[lane];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) vj.gref[(it * kp.n_ref + row) * 3 + i] = good ? (float)gr[i] : 0.f;
+        }
+        if (is_v && vj.glast) vj.glast[it * ld + my_api] = good ? (float)(2.0 * delta * s[lane]) : 0.f;
+        if (lane == 0 && kp.status) kp.status[it] = status;
         gen_sync();
         continue;
       }

@@ -165,7 +165,7 @@ struct WideTable {
 #define WTRACE_FLUSH()
 #endif
 
-enum { MODE_SOLVE = 0, MODE_EVAL = 1, MODE_FK = 2 };
+enum { MODE_SOLVE = 0, MODE_EVAL = 1, MODE_FK = 2, MODE_VJP = 3 };  // (MODE_VJP: general kernel only)
 enum { ST_CONVERGED = 0, ST_MAXITER = 1, ST_FALLBACK = 2 };  // == DEXR_STATUS_* in dexr.h
 
 // FAST selects, for double, the hardware-estimate versions of 1 / sqrt, sqrt and division (see the specialisation below); float has one version.

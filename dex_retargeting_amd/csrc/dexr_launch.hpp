@@ -127,7 +127,8 @@ static inline launch_fn find_red_launcher(int nv_bucket) {
 
 // general kernel (dexr_gen.hpp): models described by the generic table format
 struct GenTab;
-hipError_t launch_gen(int mode, const KernelParams& kp, const GenTab& tb, dim3 grid, size_t lds, hipStream_t st);
+struct GenVjp;  // MODE_VJP's arrays (NULL for the other modes)
+hipError_t launch_gen(int mode, const KernelParams& kp, const GenTab& tb, dim3 grid, size_t lds, hipStream_t st, const GenVjp* vj = nullptr);
 size_t gen_lds_bytes(const GenTab& tb);
 
 static inline launch_fn find_launcher(int bucket, int f64, int mode, bool chain = false, bool ext = false, bool tip = false) {

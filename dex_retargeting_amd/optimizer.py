@@ -77,6 +77,7 @@ class Optimizer:
         self._upper = np.full(self.opt_dof, np.inf)
         self._model: Optional[_lib.Model] = None
         self._compiled: Optional[mc.CompiledModel] = None
+        self._vjp_model: Optional[_lib.Model] = None  # vjp_model(): the same problem on generic tables
         # True: compile to the generic table format even when the model fits the fixed-size records (the general kernel
         # then serves it; used by the tests that cross-check that kernel on the shipped robots)
         self.use_generic_tables = False
@@ -95,6 +96,7 @@ class Optimizer:
         self._upper = joint_limits[:, 1] + epsilon
         self.opt.lower, self.opt.upper = self._lower.tolist(), self._upper.tolist()
         self._model = None
+        self._vjp_model = None
 
     def get_link_indices(self, target_link_names):
         return [self.robot.get_link_index(link_name) for link_name in target_link_names]
@@ -106,6 +108,7 @@ class Optimizer:
             mimic_idx = adaptor.idx_pin2mimic
             self.idx_pin2fixed = np.array([x for x in fixed_idx if x not in mimic_idx], dtype=int)
         self._model = None
+        self._vjp_model = None
 
     @property
     def fixed_joint_names(self):
@@ -126,17 +129,20 @@ class Optimizer:
 
     def compiled_model(self) -> mc.CompiledModel:
         if self._compiled is None or self._model is None:
-            mimic = []
-            if isinstance(self.adaptor, MimicJointKinematicAdaptor):
-                a = self.adaptor
-                mimic = [(int(m), int(s), float(mu), float(of)) for m, s, mu, of in
-                         zip(a.idx_pin2mimic, a.idx_pin2source, a.multipliers, a.offsets)]
-            self._compiled = mc.compile_model(
-                self.robot.kin, self._kind(), self.idx_pin2target.tolist(), self.idx_pin2fixed.tolist(), self._terms(),
-                lower=self._lower, upper=self._upper, mimic=mimic,
-                human_indices=self.target_link_human_indices, force_generic=self.use_generic_tables,
-                **self._compile_kwargs())
+            self._compiled = self._compile(self.use_generic_tables)
         return self._compiled
+
+    def _compile(self, force_generic: bool) -> mc.CompiledModel:
+        mimic = []
+        if isinstance(self.adaptor, MimicJointKinematicAdaptor):
+            a = self.adaptor
+            mimic = [(int(m), int(s), float(mu), float(of)) for m, s, mu, of in
+                     zip(a.idx_pin2mimic, a.idx_pin2source, a.multipliers, a.offsets)]
+        return mc.compile_model(
+            self.robot.kin, self._kind(), self.idx_pin2target.tolist(), self.idx_pin2fixed.tolist(), self._terms(),
+            lower=self._lower, upper=self._upper, mimic=mimic,
+            human_indices=self.target_link_human_indices, force_generic=force_generic,
+            **self._compile_kwargs())
 
     def device_model(self) -> _lib.Model:
         if self._model is None:
@@ -150,6 +156,16 @@ class Optimizer:
             self._model.tune(kernel_f64=_lib.KERNEL_WIDE if want else _lib.KERNEL_AUTO)
             self._f64_applied = want
         return self._model
+
+    def vjp_model(self) -> _lib.Model:
+        """The handle the implicit-gradient VJP runs on (dexr_retarget_vjp_dev): the same problem compiled to the generic
+        table format, whose general kernel has the VJP mode.  Built on first use; dropped whenever device_model()'s handle
+        is (set_joint_limit, set_kinematic_adaptor).  With use_generic_tables on it IS device_model()'s handle."""
+        if self.use_generic_tables:
+            return self.device_model()
+        if self._vjp_model is None:
+            self._vjp_model = _lib.Model(self._compile(True).to_blob())
+        return self._vjp_model
 
     def _options(self) -> Optional[_lib.SolveOptions]:
         if all(v is None for v in self.solve_options.values()):

@@ -228,6 +228,28 @@ int dexr_eval(const dexr_model* m, int64_t B, const float* ref, const float* fix
  * pos_out: B x n_ref x 3 float64.  Host pointers. */
 int dexr_fk(const dexr_model* m, int64_t B, const double* q, double* pos_out);
 
+/* [not-in-ref] Vector-Jacobian product of the solve: the implicit-function VJP of the argmin q*(ref, last) of
+ * F = f + norm_delta |x - last|^2 over the box, taken at the given q (the forward's answer), float64 arithmetic.
+ *   H_SS v = grad_q_S     H: exact Hessian of F at q (SmoothL1 curvature, second-order kinematic term, mimic fold,
+ *                         2 norm_delta I); S: the free variables
+ *   grad_last_out = 2 norm_delta v
+ *   grad_ref_out[r] = (dT_r/dr)^T w_r Hess(SmoothL1)(e_r) (J_r v)   T_r: the target the forward formed from ref row r
+ * Held set: a variable whose q lies on its box bound (within 4 float32 ulps of the table's bound) is held: its row and
+ * column of H are dropped, its grad_q entry is ignored and its grad_last entry is 0.  DexPilot weights and projection
+ * bits are piecewise constant in ref and are held as the forward formed them from `state_in` (the bits the FORWARD read;
+ * NULL = zero bits; never written here).  ref: B x n_ref x 3 ref_value rows (not keypoints); fixed: B x n_fixed;
+ * last, q, grad_q, grad_last_out: B x n_opt; grad_ref_out: B x n_ref x 3; status_out: B.  grad_last_out and status_out may
+ * be NULL.  Status per frame: 0 ok; 1 H_SS not positive definite (q is no strict local minimiser); 2 non-finite input or
+ * q.  Frames of status 1 / 2 get zero outputs.  No gradient flows to fixed_qpos, state or the config scalars.
+ * Handles compiled from generic tables only (the general kernel); any other returns DEXR_ERR_UNSUPPORTED. */
+int dexr_retarget_vjp_dev(const dexr_model* m, int64_t B, const float* ref, const float* fixed, const float* last,
+                          const uint32_t* state_in, const float* q, const float* grad_q, float* grad_ref_out,
+                          float* grad_last_out, int32_t* status_out, void* stream);
+/* [not-in-ref] same, host pointers: copy, run, synchronise */
+int dexr_retarget_vjp(const dexr_model* m, int64_t B, const float* ref, const float* fixed, const float* last,
+                      const uint32_t* state_in, const float* q, const float* grad_q, float* grad_ref_out,
+                      float* grad_last_out, int32_t* status_out);
+
 /* ---- frame sequences: SeqRetargeting.retarget x T frames x B sequences in ONE launch --------
  * Per sequence exactly what /root/reference/src/dex_retargeting/seq_retarget.py:112-124 does per call: clip the carried
  * last_qpos to the joint limits, solve from it (start point and regularisation target), carry the UNFILTERED float32
