@@ -14,11 +14,7 @@ BUILD = os.environ.get("DEXR_BUILD_DIR") or os.path.join(REPO, "build")
 LIB = os.environ.get("DEXR_LIB_OUT") or os.path.join(HERE, "libdexr.so")
 BUCKETS = (4, 8, 16, 24, 32)
 CHAIN_BUCKETS = (4,)
-BIG_BUCKETS = (16, 24, 32)
 VARIANTS = ((0, 0), (1, 0), (1, 1), (1, 2))  # (float64?, mode): f32 solve, f64 solve, f64 eval, f64 fk
-BIG_HEADER = os.path.join(CSRC, "dexr_big.hpp")
-QUAD_HEADER = os.path.join(CSRC, "dexr_quad.hpp")
-QUAD_BUCKETS = (16, 24)
 HEADERS = [os.path.join(CSRC, "dexr_kernel.hpp"), os.path.join(CSRC, "dexr_launch.hpp"), os.path.join(CSRC, "dexr_tip.hpp"),
            os.path.join(CSRC, "dexr_math.hpp"),
            os.path.join(INCLUDE, "dexr.h"), os.path.join(INCLUDE, "dexr_tables.h")]
@@ -27,8 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", 
 # The SLP vectoriser turns the 3-vector arithmetic of the register kernels into v_pk_* pairs that it then has to
 # assemble with v_mov_b32 (342 moves in the 4-joint chain kernel) and that need aligned register pairs: without it the
 # same kernel has 9 % fewer VALU instructions, 126 instead of 156 VGPRs (4 waves per SIMD, no scratch) and runs
-# 25 % faster (Allegro vector 0.108 -> 0.081 ms per 65 536 frames; Shadow vector 9.4 -> 4.3 ms).  The LDS kernel
-# (dexr_big) measured no gain and keeps the default.
+# 25 % faster (Allegro vector 0.108 -> 0.081 ms per 65 536 frames; Shadow vector 9.4 -> 4.3 ms).
 # float32 divisions / square roots of the solver (step scaling, Huber weights, Cholesky pivots) do not need IEEE
 # rounding or denormal support -- parity is measured against the float64 oracle: 2.5-ulp v_rcp/v_rsq sequences and
 # flushed denormals save another 8 % of the chain kernel's VALU instructions.
@@ -40,13 +35,13 @@ NO_SLP = ["-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "
 _COMMON_SOURCES = ["dexr_api.hip", "dexr_launch.hpp", "../../include/dexr.h", "../../include/dexr_tables.h"]
 KERNEL_SOURCES = {
     "allegro_vector": ["dexr_kernel.hpp", "dexr_tip.hpp", "dexr_math.hpp", "dexr_inst.hip"],
-    "shadow_dexpilot": ["dexr_wide.hpp", "dexr_wide_inst.hip", "dexr_big.hpp", "dexr_math.hpp"],
-    "leap_position": ["dexr_wide.hpp", "dexr_wide_inst.hip", "dexr_big.hpp", "dexr_math.hpp"],
+    "shadow_dexpilot": ["dexr_wide.hpp", "dexr_wide_inst.hip", "dexr_math.hpp"],
+    "leap_position": ["dexr_wide.hpp", "dexr_wide_inst.hip", "dexr_math.hpp"],
     # sub-records of the default line (bench.py --probe): the float64 / cold-start launches of the headline config, the general
     # kernel; "mixed_fleet" is absent on purpose: four robots = every kernel family, i.e. all sources (the fallback)
     "allegro_vector_f64": ["dexr_kernel.hpp", "dexr_tip.hpp", "dexr_math.hpp", "dexr_inst.hip"],
     "allegro_vector_cold": ["dexr_kernel.hpp", "dexr_tip.hpp", "dexr_math.hpp", "dexr_inst.hip"],
-    "general_kernel": ["dexr_gen.hpp", "dexr_gen_inst.hip", "dexr_kernel.hpp", "dexr_big.hpp", "dexr_math.hpp"],
+    "general_kernel": ["dexr_gen.hpp", "dexr_gen_inst.hip", "dexr_kernel.hpp", "dexr_math.hpp"],
 }
 
 
@@ -119,58 +114,42 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
                 continue
             if force or _stale(o, [inst_s] + HEADERS):
                 jobs.append((inst_s, o, NO_SLP + [f"-DDEXR_NMAX={n}", f"-DDEXR_F64={f64}", f"-DDEXR_MODE={mode}"]))
-    big_s = os.path.join(CSRC, "dexr_big_inst.hip")
-    for n in BIG_BUCKETS:  # large-component kernel (Hessian in LDS, float64 kinematics)
-        o = os.path.join(BUILD, f"dexr_big_{n}.o")
-        objs.append(o)
-        if only is not None and n not in only and os.path.exists(o):
-            continue
-        if force or _stale(o, [big_s, BIG_HEADER] + HEADERS):
-            jobs.append((big_s, o, [f"-DDEXR_NMAX={n}"]))
-    quad_s = os.path.join(CSRC, "dexr_quad_inst.hip")
-    for n in QUAD_BUCKETS:  # four-lanes-per-frame kernel for dense components
-        o = os.path.join(BUILD, f"dexr_quad_{n}.o")
-        objs.append(o)
-        if only is not None and n not in only and os.path.exists(o):
-            continue
-        if force or _stale(o, [quad_s, QUAD_HEADER, BIG_HEADER] + HEADERS):
-            jobs.append((quad_s, o, NO_SLP + [f"-DDEXR_NMAX={n}"]))
     wide_s = os.path.join(CSRC, "dexr_wide_inst.hip")
     for n in (16, 24, 32):  # sixteen-lanes-per-frame kernel for dense components
         o = os.path.join(BUILD, f"dexr_wide_{n}.o")
         objs.append(o)
-        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp"), BIG_HEADER] + HEADERS):
+        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp")] + HEADERS):
             # the 16-row grid fits three waves per SIMD (168 VGPRs, 18 of them spilled; 11.8 KB of LDS per wave)
             jobs.append((wide_s, o, NO_SLP + [f"-DDEXR_NMAX={n}"] + (["-DDEXR_WIDE_MINW=3"] if n == 16 else [])))
     for n in (16, 24, 32):  # ... one frame per wave (SPRINT): the launch shape of small batches
         o = os.path.join(BUILD, f"dexr_wide_s_{n}.o")
         objs.append(o)
-        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp"), BIG_HEADER] + HEADERS):
+        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp")] + HEADERS):
             # (register budgets: two waves per SIMD for the 16- / 24-row grids (246 / 256 registers, 3 spilled at n = 24), one for
             # the 32-row grid (272): small batches do not need the occupancy)
             jobs.append((wide_s, o, NO_SLP + [f"-DDEXR_NMAX={n}", "-DDEXR_SPRINT=1", "-DDEXR_WIDE_MINW=1" if n == 32 else "-DDEXR_WIDE_MINW=2"]))
     for tag, defs in (("s_m", ["-DDEXR_SPRINT=1"]), ("s_mc", ["-DDEXR_SPRINT=1", "-DDEXR_MODCHOL=1"])):  # ... on the variable grid
         o = os.path.join(BUILD, f"dexr_wide_{tag}_16.o")
         objs.append(o)
-        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp"), BIG_HEADER] + HEADERS):
+        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp")] + HEADERS):
             jobs.append((wide_s, o, NO_SLP + ["-DDEXR_NMAX=16", "-DDEXR_MIMIC=1"] + defs))
     for tag, defs in (("m", []), ("mc", ["-DDEXR_MODCHOL=1"])):  # the same kernel on the grid of the optimised variables
         o = os.path.join(BUILD, f"dexr_wide_{tag}_16.o")         # (mimic joints), plain / modified Cholesky
         objs.append(o)
-        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp"), BIG_HEADER] + HEADERS):
+        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp")] + HEADERS):
             jobs.append((wide_s, o, NO_SLP + ["-DDEXR_NMAX=16", "-DDEXR_MIMIC=1"] + defs))
     for tag, defs in (("16", ["-DDEXR_NMAX=16"]), ("24", ["-DDEXR_NMAX=24"]), ("m_16", ["-DDEXR_NMAX=16", "-DDEXR_MIMIC=1"]),
                       ("mc_16", ["-DDEXR_NMAX=16", "-DDEXR_MIMIC=1", "-DDEXR_MODCHOL=1"])):
         # ... its float64 instantiation (dexr_tuning.kernel_f64): one wave per SIMD, four frames per wave
         o = os.path.join(BUILD, f"dexr_wide_d_{tag}.o")
         objs.append(o)
-        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp"), BIG_HEADER] + HEADERS):
+        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp")] + HEADERS):
             jobs.append((wide_s, o, NO_SLP + defs + ["-DDEXR_WIDE_F64=1"]))
     red_s = os.path.join(CSRC, "dexr_red_inst.hip")
     for nvb in (8, 16):  # reduced-variable kernel (mimic models): Hessian of the variables in registers
         o = os.path.join(BUILD, f"dexr_red_{nvb}.o")
         objs.append(o)
-        if force or _stale(o, [red_s, os.path.join(CSRC, "dexr_red.hpp"), BIG_HEADER] + HEADERS):
+        if force or _stale(o, [red_s, os.path.join(CSRC, "dexr_red.hpp")] + HEADERS):
             jobs.append((red_s, o, NO_SLP + [f"-DDEXR_NV={nvb}"]))
     for n, f64 in ((4, 0), (8, 0), (4, 1), (8, 1)):  # small components with fleet / sequence addressing (EXT)
         o = os.path.join(BUILD, f"dexr_inst_ext_{n}_{f64}_0.o")

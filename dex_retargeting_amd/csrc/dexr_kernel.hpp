@@ -60,7 +60,7 @@ struct KernelParams {
   int32_t newton;
   int32_t max_blind;  // accepted steps below the rounding floor of F before giving up on further progress
   int32_t lds_frames, lds_terms;  // per-wave LDS rows: max frames / max terms over the model's components
-  int32_t big_nh_rows;            // dexr_big_kernel: LDS rows reserved for the Hessian (n_max (n_max + 1) / 2)
+  int32_t big_nh_rows;            // unused (always 0); kept so that the offsets of the fields below stay put
   int32_t red_nj;                 // dexr_red_kernel: joints per component the LDS axis / origin rows are sized for
   float blind_tol;                // a Newton step of a verified, undamped model shorter than this is taken without a
                                   // further evaluation of the objective and ends the solve (0: off)
@@ -91,7 +91,7 @@ struct KernelParams {
   int32_t ld;                          // row length of last / x0 / qout (>= n_opt; rows of a fleet batch are padded)
   int32_t ldf;                         // row length of fixed (>= n_fixed; = n_fixed outside fleet batches)
   // Frame sequences (SeqRetargeting.retarget semantics, seq_retarget.py:112-134): a work item is a SEQUENCE; the lane
-  // (quad) that owns it solves its T frames in order and carries the raw solution, clipped to the joint limits
+  // (or sixteen-lane row) that owns it solves its T frames in order and carries the raw solution, clipped to the joint limits
   // [lo + clip_eps, hi - clip_eps] (tables hold the optimiser's box, widened by clip_eps), as start point and
   // regularisation target of the next frame, and the DexPilot projection bits.  Frame t of sequence b reads input row
   // t * seq_stride + b and writes output row t * seq_stride + b; `last` and `state` have one row per sequence.
@@ -1134,7 +1134,9 @@ __global__ void __launch_bounds__((TIP && sizeof(real) == 4) ? DEXR_TIP_BLOCK_MA
             const bool stalled = (bool)((int)below_floor & (int)(blind >= k_stall_from) & (int)(smax > k_stall_ratio * sprev) & (int)(smax < k_stall_cap * k_tol));
             blind = below_floor ? blind + 1 : 0;
             sprev = smax;
-            // a step below tol only means convergence when the damping is not what made it small (see dexr_big.hpp)
+            // a step below tol only means convergence when the damping is not what made it small: with lambda far above the
+            // weakest curvature the model can have (the regulariser's 2 delta) such a step says nothing about the distance to
+            // the minimiser, so it shrinks lambda tenfold instead and the iteration goes on
             const real lam_ok = fmax((real)2 * k_delta, (real)10 * k_lam0);
             if ((bool)(((int)(smax < k_tol) & (int)(lam <= lam_ok)) | (int)stalled | (int)(blind >= k_max_blind))) {
               finished = true;
@@ -1385,7 +1387,9 @@ __global__ void __launch_bounds__((TIP && sizeof(real) == 4) ? DEXR_TIP_BLOCK_MA
         const bool stalled = below_floor && blind >= kp.stall_from && smax > (real)kp.stall_ratio * sprev && smax < (real)kp.stall_cap * (real)kp.tol;
         blind = below_floor ? blind + 1 : 0;
         sprev = smax;
-        // a step below tol only means convergence when the damping is not what made it small (see dexr_big.hpp)
+        // a step below tol only means convergence when the damping is not what made it small: with lambda far above the
+        // weakest curvature the model can have (the regulariser's 2 delta) such a step says nothing about the distance to the
+        // minimiser, so it shrinks lambda tenfold instead and the iteration goes on
         const real lam_ok = fmax((real)2 * delta, (real)10 * (real)kp.lam0);
         if ((smax < (real)kp.tol && lam <= lam_ok) || stalled || blind >= kp.max_blind) {
           done = true;

@@ -61,21 +61,6 @@ hipError_t launch_ext_tip_4_0_0(const KernelParams&, dim3, dim3, size_t, hipStre
 hipError_t launch_tip_4_1_0(const KernelParams&, dim3, dim3, size_t, hipStream_t);      // the same pass in float64
 hipError_t launch_ext_tip_4_1_0(const KernelParams&, dim3, dim3, size_t, hipStream_t);
 
-// large-component kernel (dexr_big.hpp): float64 kinematics + float32 Hessian in LDS
-hipError_t launch_big_16(const KernelParams&, dim3, dim3, size_t, hipStream_t);
-hipError_t launch_big_24(const KernelParams&, dim3, dim3, size_t, hipStream_t);
-hipError_t launch_big_32(const KernelParams&, dim3, dim3, size_t, hipStream_t);
-static inline launch_fn find_big_launcher(int bucket) {
-  return bucket == 16 ? launch_big_16 : bucket == 24 ? launch_big_24 : bucket == 32 ? launch_big_32 : nullptr;
-}
-
-// four-lanes-per-frame kernel for dense 9..24-joint components (dexr_quad.hpp)
-hipError_t launch_quad_16(const KernelParams&, dim3, dim3, size_t, hipStream_t);
-hipError_t launch_quad_24(const KernelParams&, dim3, dim3, size_t, hipStream_t);
-static inline launch_fn find_quad_launcher(int bucket) {
-  return bucket == 16 ? launch_quad_16 : bucket == 24 ? launch_quad_24 : nullptr;
-}
-
 // sixteen-lanes-per-frame kernel for dense 9..32-joint components without mimic joints (dexr_wide.hpp)
 typedef hipError_t (*wide_launch_fn)(const KernelParams& kp, const WideTable* wt, dim3 grid, dim3 block, size_t lds, hipStream_t st);
 hipError_t launch_wide_16(const KernelParams&, const WideTable*, dim3, dim3, size_t, hipStream_t);

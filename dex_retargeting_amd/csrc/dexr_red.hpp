@@ -3,29 +3,35 @@
 //
 // Why: with mimic joints the number of joints a component moves (Ability 10, Inspire 12, Schunk SVH 20, + 6 dummy
 // joints for position models) is two to three times the number of VARIABLES it optimises (6 / 6 / 9): the reference folds
-// the mimic columns into the source joint's column (kinematics_adaptor.py:107-113).  The joint-space kernels
-// (dexr_kernel.hpp, dexr_big.hpp) assemble and factor an n_joint x n_joint Hessian and fold afterwards -- 300 entries for
-// SVH, which pushed those models onto the spilling 24-joint register kernel + float64 polish (45 ms per 65 536 frames)
-// or the LDS kernel (23 ms).  Here the fold happens where the Jacobian column is formed:
+// the mimic columns into the source joint's column (kinematics_adaptor.py:107-113).  A joint-space kernel (dexr_kernel.hpp)
+// assembles and factors an n_joint x n_joint Hessian and folds afterwards -- 300 entries for SVH, which pushed those models
+// onto the spilling 24-joint register kernel + float64 polish (45 ms per 65 536 frames; 23 ms with that Hessian in LDS).
+// Here the fold happens where the Jacobian column is formed:
 //   * the joint loops (forward kinematics, Jacobian columns) are ROLLED: joint k is a run-time, wave-uniform index; world
 //     axes / origins live in LDS ([row][lane], conflict-free) and the tables arrive through scalar loads;
 //   * per residual term the columns of the chain joints are accumulated straight into the NV variable columns
 //     colv[var[k]] += vmul[k] * col_k, a wave-uniform switch on var[k] (registers need static indices);
 //   * the second-order (Newton) term sum_{j in fam a, k in fam b} m_j m_k f.(a_min x col_max) is accumulated in the same
 //     sweep from running per-variable axis sums A[v] = sum_{j <= k, j in fam v} m_j a_j;
-//   * value, residuals and kinematics in float64 (no polish launch needed, see dexr_big.hpp), gradient / Hessian /
-//     Cholesky in float32, persistent lanes with a per-component frame queue as in dexr_big.hpp.
+//   * value, residuals and kinematics in float64, gradient / Hessian / Cholesky in float32: the residual of a vector term
+//     is a difference of positions ~0.2 m that nearly cancels, and in float32 that rounding puts a ~1e-4 rad floor under
+//     DexPilot / position solves -- in float64 it does not, so no float64 polish launch is needed;
+//   * persistent lanes: a lane that finishes its frame stores it and takes the next one -- wave w starts with the static
+//     tile [64 w, 64 w + 64), frames from kp.q0 on are handed out 64 at a time by the per-component queue.
 // The instruction stream is a few KB per stage (one copy of each rolled loop) instead of the 100+ KB of the unrolled
 // kernels.  NV buckets: 8 and 16.
 #pragma once
 
-#include "dexr_big.hpp"  // sincos_f64, BIG_NSLOT
+#include "dexr_kernel.hpp"
+#include "dexr_math.hpp"  // sincos_f64
 
 #ifndef DEXR_RED_MINW8
 #define DEXR_RED_MINW8 1  // waves per SIMD the NV = 8 instantiation must leave room for (2: 120 B of scratch per lane)
 #endif
 
 namespace dexr {
+
+constexpr int RED_NSLOT = 2;  // saved transforms kept in registers (float64); select_kernels admits no deeper forks
 
 // blockDim.x = 64 (one wave per block); dynamic LDS = 64 * (4 * 6 * red_nj + 8 * 3 * lds_frames) bytes:
 // float32 axes + origins of red_nj joints, float64 positions of lds_frames frames, [row][lane].
@@ -194,9 +200,9 @@ __global__ void __launch_bounds__(64, (NV <= 8 ? DEXR_RED_MINW8 : 1)) dexr_red_k
   auto fk = [&]() {
     bool c0_set = false;
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
-    double sR[BIG_NSLOT][9], sp[BIG_NSLOT][3];
+    double sR[RED_NSLOT][9], sp[RED_NSLOT][3];
 #pragma unroll
-    for (int s = 0; s < BIG_NSLOT; ++s) {
+    for (int s = 0; s < RED_NSLOT; ++s) {
 #pragma unroll
       for (int i = 0; i < 9; ++i) sR[s][i] = 0;
 #pragma unroll
@@ -210,7 +216,7 @@ __global__ void __launch_bounds__(64, (NV <= 8 ? DEXR_RED_MINW8 : 1)) dexr_red_k
         p[0] = 0; p[1] = 0; p[2] = 0;
       } else if (rs >= 0) {
 #pragma unroll
-        for (int s = 0; s < BIG_NSLOT; ++s)
+        for (int s = 0; s < RED_NSLOT; ++s)
           if (rs == s) {
 #pragma unroll
             for (int i = 0; i < 9; ++i) R[i] = sR[s][i];
@@ -264,7 +270,7 @@ __global__ void __launch_bounds__(64, (NV <= 8 ? DEXR_RED_MINW8 : 1)) dexr_red_k
       const int sv = tb.save[k];
       if (sv >= 0) {
 #pragma unroll
-        for (int s = 0; s < BIG_NSLOT; ++s)
+        for (int s = 0; s < RED_NSLOT; ++s)
           if (sv == s) {
 #pragma unroll
             for (int i = 0; i < 9; ++i) sR[s][i] = R[i];
@@ -493,7 +499,10 @@ __global__ void __launch_bounds__(64, (NV <= 8 ? DEXR_RED_MINW8 : 1)) dexr_red_k
     return ok;
   };
 
-  // ---- projected Levenberg-Marquardt / Newton: the loop of dexr_big.hpp ----------------------------------------------
+  // ---- projected Levenberg-Marquardt / Newton -----------------------------------------------------------------------
+  // One pass of the loop = forward kinematics + fused value / gradient / Hessian at the point under evaluation (x itself,
+  // or the pending trial point) + one factorisation.  A rejected trial costs one extra pass (the model at the accepted
+  // point is rebuilt).
   const uint32_t varmask = nv >= 32 ? 0xffffffffu : ((1u << nv) - 1u);
   float lam = kp.lam0, nu = 2.f, sprev = 1e30f;
   bool done = true, pending = false;

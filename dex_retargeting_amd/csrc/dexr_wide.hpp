@@ -1,7 +1,7 @@
 // dexr_wide.hpp -- solve kernel for LARGE DENSE components (9..32 joints): SIXTEEN LANES PER FRAME.
 //
-// Why: a launch of the four-lanes-per-frame kernel (dexr_quad.hpp) over 65 536 Shadow-DexPilot frames is bound by its
-// SLOWEST frame, not by its throughput -- a frame that needs 44 iterations is a serial chain of ~56 wave passes of
+// Why: with four lanes per frame (the layout this kernel replaced), a launch over 65 536 Shadow-DexPilot frames is bound by
+// its SLOWEST frame, not by its throughput -- a frame that needs 44 iterations is a serial chain of ~56 wave passes of
 // ~37 000 instructions each (0.12 ms per pass, 6.5 ms per launch, while the mean frame needs 5 iterations; see
 // DESIGN.md section 4).  A pass therefore has to become short.  Here a frame is spread over a 16-lane DPP row, a wave
 // holds four frames, and every stage of a pass is parallel over the 16 lanes:
@@ -19,14 +19,17 @@
 //   * Cholesky on that grid: the pivot travels by a DPP quad broadcast + a stride-4 DPP sum, the pivot column by one DPP
 //     quad broadcast (row side) and one ds_bpermute (column side) per local row; the right-hand side rides along as an
 //     extra matrix row (forward substitution for free); backward substitution with stride-4 DPP sums.
-// The accepted point's Hessian stays in registers (its gradient in LDS), so a REJECTED step costs no extra pass (the
-// quad kernel re-assembles): every pass evaluates a new trial point.
+// The accepted point's Hessian stays in registers (its gradient in LDS), so a REJECTED step costs no extra pass (no
+// re-assembly at the accepted point): every pass evaluates a new trial point.
 // MIMIC instantiation: the grid is that of the <= 16 optimised VARIABLES; lane v forms and sums the columns of the <= 3
 // joints that move with variable v, the second-order term comes from a host-built list of (joint, revolute ancestor)
 // pairs bucketed by the lane that owns the target entry.  MODCHOL (with MIMIC): the damping rules of dexr_red.hpp.
 // Budgets: 256 VGPRs and 15-20 KB of LDS per wave = two waves per SIMD; the 16-row joint grid is built for three (168
 // VGPRs, 13 KB).  Everything that is read once or twice per pass lives in LDS or the tables, not in registers.
-// Damping / termination rules are those of dexr_quad.hpp.
+// Damping / termination (projected Levenberg-Marquardt / Newton; the reasons sit at the accept / reject code of the kernel):
+// an accepted step shrinks lambda by Nielsen's rule (or by lam_fastdec after a well-predicted step), a rejected one raises it
+// to at least lam_jump x the curvature along the failed step (MODCHOL: mean diag H); a step below tol ends the solve only
+// while lambda is near its floor.
 // SPRINT instantiations (round 5): one frame per wave for small batches and short sequences -- the four rows share the frame's
 // term loop and each tries its own damping value per pass (see the comment at the kernel).
 // F64 instantiations (dexr_tuning.kernel_f64 = DEXR_KERNEL_WIDE; 16- / 24-row joint grids and the variable grid): the same
@@ -40,7 +43,8 @@
 // rounding floor of F is the float64 register kernel's (16 eps max(|F|, 2e-3)), not floor_scale x |F|.
 #pragma once
 
-#include "dexr_big.hpp"  // sincos_f64
+#include "dexr_kernel.hpp"
+#include "dexr_math.hpp"  // sincos_f64
 
 namespace dexr {
 
@@ -493,7 +497,10 @@ __global__ void __launch_bounds__(256, F64 ? 1 : DEXR_WIDE_MINW) dexr_wide_kerne
       for (int i = 0; i < 3; ++i) rv[i] = r[i];
     }
   };
-  auto xl = [&](ColdParams& kp, int s, const float* lastp, int t_seq) -> wreal {  // regularisation target of own joint s (see dexr_quad.hpp)
+  auto xl = [&](ColdParams& kp, int s, const float* lastp, int t_seq) -> wreal {
+    // regularisation target of own joint s = start point of the frame: `last` of the item, or -- sequence mode, frame t > 0 --
+    // the previous frame's raw solution, which this row has just stored to qout (read coherently, bypassing the vector L1);
+    // clipped to the joint limits in sequence mode (seq_retarget.py:118-120)
     wreal v;
     if (seq && t_seq > 0)
       v = __hip_atomic_load(const_cast<float*>(lastp) + tb.api[jsel(s)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1572,7 +1579,11 @@ __global__ void __launch_bounds__(256, F64 ? 1 : DEXR_WIDE_MINW) dexr_wide_kerne
           const bool stalled = (bool)((int)below_floor & (int)(blind >= kp.stall_from) & (int)(smax > kp.stall_ratio * sprev) & (int)(smax < kp.stall_cap * kp.tol));
           blind = below_floor ? blind + 1 : 0;
           sprev = smax;
-          const wreal lam_ok = wmax(2.f * delta, (wreal)(10.f * kp.lam0));  // see dexr_quad.hpp
+          // A step below tol only means convergence when the damping is not what made it small: with lambda far above the
+          // weakest curvature the model can have (the regulariser's 2 delta) a step of 1e-8 says nothing about the distance to
+          // the minimiser (mimic DexPilot models: frames stopped 1e-4..8e-4 rad short after a rejected step had raised lambda).
+          // Such a step shrinks lambda tenfold instead and the iteration goes on.
+          const wreal lam_ok = wmax(2.f * delta, (wreal)(10.f * kp.lam0));
           if ((bool)(((int)(smax < kp.tol) & ((int)(lam <= lam_ok) | (int)sprint_floor)) | (int)stalled | (int)(blind >= kp.max_blind))) {
             done = true;
             status = ST_CONVERGED;
@@ -1583,6 +1594,8 @@ __global__ void __launch_bounds__(256, F64 ? 1 : DEXR_WIDE_MINW) dexr_wide_kerne
           WDIAG(++d_nrej; if (!ok) ++d_nfail;)
           ++nrej;
           lam = wmax(lam, (wreal)1e-6f) * nu;
+          // damping jump: at least lam_jump x the curvature of the damped model along the step that just failed (Rayleigh
+          // quotient -g.d / d.d; MODCHOL: mean diag H)
           if (kp.lam_jump > 0) lam = wmax(lam, kp.lam_jump * (MODCHOL ? hdmean : keff));
           nu *= 2.f;
 #pragma unroll
@@ -1591,6 +1604,9 @@ __global__ void __launch_bounds__(256, F64 ? 1 : DEXR_WIDE_MINW) dexr_wide_kerne
             done = true;
             status = finite ? ST_CONVERGED : ST_FALLBACK;
           }
+          // a step shorter than tol that does not decrease F: the decrease along the (damped) descent direction is below the
+          // resolution of F -- converged at the rounding floor (and no livelock between tiny accepted steps that shrink lambda
+          // and rounding-level rejections that raise it again)
           if ((bool)((int)(ok || MODCHOL) & (int)finite & (int)(smax < kp.tol))) {
             done = true;
             status = ST_CONVERGED;
@@ -1725,7 +1741,8 @@ __global__ void __launch_bounds__(256, F64 ? 1 : DEXR_WIDE_MINW) dexr_wide_kerne
       }
       smax = row_max(sl);
       pending = true;
-      // (see dexr_quad.hpp: verified undamped model, tiny Newton step; beyond 10 tol only on the quadratic tail of the
+      // verified, undamped model and a Newton step below blind_tol: the step is the converged answer to well below the tolerance
+      // -- take it and stop instead of spending one more pass on confirming it (beyond 10 tol only on the quadratic tail of the
       // iteration -- the step must be at most a tenth of the previous accepted one, as in the small-component kernel)
       bool last_step = (bool)((int)okf & (int)(smax < kp.blind_tol) & (int)(lam_row <= kp.lam0) & ((int)(smax < 10.f * kp.tol) | (int)(smax < 0.1f * sprev)));
       // ... and no variable held at a bound may be about to come off it (round 6).  The step is judged by the model of the FREE

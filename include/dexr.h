@@ -52,8 +52,8 @@ typedef struct dexr_solve_options {
                          -1 auto (default: up to 24 for position / DexPilot models, whose float32 rounding floor sits
                          near 1e-4 rad; 0 for vector models), 0 off, n > 0 at most n iterations           */
   int32_t strict;     /* float64 polish after the mixed-precision kernels (float64 kinematics and value, float32
-                         gradient and Hessian) that serve large components.  0 (default): only after the quad / LDS
-                         kernels on models with mimic joints; 1: after every mixed-precision kernel; -1: never.      */
+                         gradient and Hessian: reduced-variable and sixteen-lane) that serve large components.
+                         1: after every such launch; 0 (default) and -1: never (the two values act the same).       */
 } dexr_solve_options;
 
 /* Per-model launch / damping parameters.  These are the values the launcher derives from the model's shape and from
@@ -63,8 +63,7 @@ typedef struct dexr_solve_options {
  * fields, hand them back with dexr_model_set_tuning() (not thread-safe against launches in flight on that handle). */
 #define DEXR_KERNEL_AUTO (-1)
 #define DEXR_KERNEL_REGISTER 0 /* one lane per (frame, component), Hessian in registers (dexr_kernel.hpp)            */
-#define DEXR_KERNEL_QUAD 1     /* four lanes per frame, distributed Hessian rows (dexr_quad.hpp)                      */
-#define DEXR_KERNEL_LDS 2      /* one lane per frame, Hessian in LDS (dexr_big.hpp)                                   */
+/* 1 and 2 are reserved (retired kernel families): never reported, refused by dexr_model_set_tuning               */
 #define DEXR_KERNEL_REDUCED 3  /* one lane per frame, Hessian of the optimised VARIABLES (mimic joints folded while the
                                   Jacobian is formed) in registers, kinematics in LDS (dexr_red.hpp)                   */
 #define DEXR_KERNEL_WIDE 4     /* sixteen lanes per frame: chain-parallel kinematics, 4 x 4 lane grid for the Hessian and
@@ -82,7 +81,7 @@ typedef struct dexr_tuning {
   int32_t persist_occ;  /* small components: resident waves per SIMD in queue mode (0: derived from the kernel)  */
   int32_t persist_from; /* small components: queue mode from this many 64-frame tiles per resident wave (8)       */
   int32_t qchunk;       /* frames a wave takes from the queue per atomic (256)                                    */
-  int32_t resident_waves; /* quad / LDS kernels: resident waves (0: one per SIMD resp. what the LDS allows)       */
+  int32_t resident_waves; /* reduced-variable / sixteen-lane kernels: resident waves (0: what registers and LDS allow) */
   int32_t max_blind;    /* accepted steps below the rounding floor of F before the solve stops (8)                */
   int32_t stall_from;   /* see dexr_kernel.hpp "stalled"                                                          */
   float stall_ratio, stall_cap;

@@ -270,8 +270,9 @@ def test_ragged_batches(B):
 @pytest.mark.parametrize("rel", ["teleop/shadow_hand_right_dexpilot.yml", "offline/leap_hand_right.yml",
                                  "offline/ability_hand_right.yml", "teleop/allegro_hand_right_dexpilot.yml"])
 def test_ragged_batches_large_component_kernels(rel):
-    """Tile edges of the quad kernel (16 frames per wave), the LDS kernel and the register kernel (64): any prefix of
-    a batch gives the same answers as the whole batch, down to single frames and the empty batch."""
+    """Tile edges of the sixteen-lane kernel (four frames per wave, one per wave for small batches) and the
+    reduced-variable kernel (64 frames per wave): any prefix of a batch gives the same answers as the whole batch, down
+    to single frames and the empty batch."""
     seq, prob = build(rel)
     model = seq.optimizer.device_model()
     n = 200
@@ -313,9 +314,9 @@ def test_full_size_batch_properties():
 @pytest.mark.parametrize("rel", ["teleop/shadow_hand_right_dexpilot.yml", "offline/leap_hand_right.yml",
                                  "offline/inspire_hand_right.yml"])
 def test_full_size_batches_of_the_persistent_kernels(rel):
-    """BASELINE.json configs [2] and [3] at 65 536 frames (quad kernel: persistent quads refilled from a frame queue)
-    and a mimic position model (LDS kernel, persistent lanes): which quad / lane solves which frame depends on timing,
-    the answers must not -- bitwise determinism, permutation equivariance, sub-batch consistency (a 5 000-frame launch
+    """BASELINE.json configs [2] and [3] at 65 536 frames (sixteen-lane kernel: persistent rows refilled from a frame
+    queue) and a mimic position model (reduced-variable kernel, persistent lanes): which row / lane solves which frame
+    depends on timing, the answers must not -- bitwise determinism, permutation equivariance, sub-batch consistency (a 5 000-frame launch
     takes the static-tile path only), bounds, DexPilot state, and agreement with the float64 kernel on a subset."""
     seq, prob = build(rel)
     model = seq.optimizer.device_model()
@@ -968,10 +969,11 @@ def test_lane_plan_covers_the_kinematic_tree(rel):
 
 @pytest.mark.parametrize("rel", ["teleop/shadow_hand_right_dexpilot.yml", "offline/leap_hand_left.yml",
                                  "teleop/allegro_hand_right_dexpilot.yml"])
-def test_sixteen_lane_and_four_lane_kernels_agree(rel):
-    """Same damping rules, different work distribution and summation order: the two kernel families return the same
-    minimiser (to float32 solve accuracy) on all but the few frames where rounding sends them to different basins, and
-    the sixteen-lane kernel is deterministic run to run."""
+def test_sixteen_lane_and_register_kernels_agree(rel):
+    """Independent implementations (work distribution, summation order, damping rules; the register kernel adds its
+    float64 polish on these models): the two kernel families return the same minimiser (to float32 solve accuracy) on
+    all but the few frames where rounding sends them to different basins, and the sixteen-lane kernel is deterministic
+    run to run."""
     seq, prob = build(rel)
     model = seq.optimizer.device_model()
     B = 4096
@@ -990,8 +992,8 @@ def test_sixteen_lane_and_four_lane_kernels_agree(rel):
     assert model.kernel()[0] == _lib.KERNEL_WIDE
     qw2, _ = run(_lib.KERNEL_WIDE, kp[1:], last)
     assert np.array_equal(qw, qw2)
-    qq, iq = run(_lib.KERNEL_QUAD, kp[1:], last)
-    assert model.kernel()[0] == _lib.KERNEL_QUAD
+    qq, iq = run(_lib.KERNEL_REGISTER, kp[1:], last)
+    assert model.kernel()[0] == _lib.KERNEL_REGISTER
     model.tune(kernel=_lib.KERNEL_AUTO)
     assert (iw["status"] == 0).all() and (iq["status"] == 0).all()
     dq = np.abs(qw.astype(np.float64) - qq).max(1)
@@ -1332,7 +1334,7 @@ def test_launches_on_two_streams_do_not_interfere(rel):
 def test_tuning_rejects_unknown_values():
     seq, _ = build("teleop/shadow_hand_right_dexpilot.yml")
     model = seq.optimizer.device_model()
-    for bad in (dict(kernel=7), dict(pivot_rule=3), dict(longest_first=3), dict(lam_jump=-1.0), dict(chain=3)):
+    for bad in (dict(kernel=1), dict(kernel=2), dict(kernel=7), dict(pivot_rule=3), dict(longest_first=3), dict(lam_jump=-1.0), dict(chain=3)):
         with pytest.raises(_lib.DexrError):
             model.tune(**bad)
     model.tune(kernel=_lib.KERNEL_AUTO)
@@ -1478,25 +1480,25 @@ def test_native_allgather_world_size_one_and_graph_capture():
     comm.close()
 
 
-def test_damping_default_follows_the_dispatched_kernel_family():
+def test_damping_default_follows_the_register_and_sixteen_lane_families():
     """dexr_tuning.lam_jump means different things per family (curvature along the failed step vs mean diag H): after
     tune(kernel=...) the handle reports -- and launches with -- the NEW family's default unless the caller set one."""
     seq = RetargetingConfig.load_from_file(os.path.join(cases.CONFIG_DIR, "teleop/shadow_hand_right_dexpilot.yml")).build()
     model = seq.optimizer.device_model()
     assert model.kernel()[0] == _lib.KERNEL_WIDE and abs(model.get_tuning().lam_jump - 1.0) < 1e-7
-    model.tune(kernel=_lib.KERNEL_LDS)
-    assert model.kernel()[0] == _lib.KERNEL_LDS and abs(model.get_tuning().lam_jump - 0.3) < 1e-7
-    model.tune(kernel=_lib.KERNEL_QUAD)
+    model.tune(kernel=_lib.KERNEL_REGISTER)
+    assert model.kernel()[0] == _lib.KERNEL_REGISTER and abs(model.get_tuning().lam_jump - 0.3) < 1e-7
+    model.tune(kernel=_lib.KERNEL_WIDE)
     assert abs(model.get_tuning().lam_jump - 1.0) < 1e-7
     # ADVICE r3: a struct read BEFORE a family change and handed back later must not pin the old family's default ...
-    stale = model.get_tuning()                      # quad family: 1.0, no override bit
-    model.tune(kernel=_lib.KERNEL_LDS)              # LDS family: 0.3
-    stale.kernel = _lib.KERNEL_LDS
+    stale = model.get_tuning()                      # sixteen-lane family: 1.0, no override bit
+    model.tune(kernel=_lib.KERNEL_REGISTER)         # register family, bucket 24: 0.3
+    stale.kernel = _lib.KERNEL_REGISTER
     _lib.check(_lib.load().dexr_model_set_tuning(model._h, _lib.C.byref(stale)))
     assert abs(model.get_tuning().lam_jump - 0.3) < 1e-7 and model.get_tuning().user_mask == 0
-    model.tune(kernel=_lib.KERNEL_QUAD)
+    model.tune(kernel=_lib.KERNEL_WIDE)
     model.tune(lam_jump=0.5)  # an explicit value survives family changes
-    model.tune(kernel=_lib.KERNEL_LDS)
+    model.tune(kernel=_lib.KERNEL_REGISTER)
     assert abs(model.get_tuning().lam_jump - 0.5) < 1e-7 and model.get_tuning().user_mask == _lib.TUNE_LAM_JUMP
     model.tune(lam_jump=None)  # ... and an override can be dropped again: back to the family default
     assert abs(model.get_tuning().lam_jump - 0.3) < 1e-7 and model.get_tuning().user_mask == 0

@@ -67,7 +67,7 @@ def test_tuning_struct_matches_header_and_library_reads_no_environment():
 
     assert ctypes.sizeof(_lib.Tuning) == 4 * len(fields)
     # developer knobs are fields of dexr_tuning / dexr_solve_options, not environment variables
-    for src in ("dexr_api.hip", "dexr_kernel.hpp", "dexr_quad.hpp", "dexr_big.hpp", "dexr_prep.hip"):
+    for src in ("dexr_api.hip", "dexr_kernel.hpp", "dexr_wide.hpp", "dexr_red.hpp", "dexr_prep.hip"):
         path = os.path.join(REPO, "dex_retargeting_amd", "csrc", src)
         if os.path.exists(path):
             assert "getenv" not in open(path).read(), src

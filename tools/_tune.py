@@ -8,13 +8,12 @@ from dex_retargeting_amd import _lib
 _TUNE = {"persist_from": int, "persist_occ": int, "qchunk": int, "resident_waves": int, "max_blind": int,
          "stall_from": int, "stall_ratio": float, "stall_cap": float, "lam_jump": float, "lam_fastdec": float, "lam_recover": float,
          "floor_scale": float, "step_cap": float, "blind_tol_scale": float, "chain": int, "pivot_rule": int, "longest_first": int}
-_KERNEL = {"auto": _lib.KERNEL_AUTO, "register": _lib.KERNEL_REGISTER, "quad": _lib.KERNEL_QUAD, "lds": _lib.KERNEL_LDS,
-           "reduced": _lib.KERNEL_REDUCED, "wide": _lib.KERNEL_WIDE}
+_KERNEL = {"auto": _lib.KERNEL_AUTO, "register": _lib.KERNEL_REGISTER, "reduced": _lib.KERNEL_REDUCED, "wide": _lib.KERNEL_WIDE}
 _OPTS = {"max_iter": int, "tol": float, "lambda0": float, "newton": int, "polish": int, "strict": int}
 
 
 def apply(model, knobs: dict):
-    """knobs: {'kernel': 'quad', 'persist_from': 0, 'newton': 0, ...} -> (Tuning, SolveOptions or None)."""
+    """knobs: {'kernel': 'wide', 'persist_from': 0, 'newton': 0, ...} -> (Tuning, SolveOptions or None)."""
     tk = {k: _TUNE[k](v) for k, v in knobs.items() if k in _TUNE}
     if "kernel" in knobs:
         tk["kernel"] = _KERNEL[knobs["kernel"]]

@@ -259,7 +259,7 @@ def kernel_lm(cm, *, lam0=1e-4, tol=2e-6, max_iter=64, step_cap=0.3, lam_jump=1.
         rej = live & ~accept & ~take_last
         lam_rej = np.maximum(lam, 1e-6) * nu
         if lam_jump > 0:
-            if jump_mode == "keff":  # quad kernel: curvature of the damped model along the failed step
+            if jump_mode == "keff":  # sixteen-lane kernel: curvature of the damped model along the failed step
                 lam_rej = np.maximum(lam_rej, lam_jump * gd / np.maximum(dd, 1e-30))
             else:
                 hd = np.where(vm, np.einsum("btii->bti", Hs), 0.0).sum(-1) / vm.sum(-1)

@@ -5,7 +5,7 @@
                -> gpurun_out/head_slowq_<name>.npz: keypoints, start points, DexPilot bits, per-frame iteration counts
     (here)     python tools/lm_replay.py <config.yml> [frames] [predictors]
 
-Prints the GPU's iteration histogram next to the emulation's (same inputs, the quad / sixteen-lane kernels' rules: Rayleigh
+Prints the GPU's iteration histogram next to the emulation's (same inputs, the sixteen-lane kernel's rules: Rayleigh
 quotient damping jump, plain Cholesky), their per-frame agreement, a few rule variants, and -- with a third argument --
 how well quantities known at the start point predict the slow frames (longest-first scheduling).
 The emulation only reproduces the GPU when it uses the kernels' float32 joint box: a bound that differs in the 8th

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GPU: launch one config's solve kernel a few times on the bench workload (for rocprofv3 to wrap).
 
-    python tools/prof_config.py <config.yml> [kernel family: auto|register|quad|lds|reduced] [batch] [launches]
+    python tools/prof_config.py <config.yml> [kernel family: auto|register|reduced|wide] [batch] [launches]
 """
 import os
 import sys
@@ -26,8 +26,7 @@ RetargetingConfig.set_default_urdf_dir(str(DEFAULT_URDF_DIR))
 seq = RetargetingConfig.load_from_file(os.path.join(bench_data.CONFIG_DIR, rel)).build()
 model = seq.optimizer.device_model()
 if kernel != "auto":
-    model.tune(kernel={"register": _lib.KERNEL_REGISTER, "quad": _lib.KERNEL_QUAD, "lds": _lib.KERNEL_LDS,
-                       "reduced": _lib.KERNEL_REDUCED, "wide": _lib.KERNEL_WIDE}[kernel])
+    model.tune(kernel={"register": _lib.KERNEL_REGISTER, "reduced": _lib.KERNEL_REDUCED, "wide": _lib.KERNEL_WIDE}[kernel])
 if os.environ.get("DEXR_TOOL_KNOBS"):  # e.g. DEXR_TOOL_KNOBS="pivot_rule=1,lam_jump=0.3" (tools only; the library reads no environment)
     import _tune
 
