@@ -34,13 +34,13 @@ NO_SLP = ["-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "
 # summaries, profiles/pmc_<workload>.json: bench.py attaches their counters to a line only while this hash is unchanged).
 _COMMON_SOURCES = ["dexr_api.hip", "dexr_launch.hpp", "../../include/dexr.h", "../../include/dexr_tables.h"]
 KERNEL_SOURCES = {
-    "allegro_vector": ["dexr_kernel.hpp", "dexr_tip.hpp", "dexr_math.hpp", "dexr_inst.hip"],
+    "allegro_vector": ["dexr_kernel.hpp", "dexr_tip.hpp", "dexr_tip_solve.hpp", "dexr_tip_inst.hip", "dexr_math.hpp", "dexr_inst.hip"],
     "shadow_dexpilot": ["dexr_wide.hpp", "dexr_wide_inst.hip", "dexr_math.hpp"],
     "leap_position": ["dexr_wide.hpp", "dexr_wide_inst.hip", "dexr_math.hpp"],
     # sub-records of the default line (bench.py --probe): the float64 / cold-start launches of the headline config, the general
     # kernel; "mixed_fleet" is absent on purpose: four robots = every kernel family, i.e. all sources (the fallback)
     "allegro_vector_f64": ["dexr_kernel.hpp", "dexr_tip.hpp", "dexr_math.hpp", "dexr_inst.hip"],
-    "allegro_vector_cold": ["dexr_kernel.hpp", "dexr_tip.hpp", "dexr_math.hpp", "dexr_inst.hip"],
+    "allegro_vector_cold": ["dexr_kernel.hpp", "dexr_tip.hpp", "dexr_tip_solve.hpp", "dexr_tip_inst.hip", "dexr_math.hpp", "dexr_inst.hip"],
     "general_kernel": ["dexr_gen.hpp", "dexr_gen_inst.hip", "dexr_kernel.hpp", "dexr_math.hpp"],
 }
 
@@ -167,6 +167,10 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
             objs.append(o)
             if force or _stale(o, [inst_s] + HEADERS):
                 jobs.append((inst_s, o, NO_SLP + ["-DDEXR_NMAX=4", f"-DDEXR_F64={f64}", "-DDEXR_MODE=0", "-DDEXR_CHAIN=1", "-DDEXR_TIP=1"] + defs))
+    tip32_s, tip32_o = os.path.join(CSRC, "dexr_tip_inst.hip"), os.path.join(BUILD, "dexr_tip32.o")
+    objs.append(tip32_o)  # the float32 tip solve as a kernel of its own (dexr_tip_solve.hpp): plain tile launches
+    if force or _stale(tip32_o, [tip32_s, os.path.join(CSRC, "dexr_tip_solve.hpp")] + HEADERS):
+        jobs.append((tip32_s, tip32_o, NO_SLP))
     for n in CHAIN_BUCKETS:  # serial-chain specialisation, float32 solve only
         o = os.path.join(BUILD, f"dexr_inst_chain_{n}_0_0.o")
         objs.append(o)

@@ -41,6 +41,7 @@ _TUNE_BITS = {"lam_jump": TUNE_LAM_JUMP, "lam_fastdec": TUNE_LAM_FASTDEC}
 
 
 KERNEL_AUTO, KERNEL_REGISTER, KERNEL_REDUCED, KERNEL_WIDE, KERNEL_GENERAL = -1, 0, 3, 4, 5  # (1 and 2: retired families)
+KERNEL_REGISTER_CHAIN = 6  # KERNEL_REGISTER without the dedicated tip solve kernel (dexr.h)
 
 EXPORTS = ["dexr_last_error", "dexr_version", "dexr_device_count", "dexr_default_options", "dexr_model_create",
            "dexr_model_destroy", "dexr_model_info", "dexr_model_get_tuning", "dexr_model_set_tuning", "dexr_model_kernel",

@@ -671,6 +671,14 @@ int launch(const dexr_model* m, int mode, int f64, dexr::KernelParams kp, hipStr
   const int64_t blocks = (waves + wpb - 1) / wpb;
   if (blocks > 0x7fffffffLL) return fail(DEXR_ERR_INVALID, "batch too large for one launch");
   dexr::launch_fn fn = dexr::find_launcher(m->bucket, f64, mode, m->chain, ext, m->tip);
+#if !defined(DEXR_SMALL_PROF) && !defined(DEXR_WAVE_TRACE)  // (the profiling hooks live in dexr_kernel)
+  // A plain tile launch of the float32 tip kernel -- every lane gets its one frame on entry; no queue, no sequence, no fleet
+  // addressing, no objective values, no float64 hooks -- runs dexr_tip32_kernel (dexr_tip_solve.hpp): the same pass without
+  // the persistent-lane loop's bookkeeping, bitwise the same answers.  dexr_tuning.kernel = DEXR_KERNEL_REGISTER_CHAIN keeps
+  // dexr_kernel.
+  if (tip_kernel && !f64 && !ext && kp.qchunk == 0 && kp.T == 0 && !kp.fval && !kp.x0 && !kp.qout64 && m->tune.kernel != DEXR_KERNEL_REGISTER_CHAIN)
+    fn = dexr::launch_tip32;
+#endif
   if (!fn) return fail(DEXR_ERR_UNSUPPORTED, "no kernel for bucket %d / f64=%d / mode=%d", m->bucket, f64, mode);
 #ifdef DEXR_SMALL_PROF
   static double* sprof = nullptr;  // profiling build only: stage cycles of wave 0 (dexr_kernel.hpp SPROF_*)
@@ -1179,7 +1187,8 @@ int dexr_model_set_tuning(dexr_model* m, const dexr_tuning* tuning) {
   dexr_tuning t = m->tune;  // fields beyond the caller's (older, shorter) struct keep their values
   std::memcpy(&t, tuning, tuning->struct_size);
   t.struct_size = (uint32_t)sizeof(dexr_tuning);
-  if (t.kernel != DEXR_KERNEL_AUTO && t.kernel != DEXR_KERNEL_REGISTER && t.kernel != DEXR_KERNEL_REDUCED && t.kernel != DEXR_KERNEL_WIDE)
+  if (t.kernel != DEXR_KERNEL_AUTO && t.kernel != DEXR_KERNEL_REGISTER && t.kernel != DEXR_KERNEL_REDUCED && t.kernel != DEXR_KERNEL_WIDE &&
+      t.kernel != DEXR_KERNEL_REGISTER_CHAIN)
     return fail(DEXR_ERR_INVALID, "unknown kernel family %d", t.kernel);
   if (t.pivot_rule < -1 || t.pivot_rule > 1) return fail(DEXR_ERR_INVALID, "unknown pivot rule %d", t.pivot_rule);
   if (t.chain < 0 || t.chain > 2) return fail(DEXR_ERR_INVALID, "chain must be 0 (never), 1 (serial-chain kernel + tip pass) or 2 (serial-chain kernel)");

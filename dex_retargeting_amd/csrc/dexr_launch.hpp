@@ -60,6 +60,8 @@ hipError_t launch_tip_4_0_0(const KernelParams&, dim3, dim3, size_t, hipStream_t
 hipError_t launch_ext_tip_4_0_0(const KernelParams&, dim3, dim3, size_t, hipStream_t);
 hipError_t launch_tip_4_1_0(const KernelParams&, dim3, dim3, size_t, hipStream_t);      // the same pass in float64
 hipError_t launch_ext_tip_4_1_0(const KernelParams&, dim3, dim3, size_t, hipStream_t);
+// the float32 tip solve as a kernel of its own (dexr_tip_solve.hpp): plain tile launches only, see dexr_api.hip launch()
+hipError_t launch_tip32(const KernelParams&, dim3, dim3, size_t, hipStream_t);
 
 // sixteen-lanes-per-frame kernel for dense 9..32-joint components without mimic joints (dexr_wide.hpp)
 typedef hipError_t (*wide_launch_fn)(const KernelParams& kp, const WideTable* wt, dim3 grid, dim3 block, size_t lds, hipStream_t st);

@@ -1,0 +1,326 @@
+// dexr_tip_solve.hpp -- dexr_tip32_kernel: the float32 solve of tip models (dexr_tip.hpp) as a kernel of its own.
+//
+// dexr_kernel<4, float, MODE_SOLVE, CHAIN, EXT, TIP> runs the tip pass inside the generic persistent-lane loop of the small
+// components: every pass of every wave goes through the hand-out of frames to idle lanes, the `fresh` start-point case, the
+// free-variable masks of models with fixed / mimic joints, and carries the queue, sequence mode, the float64 hooks and the
+// objective-value output as live branches and live scalar registers.  A plain tile launch of a tip model -- the headline: every
+// lane gets its one frame before the first pass and never another -- needs none of it.  This kernel is that launch written
+// straight:
+//   prologue  table pin, the lane's frame (same loads, same LDS layout as dexr_kernel), clamp to the box, evaluation of the
+//             start point (dexr_kernel's pass 0), whose model is adopted;
+//   loop      (a) damped 4 x 4 step from the kept model, (b) tip_eval at the trial point unless every live lane takes its
+//             blind last step, (c) accept / reject / damping / termination, (d) finished lanes store and drop out;
+//             the wave leaves when no lane holds a frame.
+// Every floating-point operation the answer depends on is the one dexr_kernel does, on the same operands in the same order
+// (steps (2)-(5) of its loop with optmask = all four joints, has && !fresh = has); qpos, status and iters are bitwise
+// those of dexr_kernel (tests/test_gpu_tip32_kernel.py).  Calls that need anything else -- queue mode, sequences, fleet
+// addressing, fval, float64 -- keep dexr_kernel (dexr_api.hip launch()).
+#pragma once
+#include "dexr_kernel.hpp"
+
+namespace dexr {
+
+// In-place Cholesky of the damped 4 x 4 model (lower triangle, hidx order) + solve H d = -g: LaneSolver::chol_solve<true>
+// (modified Cholesky: a pivot that is not positive is reflected, max(|pivot|, pivot_floor)), operation for operation.
+// Returns false where a pivot had to be modified.
+static __device__ __forceinline__ bool tip32_chol(float (&H)[10], const float (&g)[4], float (&d)[4], float pivot_floor) {
+  using RT = RealTraits<float, true>;
+  constexpr auto hidx = [](int r, int c) constexpr { return r * (r + 1) / 2 + c; };
+  bool ok = true;
+  float inv[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float dj = H[hidx(j, j)];
+#pragma unroll
+    for (int k = 0; k < j; ++k) dj -= H[hidx(j, k)] * H[hidx(j, k)];
+    if (!(dj > 1e-6f * pivot_floor)) {
+      ok = false;
+      dj = fmax(fabs(dj), pivot_floor);
+    }
+    const float iv = RT::rsqrt(dj);
+    inv[j] = iv;
+    H[hidx(j, j)] = dj * iv;
+#pragma unroll
+    for (int i = j + 1; i < 4; ++i) {
+      float s = H[hidx(i, j)];
+#pragma unroll
+      for (int k = 0; k < j; ++k) s -= H[hidx(i, k)] * H[hidx(j, k)];
+      H[hidx(i, j)] = s * iv;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {  // forward: L y = -g
+    float s = -g[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) s -= H[hidx(i, k)] * d[k];
+    d[i] = s * inv[i];
+  }
+#pragma unroll
+  for (int i = 3; i >= 0; --i) {  // backward: L^T d = y
+    float s = d[i];
+#pragma unroll
+    for (int k = i + 1; k < 4; ++k) s -= H[hidx(k, i)] * d[k];
+    d[i] = s * inv[i];
+  }
+  return ok;
+}
+
+// One wave = 64 frames x one tip component (wave w: component w % n_comp of tile w / n_comp, as dexr_kernel in tile mode).
+// blockDim.x = 64 * waves_per_block; dynamic LDS = waves_per_block * 64 * 4 * (3 * lds_frames + 4 * lds_terms + 1) bytes, laid
+// out as dexr_kernel's: the lane's target at T[(0..2) * 64 + lane], the broadcast placements of joints 1..3 behind W.
+__global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip32_kernel(const KernelParams kp, const dexr_comp_table* __restrict__ comps) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  using RT = RealTraits<float, true>;
+  constexpr auto hidx = [](int r, int c) constexpr { return r * (r + 1) / 2 + c; };
+  const int lane = threadIdx.x & 63;
+  const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int waves_per_block = blockDim.x >> 6;
+  const int64_t wave_global = (int64_t)blockIdx.x * waves_per_block + wave_in_block;
+  const int comp = (int)(wave_global % kp.n_comp);
+  const int64_t tile = wave_global / kp.n_comp;
+  const int64_t nB = kp.B;
+  if (tile * 64 >= nB) return;  // (the grid is rounded up to whole blocks)
+  const int64_t item = tile * 64 + lane;  // (prologue only: the loop keeps no per-lane address, see retire)
+  bool has = item < nB;  // the lane holds a frame that is not finished
+  const int ld = kp.n_opt;
+
+  const int per_wave = 64 * (3 * kp.lds_frames + 4 * kp.lds_terms + 1);
+  float* P = reinterpret_cast<float*>(lds_raw) + (size_t)wave_in_block * per_wave;
+  float* T = P + 64 * 3 * kp.lds_frames;
+  float* W = T + 64 * 3 * kp.lds_terms;
+
+  const dexr_comp_table& tb = comps[comp];
+  const int api0 = tip_pin((int)tb.api[0]);  // a tip component's four joints are consecutive columns of last_qpos / qpos_out
+  const int row = tb.term_ref[0];
+
+  // launches that do not fill the chip: touch the lines of the lane's frame before the constants of the pass are fetched
+  // and pinned (see dexr_kernel: the HBM round trip overlaps the table set-up)
+  float touch0 = 0.f, touch1 = 0.f, touch2 = 0.f;
+  const bool touch = kp.kpts != nullptr && has && (int64_t)gridDim.x * waves_per_block < 4096;
+  if (touch) {
+    touch0 = kp.last[item * ld + api0];
+    touch1 = kp.kpts[(item * kp.n_kp + kp.h_task[row]) * 3];
+    const int o = kp.h_origin[row];
+    touch2 = kp.kpts[(item * kp.n_kp + (o >= 0 ? o : 0)) * 3];
+  }
+  TipTabT<float> tt;
+  tt.load(tb, tb.term_task[0], tb.term_origin[0], W + 64 * kp.lds_terms, lane);
+  if (touch) asm volatile("" ::"v"(touch0), "v"(touch1), "v"(touch2));
+
+  // constants of the pass, pinned in SGPRs (the values read by every pass first)
+  const float k_delta = tip_pin(kp.norm_delta), k_lam0 = tip_pin(kp.lam0), k_tol = tip_pin(kp.tol), k_blind_tol = tip_pin(kp.blind_tol);
+  const float k_step_cap = tip_pin(kp.step_cap);
+  const float tip_beta = tip_pin(kp.huber_delta), tip_ibeta = tip_pin(1.f / kp.huber_delta);
+  const float tip_w = tip_pin(kp.inv_norm), tip_nw = tip_pin(kp.newton != 0 ? 1.f : 0.f);
+  const float k_lam_fastdec = tip_pin(kp.lam_fastdec), k_lam_jump = tip_pin(kp.lam_jump), k_lam_recover = tip_pin(kp.lam_recover);
+  const float k_stall_ratio = tip_pin(kp.stall_ratio);
+  const int k_stall_from = tip_pin(kp.stall_from), k_max_blind = tip_pin(kp.max_blind), k_max_iter = tip_pin(kp.max_iter);
+  // ... and what the pass derives from them, formed once (the same single multiplications dexr_kernel does) and pinned as
+  // well: left to the compiler each becomes a VGPR that is live through the whole loop
+  const float k_2delta = tip_pin(2.f * k_delta), k_10tol = tip_pin(10.f * k_tol);
+  const float k_stall_max = tip_pin(kp.stall_cap * k_tol);
+  const float k_lam_ok = tip_pin(fmax(2.f * k_delta, 10.f * k_lam0)), k_lam_ok_half = tip_pin(0.5f * fmax(2.f * k_delta, 10.f * k_lam0));
+  // options as thresholds (a comparison with +inf is never true): "lam_fastdec > 0 and rho > 0.9" is rho > k_rho_fast,
+  // "lam_recover > 0 and lambda > 10 lam0" is lambda > k_lam_rec_from -- one SGPR each instead of a hoisted lane mask
+  const float k_inf = __builtin_inff();
+  const float k_rho_fast = tip_pin(kp.lam_fastdec > 0 ? 0.9f : k_inf), k_lam_rec_from = tip_pin(kp.lam_recover > 0 ? 10.f * kp.lam0 : k_inf);
+
+  // ---- the lane's frame: start point / regularisation target from last_qpos, the term's target into the lane's LDS column
+  float x[4] = {0.f, 0.f, 0.f, 0.f}, xl[4] = {0.f, 0.f, 0.f, 0.f};
+  if (has) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float v = kp.last[item * ld + api0 + k];
+      xl[k] = v;
+      x[k] = v;
+    }
+    float rv[3];
+    if (kp.kpts) {
+      const float* a = kp.kpts + (item * kp.n_kp + kp.h_task[row]) * 3;
+      const int o = kp.h_origin[row];
+      if (o >= 0) {
+        const float* b = kp.kpts + (item * kp.n_kp + o) * 3;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) rv[i] = a[i] - b[i];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) rv[i] = a[i];
+      }
+    } else {
+      const float* r = kp.ref + (item * kp.n_ref + row) * 3;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) rv[i] = r[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) T[i * 64 + lane] = rv[i] * kp.scaling;  // f32 multiply: optimizer.py:246
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = RT::clamp(x[k], tt.lo[k], tt.hi[k]);
+  }
+
+  // kept model: data term + regulariser at the accepted point x
+  float Hs[10], gs[4], xo[4];
+  float F, lam = k_lam0, nu = 2, sprev = 1e30f;
+  int my_iters = 0, blind = 0, nrej = 0;
+
+  // value / gradient / Hessian at xe, regulariser included
+  auto eval = [&](const float (&xe)[4], float (&g)[4], float (&H)[10]) -> float {
+    float Ft = tip_eval<float>(tt, xe, T[lane], T[64 + lane], T[128 + lane], tip_beta, tip_ibeta, tip_w, tip_nw, g, H);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float dx = xe[k] - xl[k];
+      Ft += k_delta * dx * dx;
+      g[k] += k_2delta * dx;
+    }
+    return Ft;
+  };
+  // a finished lane hands back its four joints (last_qpos where the solve produced no finite answer) and drops out
+  // (the addresses are formed here, from the lane number, behind an opaque copy: hoisted out of the loop they would hold six
+  // VGPRs through every pass for three stores per frame)
+  auto retire = [&](int status) {
+    int l = lane;
+    asm volatile("" : "+v"(l));
+    const int64_t it = tile * 64 + l;
+    bool bad = (status == ST_FALLBACK);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) bad = bad || !(x[k] == x[k]);
+    if (bad) status = ST_FALLBACK;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) kp.qout[it * ld + api0 + k] = bad ? xl[k] : x[k];
+    if (kp.status) atomicMax(&kp.status[it], status);  // (max over the frame's components)
+    if (kp.iters) atomicMax(&kp.iters[it], my_iters);
+    has = false;
+  };
+
+  // ---- start point: adopt its model unconditionally
+  F = eval(x, gs, Hs);
+  if (has && !((bool)((int)(F == F) & (int)(fabs(F) < 1e30f)))) retire(ST_FALLBACK);
+
+  while (__any(has)) {
+    // (a) step from the kept model; joints held at a bound by the gradient sign are taken out of the system
+    float g[4], H[10], d[4];
+    uint32_t freemask = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float gk = gs[k];
+      const bool act = (bool)(((int)(x[k] <= tt.lo[k]) & (int)(gk > 0)) | ((int)(x[k] >= tt.hi[k]) & (int)(gk < 0)));
+      if (!act) freemask |= 1u << k;
+      g[k] = !act ? gk : 0.f;
+    }
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const bool fr = (freemask >> rr) & 1u;
+#pragma unroll
+      for (int cc = 0; cc < rr; ++cc) {
+        const bool fc = (freemask >> cc) & 1u;
+        H[hidx(rr, cc)] = (fr && fc) ? Hs[hidx(rr, cc)] : 0.f;
+      }
+      H[hidx(rr, rr)] = fr ? Hs[hidx(rr, rr)] + k_2delta + lam : 1.f;
+    }
+    float gm[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) gm[k] = g[k];
+    // `ok`: no pivot had to be modified, d is the Newton step of the damped model; a modified step is still tried
+    const bool ok = tip32_chol(H, g, d, k_2delta + lam);
+    // trust radius: no joint moves more than step_cap; a step from a modified factorisation is stretched (up to 8 x) towards it
+    // (sums of two products are written with fmaf: which product a contraction fuses is the compiler's choice per kernel,
+    // these are the ones dexr_kernel's code object has -- d.d as d0^2 rounded, then one FMA per further term; pred as the
+    // lambda term rounded, then one FMA with g.d)
+    float dmax = 0, gd = 0, dd = d[0] * d[0];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      dmax = fmax(dmax, fabs(d[k]));
+      gd -= gm[k] * d[k];
+      if (k > 0) dd = fmaf(d[k], d[k], dd);
+    }
+    const bool cut = (bool)((int)(k_step_cap > 0) & ((int)(dmax > k_step_cap) | ((int)!ok & (int)(dmax > 0.f))));
+    const float alpha = cut ? fmin(RT::div(k_step_cap, dmax), 8.f) : 1.f;
+    // predicted decrease of the damped model along alpha*d:  alpha (1 - alpha/2) (-g.d) + alpha^2/2 lam d.d
+    const float pred = fmaf(alpha * (1.f - 0.5f * alpha), gd, 0.5f * alpha * alpha * lam * dd);
+    float smax = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      xo[k] = x[k];
+      const float xt = RT::clamp(x[k] + alpha * d[k], tt.lo[k], tt.hi[k]);
+      smax = fmax(smax, fabs(xt - x[k]));
+      x[k] = xt;
+    }
+    // verified, undamped model and a Newton step this short: take it without evaluating the objective there (see dexr_kernel)
+    const bool last_step = (bool)((int)has & (int)ok & (int)(smax < k_blind_tol) & (int)(lam <= k_lam0) &
+                                  ((int)(smax < k_10tol) | (int)(smax < 0.1f * sprev)));
+
+    // (b) model at the trial point -- unless every lane that still holds a frame retires on the step alone
+    float Ft = F;
+    if (__any(has && !last_step)) Ft = eval(x, g, H);
+
+    // (c) accept / reject, damping update, termination
+    bool accept = false, finished = false;
+    int status = ST_MAXITER;
+    if (has) {
+      const bool finite = (bool)((int)(Ft == Ft) & (int)(smax == smax) & (int)(fabs(Ft) < 1e30f));
+      if (last_step && finite) {
+        accept = true;
+        finished = true;
+        status = ST_CONVERGED;
+        ++my_iters;
+        F = Ft;
+      } else {
+        // resolution of F in float32 (see dexr_kernel): a predicted decrease below it cannot be verified, only trusted
+        const float noise = 16.f * RT::eps() * fmax(fabs(F), 2e-3f);
+        const bool below_floor = (bool)((int)ok & (int)finite & (int)(pred <= noise) & (int)(smax < 1e-2f));
+        accept = (bool)((int)finite & ((int)(Ft <= F) | (int)below_floor));
+        ++my_iters;
+        if (accept) {
+          const float rho = RT::div(F - Ft, fmax(pred, 1e-30f));
+          const float t = 2.f * rho - 1.f;
+          float shrink = below_floor ? (float)(1.0 / 3.0) : fmax((float)(1.0 / 3.0), 1.f - t * t * t);
+          if (rho > k_rho_fast) shrink = (bool)((int)(nrej <= 2) & (int)(lam > k_lam_rec_from)) ? k_lam_recover : k_lam_fastdec;
+          lam = fmax(lam * shrink, 1e-9f);
+          nu = 2;
+          F = Ft;
+          const bool stalled = (bool)((int)below_floor & (int)(blind >= k_stall_from) & (int)(smax > k_stall_ratio * sprev) & (int)(smax < k_stall_max));
+          blind = below_floor ? blind + 1 : 0;
+          sprev = smax;
+          // a step below tol only means convergence when the damping is not what made it small (see dexr_kernel)
+          if ((bool)(((int)(smax < k_tol) & (int)(lam <= k_lam_ok)) | (int)stalled | (int)(blind >= k_max_blind))) {
+            finished = true;
+            status = ST_CONVERGED;
+          } else if (smax < k_tol) {
+            lam = fmax(0.1f * lam, k_lam_ok_half);
+          }
+        } else {
+          ++nrej;
+          lam = fmax(lam, 1e-6f) * nu;
+          // go straight to a damping that matters next to the curvature (lam_jump = 0, plain Nielsen: lambda >= 2e-6 here and
+          // fmax ignores a NaN, so the fmax with 0 x ds leaves it as it is -- dexr_kernel's `if (lam_jump > 0)` without the branch)
+          float ds = 0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) ds += Hs[hidx(k, k)];
+          lam = fmax(lam, k_lam_jump * ds / 4.f);
+          nu *= 2;
+          if (lam > 1e10f) {  // no descent direction resolvable any more
+            finished = true;
+            status = finite ? ST_CONVERGED : ST_FALLBACK;
+          }
+          if ((bool)((int)finite & (int)(smax < k_tol))) {  // rejected step below tol: converged at the rounding floor of F
+            finished = true;
+            status = ST_CONVERGED;
+          }
+        }
+        finished = (bool)((int)finished | (int)(my_iters >= k_max_iter));  // status stays ST_MAXITER
+      }
+    }
+    // the kept model follows the accepted point; a rejected step goes back to where it started
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      x[k] = accept ? x[k] : xo[k];
+      gs[k] = accept ? g[k] : gs[k];
+    }
+#pragma unroll
+    for (int i = 0; i < 10; ++i) Hs[i] = accept ? H[i] : Hs[i];
+
+    // (d) retire finished frames
+    if (finished) retire(status);
+  }
+}
+
+}  // namespace dexr

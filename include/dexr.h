@@ -68,6 +68,11 @@ typedef struct dexr_solve_options {
                                   Jacobian is formed) in registers, kinematics in LDS (dexr_red.hpp)                   */
 #define DEXR_KERNEL_WIDE 4     /* sixteen lanes per frame: chain-parallel kinematics, 4 x 4 lane grid for the Hessian and
                                   its Cholesky factor, no re-assembly after a rejected step (dexr_wide.hpp)             */
+#define DEXR_KERNEL_REGISTER_CHAIN 6 /* selectable, never reported: DEXR_KERNEL_REGISTER, and tip models (chain = 1) run every
+                                  float32 solve inside the serial-chain kernel dexr_kernel<4, float, SOLVE, CHAIN, EXT, TIP>.  Under
+                                  every other value their plain tile launches -- no queue, sequence, fleet addressing or objective
+                                  values asked for -- run the dedicated tip solve kernel (csrc/dexr_tip_solve.hpp): same arithmetic,
+                                  bitwise the same answers; this value exists to compare the two from one build                */
 #define DEXR_KERNEL_GENERAL 5  /* reported by dexr_model_kernel for models in the generic table format (dexr_tables.h): one
                                   wavefront per frame, every table in memory, float64 (dexr_gen.hpp); not selectable      */
 typedef struct dexr_tuning {
