@@ -94,6 +94,11 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     objs.append(comm_o)
     if force or _stale(comm_o, [comm_s, os.path.join(INCLUDE, "dexr.h")]):
         jobs.append((comm_s, comm_o, []))
+    pose_s, pose_o = os.path.join(CSRC, "dexr_pose.hip"), os.path.join(BUILD, "dexr_pose.o")
+    objs.append(pose_o)  # link poses + their VJP (include/dexr_pose.h): a unit of its own, in no workload's source hash
+    if force or _stale(pose_o, [pose_s, os.path.join(INCLUDE, "dexr_pose.h"), os.path.join(INCLUDE, "dexr.h"),
+                                os.path.join(CSRC, "dexr_math.hpp")]):
+        jobs.append((pose_s, pose_o, []))
     gen_s, gen_o = os.path.join(CSRC, "dexr_gen_inst.hip"), os.path.join(BUILD, "dexr_gen.o")
     objs.append(gen_o)
     if force or _stale(gen_o, [gen_s, os.path.join(CSRC, "dexr_gen.hpp")] + HEADERS):

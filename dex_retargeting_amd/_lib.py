@@ -51,6 +51,9 @@ EXPORTS = ["dexr_last_error", "dexr_version", "dexr_device_count", "dexr_default
            "dexr_retarget_kp_dev", "dexr_retarget_kp", "dexr_eval", "dexr_fk", "dexr_mano_keypoints_dev",
            "dexr_mano_keypoints", "dexr_comm_unique_id", "dexr_comm_create", "dexr_comm_destroy", "dexr_comm_info",
            "dexr_allgather", "dexr_comm_max_f64", "dexr_comm_barrier", "dexr_retarget_vjp_dev", "dexr_retarget_vjp"]
+# include/dexr_pose.h (link poses and their VJP): a list of its own, EXPORTS mirrors dexr.h alone
+POSE_EXPORTS = ["dexr_pose_model_create", "dexr_pose_model_destroy", "dexr_pose_model_info", "dexr_link_poses_dev",
+                "dexr_link_poses_vjp_dev", "dexr_link_poses", "dexr_link_poses_vjp"]
 UNIQUE_ID_BYTES = 128
 
 
@@ -116,6 +119,14 @@ def load() -> C.CDLL:
     lib.dexr_allgather.argtypes = [vp, vp, vp, C.c_size_t, vp]
     lib.dexr_comm_max_f64.argtypes = [vp, f64p, C.c_int32, vp]
     lib.dexr_comm_barrier.argtypes = [vp, vp]
+    lib.dexr_pose_model_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(vp)]
+    lib.dexr_pose_model_destroy.argtypes = [vp]
+    lib.dexr_pose_model_destroy.restype = None
+    lib.dexr_pose_model_info.argtypes = [vp, i32p, i32p, i32p, i32p]
+    lib.dexr_link_poses_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    lib.dexr_link_poses_vjp_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.dexr_link_poses.argtypes = [vp, i64, f64p, f64p, f64p, f64p]
+    lib.dexr_link_poses_vjp.argtypes = [vp, i64, f64p, f64p, f64p, f64p, f64p]
     _lib = lib
     return lib
 
@@ -350,6 +361,83 @@ class Model:
         check(load().dexr_retarget_vjp_dev(self._h, B, ref_ptr or None, fixed_ptr or None, last_ptr or None,
                                            state_ptr or None, q_ptr or None, grad_q_ptr or None, grad_ref_ptr or None,
                                            grad_last_ptr or None, status_ptr or None, stream or None))
+
+
+class PoseModel:
+    """Owns one dexr_pose_model (include/dexr_pose.h): the pose table of a list of links, resident in HBM."""
+
+    def __init__(self, blob: bytes):
+        lib = load()
+        self._h = C.c_void_p()
+        buf = C.create_string_buffer(blob, len(blob))
+        check(lib.dexr_pose_model_create(buf, len(blob), C.byref(self._h)))
+        v = [C.c_int32() for _ in range(4)]
+        check(lib.dexr_pose_model_info(self._h, *[C.byref(a) for a in v]))
+        self.n_in, self.n_fixed, self.n_link, self.n_joint = (int(a.value) for a in v)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib is not None:
+            _lib.dexr_pose_model_destroy(h)
+            self._h = None
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    # device-pointer entry points: float32, C-contiguous, enqueued on `stream` ------------------------
+    def poses_dev(self, B: int, x_ptr: int, fixed_ptr: int, pos_ptr: int, rot_ptr: int = 0, stream: int = 0):
+        """x (B, n_in), fixed (B, n_fixed) or 0 -> pos (B, n_link, 3), rot (B, n_link, 3, 3) or 0 (dexr_link_poses_dev)."""
+        check(load().dexr_link_poses_dev(self._h, B, x_ptr or None, fixed_ptr or None, pos_ptr or None, rot_ptr or None,
+                                         stream or None))
+
+    def vjp_dev(self, B: int, x_ptr: int, fixed_ptr: int, grad_pos_ptr: int, grad_rot_ptr: int, grad_x_ptr: int,
+                stream: int = 0):
+        """grad_pos (B, n_link, 3) and / or grad_rot (B, n_link, 3, 3) (0: absent) -> grad_x (B, n_in)
+        (dexr_link_poses_vjp_dev)."""
+        check(load().dexr_link_poses_vjp_dev(self._h, B, x_ptr or None, fixed_ptr or None, grad_pos_ptr or None,
+                                             grad_rot_ptr or None, grad_x_ptr or None, stream or None))
+
+    # host-pointer entry points: float64 in, float64 arithmetic, float64 out ----------------------------
+    def _host_inputs(self, x, fixed):
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float64)))
+        if x.shape[1] != self.n_in:
+            raise ValueError(f"x must have shape (B, {self.n_in}), got {x.shape}")
+        B = x.shape[0]
+        if self.n_fixed == 0:
+            fixed = None
+        else:
+            if fixed is None:
+                raise ValueError(f"the table reads {self.n_fixed} fixed joints: fixed of shape ({B}, {self.n_fixed}) is required")
+            fixed = np.ascontiguousarray(np.asarray(fixed, dtype=np.float64).reshape(B, -1))
+            if fixed.shape != (B, self.n_fixed):
+                raise ValueError(f"fixed must have shape ({B}, {self.n_fixed}), got {fixed.shape}")
+        return x, fixed, B
+
+    def poses(self, x, fixed=None, rotations: bool = True):
+        """-> pos (B, n_link, 3), rot (B, n_link, 3, 3) or None; float64 (dexr_link_poses)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        pos = np.zeros((B, self.n_link, 3), dtype=np.float64)
+        rot = np.zeros((B, self.n_link, 3, 3), dtype=np.float64) if rotations else None
+        check(load().dexr_link_poses(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), _ptr(pos, C.c_double),
+                                     _ptr(rot, C.c_double)))
+        return pos, rot
+
+    def vjp(self, x, fixed=None, grad_pos=None, grad_rot=None):
+        """-> grad_x (B, n_in) float64 (dexr_link_poses_vjp); at least one of the two gradients is required."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        if grad_pos is not None:
+            grad_pos = np.ascontiguousarray(grad_pos, dtype=np.float64)
+            if grad_pos.shape != (B, self.n_link, 3):
+                raise ValueError(f"grad_pos must have shape ({B}, {self.n_link}, 3), got {grad_pos.shape}")
+        if grad_rot is not None:
+            grad_rot = np.ascontiguousarray(grad_rot, dtype=np.float64)
+            if grad_rot.shape != (B, self.n_link, 3, 3):
+                raise ValueError(f"grad_rot must have shape ({B}, {self.n_link}, 3, 3), got {grad_rot.shape}")
+        gx = np.zeros((B, self.n_in), dtype=np.float64)
+        check(load().dexr_link_poses_vjp(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), _ptr(grad_pos, C.c_double),
+                                         _ptr(grad_rot, C.c_double), _ptr(gx, C.c_double)))
+        return gx
 
 
 def seq_compose_dev(B: int, T: int, dof_kind, dof_idx, dof_mult, dof_off, n_opt: int, n_fixed: int, qraw_ptr: int,

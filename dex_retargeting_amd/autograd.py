@@ -13,6 +13,10 @@ Variables that sit on a joint limit are held (zero gradient through them).  ``fi
 config scalars get no gradient; the DexPilot weights and projection bits are piecewise constant in ref_value and are held.
 Frames whose forward solve fell back to last_qpos (non-finite state) and frames whose Hessian is not positive definite at q get
 zero gradients.
+
+The task-space half: ``link_poses(optimizer, q, link_names)`` gives positions and rotations of any links at q
+(``dexr_link_poses_dev``) and back-propagates through them with the closed-form VJP kernel (``dexr_link_poses_vjp_dev``), so
+``keypoints -> retarget -> link_poses -> loss -> backward`` stays on the GPU.
 """
 from __future__ import annotations
 
@@ -147,4 +151,130 @@ def ref_value_from_keypoints(optimizer, keypoints):
     return keypoints[:, idx[1]] - keypoints[:, idx[0]]
 
 
-__all__ = ["retarget", "ref_value_from_keypoints"]
+# ---- task space: link poses of q, differentiable ---------------------------------------------------------------------
+def _check_poses(n_in, n_fixed, q, fixed_qpos, link_names, what="q"):
+    """Every argument rule -- types, dtypes, shapes, then the device -- before anything touches the GPU."""
+    import torch
+
+    if not isinstance(q, torch.Tensor):
+        raise ValueError(f"{what} must be a torch tensor")
+    if isinstance(link_names, str) or len(link_names) == 0:
+        raise ValueError("link_names must be a non-empty sequence of link names")
+    named = [(what, q)]
+    if fixed_qpos is not None:
+        if not isinstance(fixed_qpos, torch.Tensor):
+            raise ValueError("fixed_qpos must be a torch tensor")
+        named.append(("fixed_qpos", fixed_qpos))
+    for name, t in named:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if q.ndim != 2 or q.shape[1] != n_in:
+        raise ValueError(f"{what} must have shape (B, {n_in}), got {tuple(q.shape)}")
+    B = q.shape[0]
+    if n_fixed > 0 and fixed_qpos is None:
+        raise ValueError(f"the optimizer has {n_fixed} fixed joints: fixed_qpos of shape ({B}, {n_fixed}) is required")
+    if fixed_qpos is not None and tuple(fixed_qpos.shape) != (B, n_fixed):
+        raise ValueError(f"fixed_qpos must have shape ({B}, {n_fixed}), got {tuple(fixed_qpos.shape)}")
+    dev = q.device
+    if dev.type != "cuda":
+        raise ValueError(f"the tensors must be CUDA (HIP) tensors, got device {dev}")
+    for name, t in named:
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, {what} on {dev}: all tensors must be on one CUDA device")
+
+
+def _make_pose_function():
+    import torch
+
+    class _LinkPoses(torch.autograd.Function):
+        """One chunk of at most 64 links (one pose table).  Saves x (and fixed) only: the VJP kernel recomputes the walk."""
+
+        @staticmethod
+        def forward(ctx, x, fixed_qpos, model, rotations):
+            B = x.shape[0]
+            xc = x.detach().contiguous()
+            fixed = None if fixed_qpos is None or fixed_qpos.shape[1] == 0 else fixed_qpos.detach().contiguous()
+            pos = torch.empty((B, model.n_link, 3), dtype=torch.float32, device=x.device)
+            rot = torch.empty((B, model.n_link, 3, 3), dtype=torch.float32, device=x.device) if rotations else None
+            if B > 0:
+                model.poses_dev(B, xc.data_ptr(), 0 if fixed is None else fixed.data_ptr(), pos.data_ptr(),
+                                0 if rot is None else rot.data_ptr(), stream=torch.cuda.current_stream(x.device).cuda_stream)
+            ctx.model = model
+            ctx.has_fixed = fixed is not None
+            ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None -> NULL for the kernel
+            ctx.save_for_backward(*([xc] + ([fixed] if fixed is not None else [])))
+            if rot is None:
+                return pos
+            return pos, rot
+
+        @staticmethod
+        def backward(ctx, grad_pos, grad_rot=None):
+            if not ctx.needs_input_grad[0] or (grad_pos is None and grad_rot is None):
+                return None, None, None, None
+            saved = list(ctx.saved_tensors)
+            x = saved[0]
+            fixed = saved[1] if ctx.has_fixed else None
+            B = x.shape[0]
+            gp = None if grad_pos is None else grad_pos.detach().to(torch.float32).contiguous()
+            gr = None if grad_rot is None else grad_rot.detach().to(torch.float32).contiguous()
+            gx = torch.zeros_like(x)
+            if B > 0:
+                ctx.model.vjp_dev(B, x.data_ptr(), 0 if fixed is None else fixed.data_ptr(), 0 if gp is None else gp.data_ptr(),
+                                  0 if gr is None else gr.data_ptr(), gx.data_ptr(),
+                                  stream=torch.cuda.current_stream(x.device).cuda_stream)
+            return gx, None, None, None
+
+    return _LinkPoses
+
+
+_POSE_FN = None
+
+
+def _link_poses(model_of, x, fixed_qpos, link_names, rotations):
+    """chunks of 64 links -> one table each, results concatenated along the link axis."""
+    global _POSE_FN
+    import torch
+
+    if _POSE_FN is None:
+        _POSE_FN = _make_pose_function()
+    names = list(link_names)
+    pos, rot = [], []
+    with torch.cuda.device(x.device):
+        for c in range(0, len(names), 64):
+            out = _POSE_FN.apply(x, fixed_qpos, model_of(names[c:c + 64]), bool(rotations))
+            if rotations:
+                pos.append(out[0])
+                rot.append(out[1])
+            else:
+                pos.append(out)
+    if len(pos) == 1:
+        return pos[0], (rot[0] if rotations else None)
+    return torch.cat(pos, dim=1), (torch.cat(rot, dim=1) if rotations else None)
+
+
+def link_poses(optimizer, q, link_names, fixed_qpos=None, rotations=True):
+    """World poses of `link_names` at the optimiser's variables: q (B, n_opt) float32 CUDA -- what `retarget` returns --,
+    fixed_qpos (B, n_fixed) or None -> (pos (B, L, 3), rot (B, L, 3, 3) or None), float32, rotations row-major in the
+    URDF's own link frames.  Mimic joints follow their source.  Gradients flow to q only; `rotations=False` neither
+    computes nor allocates `rot`."""
+    n_fixed = len(optimizer.idx_pin2fixed)
+    _check_poses(optimizer.opt_dof, n_fixed, q, fixed_qpos, link_names)
+    for n in link_names:
+        optimizer.robot.kin.body_frame_index(n)  # ValueError on an unknown link, before any launch
+    return _link_poses(optimizer.pose_model, q, fixed_qpos, link_names, rotations)
+
+
+def robot_link_poses(robot, qpos, link_names, rotations=True):
+    """The same for a full robot qpos (B, robot.dof) in dof order -- what SeqRetargeting / DeviceSeqRetargeting return;
+    float64 tensors are converted to float32 once."""
+    import torch
+
+    if isinstance(qpos, torch.Tensor) and qpos.dtype == torch.float64:
+        qpos = qpos.to(torch.float32)
+    _check_poses(robot.dof, 0, qpos, None, link_names, what="qpos")
+    for n in link_names:
+        robot.kin.body_frame_index(n)
+    return _link_poses(robot.pose_model, qpos, None, link_names, rotations)
+
+
+__all__ = ["retarget", "ref_value_from_keypoints", "link_poses", "robot_link_poses"]

@@ -1,0 +1,632 @@
+// dexr_pose.hip -- batched link poses (positions AND rotations of any set of links) and their vector-Jacobian product:
+// the task-space half of differentiable retargeting (include/dexr_pose.h: table format and C ABI).
+//
+// MAPPING: one lane per frame, 64 frames per block.  The table (joint and link records, converted once at create time to
+// the arithmetic type of the kernel) is read with wave-uniform indices, i.e. through scalar loads; a lane holds the running
+// transform [R | p] of the joint it has just passed in registers.  The joints come in depth-first order, so the parent of
+// joint k is joint k-1 except where the walk returns to a fork: the table compiler numbers the fork transforms that are alive
+// at once (`save` / `restore` slots, children ordered smallest subtree first, so a 64-joint tree needs at most 6), and the
+// kernel keeps those slots in LDS, laid out [value][lane] (bank = lane: conflict free).  Nothing is indexed at run time in
+// registers, so nothing goes to scratch.
+//
+// Per joint the create step precomputes A = Rx, Bm = Rx K, C = Rx K^2 (K = skew(axis), Rx the placement's rotation), so that
+//   Rx Rot(axis, q) = A + sin q Bm + (1 - cos q) C                               (Rodrigues, 18 fma)
+//   R_k = R_parent (A + s Bm + (1 - c) C),   p_k = p_parent + R_parent (px + d xa)      (xa = Rx axis, d = q if prismatic)
+//
+// VJP (no Jacobian matrix): sweep 1 is the forward walk, and per link it forms the wrench about the world origin,
+//   f_l = grad_pos_l,   t_l = p_l x f_l + sum_j R_l[:, j] x grad_rot_l[:, j],
+// and parks it in LDS ([value][lane] again) at the link's SORTED position: links are sorted by parent joint and a subtree is
+// a contiguous run of joints, hence the links below joint k are the contiguous range [link_begin, sub_link_end).  Sweep 2
+// walks the joints again and at joint k sums that range (F, T0) and takes
+//   dL/dq_k = a_k . (T0 - o_k x F)   (revolute; a_k world axis, o_k world origin)        a_k . F   (prismatic),
+// then grad_x[col_k] (+)= mult_k dL/dq_k with plain loads / stores by the lane that owns the row (the first joint of a column
+// stores, later ones -- mimic joints of the same variable -- read, add, store; columns no joint reads are zeroed).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <new>
+#include <vector>
+
+#include "dexr.h"
+#include "dexr_math.hpp"
+#include "dexr_pose.h"
+
+int dexr_set_error(int code, const char* fmt, ...);  // dexr_api.hip
+
+namespace {
+
+constexpr int POSE_BLOCK = 64;
+
+template <typename T>
+struct JointD {
+  int32_t type, src_kind, src_col, restore, save, link_begin, link_end, sub_link_end, first_of_col, pad;
+  T mult, off;
+  T A[9], Bm[9], C[9], p[3], xa[3];
+};
+
+template <typename T>
+struct LinkD {
+  int32_t parent, out;
+  T R[9], p[3];
+};
+
+template <typename T>
+struct PoseArgs {
+  int32_t n_joint, n_link, n_base, n_in, n_fixed, n_slot;
+  uint64_t unused_lo, unused_hi, unused_2, unused_3;  // columns of x no joint reads (256 bits)
+  int64_t B;
+};
+
+__device__ __forceinline__ void sincos_t(float a, float* s, float* c) { sincosf(a, s, c); }
+__device__ __forceinline__ void sincos_t(double a, double* s, double* c) { dexr::sincos_f64(a, s, c); }
+
+// running transform of a lane
+template <typename T>
+struct Xf {
+  T R[9], p[3];
+};
+
+template <typename T>
+__device__ __forceinline__ void slot_store(T* lds, int slot, int nl, int lane, const Xf<T>& t) {
+  T* s = lds + (size_t)slot * 12 * nl + lane;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) s[i * nl] = t.R[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) s[(9 + i) * nl] = t.p[i];
+}
+
+template <typename T>
+__device__ __forceinline__ void slot_load(const T* lds, int slot, int nl, int lane, Xf<T>& t) {
+  const T* s = lds + (size_t)slot * 12 * nl + lane;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) t.R[i] = s[i * nl];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t.p[i] = s[(9 + i) * nl];
+}
+
+// one joint of the walk: t (transform of the previous joint, or of the fork this joint hangs off) -> transform of joint k;
+// `a` receives the world axis of the joint (its origin is the new t.p for a revolute joint)
+template <typename T>
+__device__ __forceinline__ void joint_step(const JointD<T>& J, const PoseArgs<T>& P, const T* __restrict__ x,
+                                           const T* __restrict__ fixed, int64_t b, T* slots, int nl, int lane, Xf<T>& t,
+                                           T a[3]) {
+  if (J.restore == DEXR_POSE_ROOT) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) t.R[i] = (i % 4 == 0) ? T(1) : T(0);
+    t.p[0] = t.p[1] = t.p[2] = T(0);
+  } else if (J.restore >= 0) {
+    slot_load(slots, J.restore, nl, lane, t);
+  }
+  T q = J.off;
+  if (J.src_kind == DEXR_POSE_SRC_X) q = fma(J.mult, x[b * P.n_in + J.src_col], J.off);
+  else if (J.src_kind == DEXR_POSE_SRC_FIXED) q = fma(J.mult, fixed[b * P.n_fixed + J.src_col], J.off);
+  T M[9], pl[3];
+  if (J.type == DEXR_POSE_REVOLUTE) {
+    T s, c;
+    sincos_t(q, &s, &c);
+    const T v = T(1) - c;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) M[i] = fma(v, J.C[i], fma(s, J.Bm[i], J.A[i]));
+#pragma unroll
+    for (int i = 0; i < 3; ++i) pl[i] = J.p[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) M[i] = J.A[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) pl[i] = fma(q, J.xa[i], J.p[i]);
+  }
+  Xf<T> n;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    n.p[i] = fma(t.R[3 * i + 2], pl[2], fma(t.R[3 * i + 1], pl[1], fma(t.R[3 * i], pl[0], t.p[i])));
+    a[i] = fma(t.R[3 * i + 2], J.xa[2], fma(t.R[3 * i + 1], J.xa[1], t.R[3 * i] * J.xa[0]));
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      n.R[3 * i + j] = fma(t.R[3 * i + 2], M[6 + j], fma(t.R[3 * i + 1], M[3 + j], t.R[3 * i] * M[j]));
+  }
+  t = n;
+  if (J.save >= 0) slot_store(slots, J.save, nl, lane, t);
+}
+
+// world pose of a link hanging off the joint whose transform is t
+template <typename T>
+__device__ __forceinline__ void link_pose(const LinkD<T>& L, const Xf<T>& t, T R[9], T p[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    p[i] = fma(t.R[3 * i + 2], L.p[2], fma(t.R[3 * i + 1], L.p[1], fma(t.R[3 * i], L.p[0], t.p[i])));
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      R[3 * i + j] = fma(t.R[3 * i + 2], L.R[6 + j], fma(t.R[3 * i + 1], L.R[3 + j], t.R[3 * i] * L.R[j]));
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(POSE_BLOCK) pose_forward_kernel(const JointD<T>* __restrict__ joints, const LinkD<T>* __restrict__ links,
+                                                                  PoseArgs<T> P, const T* __restrict__ x, const T* __restrict__ fixed,
+                                                                  T* __restrict__ pos, T* __restrict__ rot) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pose_lds[];
+  T* slots = reinterpret_cast<T*>(pose_lds);
+  const int nl = blockDim.x, lane = threadIdx.x;
+  const int64_t b0 = (int64_t)blockIdx.x * nl + lane;
+  const bool live = b0 < P.B;
+  const int64_t b = live ? b0 : P.B - 1;  // ragged tail: idle lanes recompute the last frame and store nothing
+  for (int l = 0; l < P.n_base; ++l) {    // links on the fixed base: their constant placement
+    const LinkD<T>& L = links[l];
+    if (live) {
+      T* o = pos + (b * P.n_link + L.out) * 3;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) o[i] = L.p[i];
+      if (rot) {
+        T* r = rot + (b * P.n_link + L.out) * 9;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) r[i] = L.R[i];
+      }
+    }
+  }
+  Xf<T> t;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) t.R[i] = (i % 4 == 0) ? T(1) : T(0);
+  t.p[0] = t.p[1] = t.p[2] = T(0);
+  for (int k = 0; k < P.n_joint; ++k) {
+    const JointD<T>& J = joints[k];
+    T a[3];
+    joint_step(J, P, x, fixed, b, slots, nl, lane, t, a);
+    for (int l = J.link_begin; l < J.link_end; ++l) {
+      const LinkD<T>& L = links[l];
+      T R[9], p[3];
+      link_pose(L, t, R, p);
+      if (live) {
+        T* o = pos + (b * P.n_link + L.out) * 3;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) o[i] = p[i];
+        if (rot) {
+          T* r = rot + (b * P.n_link + L.out) * 9;
+#pragma unroll
+          for (int i = 0; i < 9; ++i) r[i] = R[i];
+        }
+      }
+    }
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(POSE_BLOCK) pose_vjp_kernel(const JointD<T>* __restrict__ joints, const LinkD<T>* __restrict__ links,
+                                                              PoseArgs<T> P, const T* __restrict__ x, const T* __restrict__ fixed,
+                                                              const T* __restrict__ gpos, const T* __restrict__ grot,
+                                                              T* __restrict__ gx) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pose_lds[];
+  const int nl = blockDim.x, lane = threadIdx.x;
+  T* slots = reinterpret_cast<T*>(pose_lds);
+  T* wr = slots + (size_t)P.n_slot * 12 * nl + lane;  // wrench of sorted link l: wr[(6 l + i) nl]
+  const int64_t b0 = (int64_t)blockIdx.x * nl + lane;
+  const bool live = b0 < P.B;
+  const int64_t b = live ? b0 : P.B - 1;
+  Xf<T> t;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) t.R[i] = (i % 4 == 0) ? T(1) : T(0);
+  t.p[0] = t.p[1] = t.p[2] = T(0);
+  // sweep 1: link poses -> link wrenches about the world origin
+  for (int k = 0; k < P.n_joint; ++k) {
+    const JointD<T>& J = joints[k];
+    T a[3];
+    joint_step(J, P, x, fixed, b, slots, nl, lane, t, a);
+    for (int l = J.link_begin; l < J.link_end; ++l) {
+      const LinkD<T>& L = links[l];
+      T R[9], p[3], f[3] = {T(0), T(0), T(0)}, tq[3] = {T(0), T(0), T(0)};
+      link_pose(L, t, R, p);
+      if (gpos) {
+        const T* g = gpos + (b * P.n_link + L.out) * 3;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) f[i] = g[i];
+        tq[0] = p[1] * f[2] - p[2] * f[1];
+        tq[1] = p[2] * f[0] - p[0] * f[2];
+        tq[2] = p[0] * f[1] - p[1] * f[0];
+      }
+      if (grot) {
+        const T* g = grot + (b * P.n_link + L.out) * 9;
+        T G[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) G[i] = g[i];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {  // column j of R x column j of G
+          tq[0] += R[3 + j] * G[6 + j] - R[6 + j] * G[3 + j];
+          tq[1] += R[6 + j] * G[j] - R[j] * G[6 + j];
+          tq[2] += R[j] * G[3 + j] - R[3 + j] * G[j];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        wr[(6 * l + i) * nl] = f[i];
+        wr[(6 * l + 3 + i) * nl] = tq[i];
+      }
+    }
+  }
+  // columns of x that no joint reads: zero gradient
+  for (int c = 0; c < P.n_in; ++c) {
+    const uint64_t w = c < 64 ? P.unused_lo : (c < 128 ? P.unused_hi : (c < 192 ? P.unused_2 : P.unused_3));
+    if (((w >> (c & 63)) & 1ull) && live) gx[b * P.n_in + c] = T(0);
+  }
+  // sweep 2: per joint the wrench of the links below it, projected on the joint's motion
+  for (int k = 0; k < P.n_joint; ++k) {
+    const JointD<T>& J = joints[k];
+    T a[3];
+    joint_step(J, P, x, fixed, b, slots, nl, lane, t, a);
+    if (J.src_kind != DEXR_POSE_SRC_X) continue;
+    T F[3] = {T(0), T(0), T(0)}, M[3] = {T(0), T(0), T(0)};
+    for (int l = J.link_begin; l < J.sub_link_end; ++l) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        F[i] += wr[(6 * l + i) * nl];
+        M[i] += wr[(6 * l + 3 + i) * nl];
+      }
+    }
+    T g;
+    if (J.type == DEXR_POSE_REVOLUTE) {
+      const T* o = t.p;
+      const T m0 = M[0] - (o[1] * F[2] - o[2] * F[1]);
+      const T m1 = M[1] - (o[2] * F[0] - o[0] * F[2]);
+      const T m2 = M[2] - (o[0] * F[1] - o[1] * F[0]);
+      g = a[0] * m0 + a[1] * m1 + a[2] * m2;
+    } else {
+      g = a[0] * F[0] + a[1] * F[1] + a[2] * F[2];
+    }
+    g *= J.mult;
+    if (live) {
+      T* dst = gx + b * P.n_in + J.src_col;
+      if (J.first_of_col) *dst = g;
+      else *dst = *dst + g;
+    }
+  }
+}
+
+template <typename T>
+struct DevTables {
+  JointD<T>* joints = nullptr;
+  LinkD<T>* links = nullptr;
+};
+
+}  // namespace
+
+struct dexr_pose_model {
+  dexr_pose_header h;
+  int n_base = 0;
+  uint64_t unused[4] = {0, 0, 0, 0};
+  DevTables<float> f32;
+  DevTables<double> f64;
+};
+
+namespace {
+
+template <typename T>
+void build_tables(const dexr_pose_header& h, const std::vector<dexr_pose_joint>& js, const std::vector<dexr_pose_link>& ls,
+                  std::vector<JointD<T>>& dj, std::vector<LinkD<T>>& dl) {
+  dj.resize(js.size());
+  dl.resize(ls.size());
+  std::vector<char> seen(DEXR_POSE_MAXIN, 0);
+  for (size_t k = 0; k < js.size(); ++k) {
+    const dexr_pose_joint& j = js[k];
+    JointD<T>& d = dj[k];
+    memset(&d, 0, sizeof(d));
+    d.type = j.type;
+    d.src_kind = j.src_kind;
+    d.src_col = j.src_col;
+    d.restore = j.restore;
+    d.save = j.save;
+    d.link_begin = j.link_begin;
+    d.link_end = j.link_end;
+    d.sub_link_end = j.sub_link_end;
+    if (j.src_kind == DEXR_POSE_SRC_X) {
+      d.first_of_col = seen[j.src_col] ? 0 : 1;
+      seen[j.src_col] = 1;
+    }
+    d.mult = (T)j.mult;
+    d.off = (T)j.off;
+    const double* a = j.axis;
+    const double K[9] = {0, -a[2], a[1], a[2], 0, -a[0], -a[1], a[0], 0};
+    double K2[9], Rx[9];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        Rx[3 * r + c] = j.X[4 * r + c];
+        K2[3 * r + c] = K[3 * r] * K[c] + K[3 * r + 1] * K[3 + c] + K[3 * r + 2] * K[6 + c];
+      }
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) {
+        d.A[3 * r + c] = (T)Rx[3 * r + c];
+        d.Bm[3 * r + c] = (T)(Rx[3 * r] * K[c] + Rx[3 * r + 1] * K[3 + c] + Rx[3 * r + 2] * K[6 + c]);
+        d.C[3 * r + c] = (T)(Rx[3 * r] * K2[c] + Rx[3 * r + 1] * K2[3 + c] + Rx[3 * r + 2] * K2[6 + c]);
+      }
+      d.p[r] = (T)j.X[4 * r + 3];
+      d.xa[r] = (T)(Rx[3 * r] * a[0] + Rx[3 * r + 1] * a[1] + Rx[3 * r + 2] * a[2]);
+    }
+  }
+  for (size_t l = 0; l < ls.size(); ++l) {
+    dl[l].parent = ls[l].parent;
+    dl[l].out = ls[l].out;
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) dl[l].R[3 * r + c] = (T)ls[l].X[4 * r + c];
+      dl[l].p[r] = (T)ls[l].X[4 * r + 3];
+    }
+  }
+  (void)h;
+}
+
+template <typename T>
+hipError_t upload(const std::vector<JointD<T>>& dj, const std::vector<LinkD<T>>& dl, DevTables<T>& out) {
+  // (one record more than needed: an empty joint list still gets a valid pointer)
+  hipError_t e = hipMalloc((void**)&out.joints, (dj.size() + 1) * sizeof(JointD<T>));
+  if (e != hipSuccess) return e;
+  e = hipMalloc((void**)&out.links, (dl.size() + 1) * sizeof(LinkD<T>));
+  if (e != hipSuccess) return e;
+  if (!dj.empty()) {
+    e = hipMemcpy(out.joints, dj.data(), dj.size() * sizeof(JointD<T>), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+  }
+  return hipMemcpy(out.links, dl.data(), dl.size() * sizeof(LinkD<T>), hipMemcpyHostToDevice);
+}
+
+template <typename T>
+const DevTables<T>& tables_of(const dexr_pose_model* m);
+template <>
+const DevTables<float>& tables_of<float>(const dexr_pose_model* m) { return m->f32; }
+template <>
+const DevTables<double>& tables_of<double>(const dexr_pose_model* m) { return m->f64; }
+
+template <typename T>
+PoseArgs<T> args_of(const dexr_pose_model* m, int64_t B) {
+  PoseArgs<T> P;
+  P.n_joint = m->h.n_joint;
+  P.n_link = m->h.n_link;
+  P.n_base = m->n_base;
+  P.n_in = m->h.n_in;
+  P.n_fixed = m->h.n_fixed;
+  P.n_slot = m->h.n_slot;
+  P.unused_lo = m->unused[0];
+  P.unused_hi = m->unused[1];
+  P.unused_2 = m->unused[2];
+  P.unused_3 = m->unused[3];
+  P.B = B;
+  return P;
+}
+
+// lanes per block: 64, fewer only where the per-lane LDS rows of a block would not fit 64 KB (float64 VJP of a 64-link table)
+int block_lanes(size_t per_lane) {
+  int nl = POSE_BLOCK;
+  while (nl > 8 && per_lane * nl > 64 * 1024) nl /= 2;
+  return nl;
+}
+
+int check_call(const dexr_pose_model* m, int64_t B, const void* x, const void* fixed) {
+  if (!m) return dexr_set_error(DEXR_ERR_INVALID, "null pose model");
+  if (B < 0) return dexr_set_error(DEXR_ERR_INVALID, "negative batch size");
+  if (B == 0) return 1;
+  if (!x && m->h.n_in > 0) return dexr_set_error(DEXR_ERR_INVALID, "x is NULL");
+  if (!fixed && m->h.n_fixed > 0) return dexr_set_error(DEXR_ERR_INVALID, "the table reads %d fixed columns: fixed must not be NULL", m->h.n_fixed);
+  return 0;
+}
+
+template <typename T>
+int launch_forward(const dexr_pose_model* m, int64_t B, const T* x, const T* fixed, T* pos, T* rot, hipStream_t st) {
+  const size_t per_lane = (size_t)m->h.n_slot * 12 * sizeof(T);
+  const int nl = block_lanes(per_lane);
+  const int64_t blocks = (B + nl - 1) / nl;
+  if (blocks > 0x7fffffffLL) return dexr_set_error(DEXR_ERR_INVALID, "batch too large for one launch");
+  hipLaunchKernelGGL(pose_forward_kernel<T>, dim3((unsigned)blocks), dim3(nl), per_lane * nl, st, (const JointD<T>*)tables_of<T>(m).joints,
+                     (const LinkD<T>*)tables_of<T>(m).links, args_of<T>(m, B), x, fixed, pos, rot);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "link pose kernel launch failed: %s", hipGetErrorString(e));
+  return DEXR_OK;
+}
+
+template <typename T>
+int launch_vjp(const dexr_pose_model* m, int64_t B, const T* x, const T* fixed, const T* gpos, const T* grot, T* gx, hipStream_t st) {
+  const size_t per_lane = ((size_t)m->h.n_slot * 12 + (size_t)m->h.n_link * 6) * sizeof(T);
+  const int nl = block_lanes(per_lane);
+  const int64_t blocks = (B + nl - 1) / nl;
+  if (blocks > 0x7fffffffLL) return dexr_set_error(DEXR_ERR_INVALID, "batch too large for one launch");
+  hipLaunchKernelGGL(pose_vjp_kernel<T>, dim3((unsigned)blocks), dim3(nl), per_lane * nl, st, (const JointD<T>*)tables_of<T>(m).joints,
+                     (const LinkD<T>*)tables_of<T>(m).links, args_of<T>(m, B), x, fixed, gpos, grot, gx);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "link pose VJP kernel launch failed: %s", hipGetErrorString(e));
+  return DEXR_OK;
+}
+
+// device staging of the host-pointer entry points
+struct DevBuf {
+  void* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t put(const void* src, size_t n) {
+    hipError_t e = hipMalloc(&p, n ? n : 8);
+    if (e == hipSuccess && src && n) e = hipMemcpy(p, src, n, hipMemcpyHostToDevice);
+    return e;
+  }
+};
+
+#define POSE_HIP(expr)                                                                                         \
+  do {                                                                                                         \
+    hipError_t e_ = (expr);                                                                                    \
+    if (e_ != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+}  // namespace
+
+extern "C" {
+
+int dexr_pose_model_create(const void* blob, size_t nbytes, dexr_pose_model** out) {
+  if (!blob || !out) return dexr_set_error(DEXR_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (nbytes < sizeof(dexr_pose_header)) return dexr_set_error(DEXR_ERR_INVALID, "pose blob truncated: shorter than its header");
+  dexr_pose_header h;
+  memcpy(&h, blob, sizeof(h));
+  if (h.magic != DEXR_POSE_MAGIC) return dexr_set_error(DEXR_ERR_INVALID, "bad magic 0x%08x in pose blob", h.magic);
+  if (h.version != DEXR_POSE_VERSION) return dexr_set_error(DEXR_ERR_INVALID, "pose table version %u, library expects %u", h.version, DEXR_POSE_VERSION);
+  if (h.n_joint < 0 || h.n_joint > DEXR_POSE_MAXJ) return dexr_set_error(DEXR_ERR_INVALID, "pose table has %d joints (0..%d)", h.n_joint, DEXR_POSE_MAXJ);
+  if (h.n_link < 1 || h.n_link > DEXR_POSE_MAXL) return dexr_set_error(DEXR_ERR_INVALID, "pose table has %d links (1..%d)", h.n_link, DEXR_POSE_MAXL);
+  if (h.n_in < 0 || h.n_in > DEXR_POSE_MAXIN || h.n_fixed < 0 || h.n_fixed > DEXR_POSE_MAXIN)
+    return dexr_set_error(DEXR_ERR_INVALID, "pose table input widths out of range (n_in %d, n_fixed %d)", h.n_in, h.n_fixed);
+  if (h.n_slot < 0 || h.n_slot > DEXR_POSE_MAXSLOT) return dexr_set_error(DEXR_ERR_INVALID, "pose table uses %d slots (0..%d)", h.n_slot, DEXR_POSE_MAXSLOT);
+  const size_t want = sizeof(h) + (size_t)h.n_joint * sizeof(dexr_pose_joint) + (size_t)h.n_link * sizeof(dexr_pose_link);
+  if (nbytes < want) return dexr_set_error(DEXR_ERR_INVALID, "pose blob truncated: %zu B, its header implies %zu B", nbytes, want);
+  if (nbytes != want) return dexr_set_error(DEXR_ERR_INVALID, "pose blob size %zu B, its header implies %zu B", nbytes, want);
+  std::vector<dexr_pose_joint> js(h.n_joint);
+  std::vector<dexr_pose_link> ls(h.n_link);
+  const unsigned char* p = static_cast<const unsigned char*>(blob) + sizeof(h);
+  if (h.n_joint) memcpy(js.data(), p, (size_t)h.n_joint * sizeof(dexr_pose_joint));
+  memcpy(ls.data(), p + (size_t)h.n_joint * sizeof(dexr_pose_joint), (size_t)h.n_link * sizeof(dexr_pose_link));
+
+  // links: sorted by parent joint (base first), `out` a permutation
+  uint64_t out_seen = 0;
+  int n_base = 0;
+  for (int l = 0; l < h.n_link; ++l) {
+    const dexr_pose_link& L = ls[l];
+    if (L.parent < -1 || L.parent >= h.n_joint) return dexr_set_error(DEXR_ERR_INVALID, "pose link %d: parent joint %d out of range", l, L.parent);
+    if (l > 0 && L.parent < ls[l - 1].parent) return dexr_set_error(DEXR_ERR_INVALID, "pose link %d: links are not sorted by parent joint", l);
+    if (L.out < 0 || L.out >= h.n_link || ((out_seen >> L.out) & 1ull)) return dexr_set_error(DEXR_ERR_INVALID, "pose link %d: output row %d out of range or repeated", l, L.out);
+    out_seen |= 1ull << L.out;
+    if (L.parent == -1) ++n_base;
+  }
+  // joints: parent before child, contiguous subtrees, slot discipline, link ranges that match the link records
+  std::vector<int> slot_owner(DEXR_POSE_MAXSLOT, -1), sub_end(h.n_joint, 0);
+  uint64_t used[4] = {0, 0, 0, 0};
+  int next_link = n_base;
+  for (int k = 0; k < h.n_joint; ++k) {
+    const dexr_pose_joint& J = js[k];
+    if (J.parent < -1 || J.parent >= k) return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: parent %d does not come before it", k, J.parent);
+    if (J.type != DEXR_POSE_REVOLUTE && J.type != DEXR_POSE_PRISMATIC) return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: unknown type %d", k, J.type);
+    if (J.src_kind < DEXR_POSE_SRC_X || J.src_kind > DEXR_POSE_SRC_CONST) return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: unknown source kind %d", k, J.src_kind);
+    const int ncol = J.src_kind == DEXR_POSE_SRC_X ? h.n_in : (J.src_kind == DEXR_POSE_SRC_FIXED ? h.n_fixed : 1);
+    if (J.src_col < 0 || J.src_col >= ncol) return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: source column %d out of range (%d columns)", k, J.src_col, ncol);
+    if (J.src_kind == DEXR_POSE_SRC_X) used[J.src_col >> 6] |= 1ull << (J.src_col & 63);
+    // where the running transform comes from
+    if (J.parent == -1) {
+      if (J.restore != DEXR_POSE_ROOT) return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: a root joint must restore the identity", k);
+    } else if (J.restore == DEXR_POSE_CONTINUE) {
+      if (J.parent != k - 1) return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: continues joint %d but its parent is %d", k, k - 1, J.parent);
+    } else {
+      if (J.restore < 0 || J.restore >= h.n_slot || slot_owner[J.restore] != J.parent)
+        return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: restore slot %d does not hold the transform of its parent %d", k, J.restore, J.parent);
+    }
+    if (J.save != -1) {
+      if (J.save < 0 || J.save >= h.n_slot) return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: save slot %d out of range", k, J.save);
+      slot_owner[J.save] = k;
+    }
+    if (J.link_begin != next_link || J.link_end < J.link_begin || J.link_end > h.n_link)
+      return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: link range [%d, %d) malformed", k, J.link_begin, J.link_end);
+    for (int l = J.link_begin; l < J.link_end; ++l)
+      if (ls[l].parent != k) return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: link %d in its range has parent %d", k, l, ls[l].parent);
+    next_link = J.link_end;
+  }
+  if (next_link != h.n_link) return dexr_set_error(DEXR_ERR_INVALID, "pose table: %d links are in no joint's range", h.n_link - next_link);
+  // subtree link ranges: joints below k are the run k+1 .. while parent >= k
+  for (int k = 0; k < h.n_joint; ++k) {
+    int e = k + 1;
+    while (e < h.n_joint && js[e].parent >= k) ++e;
+    const int want_end = e < h.n_joint ? js[e].link_begin : h.n_link;
+    if (js[k].sub_link_end != want_end) return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: subtree link range ends at %d, the tree says %d", k, js[k].sub_link_end, want_end);
+    for (int c = k + 1; c < e; ++c) {  // every joint of the run must descend from k (depth-first order)
+      int a = js[c].parent;
+      while (a > k) a = js[a].parent;
+      if (a != k) return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: joints are not in depth-first order", c);
+    }
+  }
+
+  dexr_pose_model* m = new (std::nothrow) dexr_pose_model();
+  if (!m) return dexr_set_error(DEXR_ERR_INVALID, "out of host memory");
+  m->h = h;
+  m->n_base = n_base;
+  for (int w = 0; w < 4; ++w) m->unused[w] = ~used[w];
+  std::vector<JointD<float>> jf;
+  std::vector<LinkD<float>> lf;
+  std::vector<JointD<double>> jd;
+  std::vector<LinkD<double>> ld;
+  build_tables<float>(h, js, ls, jf, lf);
+  build_tables<double>(h, js, ls, jd, ld);
+  hipError_t e = upload(jf, lf, m->f32);
+  if (e == hipSuccess) e = upload(jd, ld, m->f64);
+  if (e != hipSuccess) {
+    dexr_pose_model_destroy(m);
+    return dexr_set_error(DEXR_ERR_HIP, "uploading pose tables failed: %s", hipGetErrorString(e));
+  }
+  *out = m;
+  return DEXR_OK;
+}
+
+void dexr_pose_model_destroy(dexr_pose_model* m) {
+  if (!m) return;
+  if (m->f32.joints) (void)hipFree(m->f32.joints);
+  if (m->f32.links) (void)hipFree(m->f32.links);
+  if (m->f64.joints) (void)hipFree(m->f64.joints);
+  if (m->f64.links) (void)hipFree(m->f64.links);
+  delete m;
+}
+
+int dexr_pose_model_info(const dexr_pose_model* m, int32_t* n_in, int32_t* n_fixed, int32_t* n_link, int32_t* n_joint) {
+  if (!m) return dexr_set_error(DEXR_ERR_INVALID, "null pose model");
+  if (n_in) *n_in = m->h.n_in;
+  if (n_fixed) *n_fixed = m->h.n_fixed;
+  if (n_link) *n_link = m->h.n_link;
+  if (n_joint) *n_joint = m->h.n_joint;
+  return DEXR_OK;
+}
+
+int dexr_link_poses_dev(const dexr_pose_model* m, int64_t B, const float* x, const float* fixed, float* pos_out, float* rot_out,
+                        void* stream) {
+  const int c = check_call(m, B, x, fixed);
+  if (c) return c < 0 ? c : DEXR_OK;
+  if (!pos_out) return dexr_set_error(DEXR_ERR_INVALID, "pos_out is NULL");
+  return launch_forward<float>(m, B, x, fixed, pos_out, rot_out, (hipStream_t)stream);
+}
+
+int dexr_link_poses_vjp_dev(const dexr_pose_model* m, int64_t B, const float* x, const float* fixed, const float* grad_pos,
+                            const float* grad_rot, float* grad_x_out, void* stream) {
+  if (m && !grad_pos && !grad_rot) return dexr_set_error(DEXR_ERR_INVALID, "grad_pos and grad_rot are both NULL");
+  const int c = check_call(m, B, x, fixed);
+  if (c) return c < 0 ? c : DEXR_OK;
+  if (!grad_x_out && m->h.n_in > 0) return dexr_set_error(DEXR_ERR_INVALID, "grad_x_out is NULL");
+  return launch_vjp<float>(m, B, x, fixed, grad_pos, grad_rot, grad_x_out, (hipStream_t)stream);
+}
+
+int dexr_link_poses(const dexr_pose_model* m, int64_t B, const double* x, const double* fixed, double* pos_out, double* rot_out) {
+  const int c = check_call(m, B, x, fixed);
+  if (c) return c < 0 ? c : DEXR_OK;
+  if (!pos_out) return dexr_set_error(DEXR_ERR_INVALID, "pos_out is NULL");
+  const size_t nx = (size_t)B * m->h.n_in * sizeof(double), nf = (size_t)B * m->h.n_fixed * sizeof(double);
+  const size_t np = (size_t)B * m->h.n_link * 3 * sizeof(double);
+  DevBuf dx, dfix, dp, dr;
+  POSE_HIP(dx.put(x, nx));
+  POSE_HIP(dfix.put(fixed, nf));
+  POSE_HIP(dp.put(nullptr, np));
+  if (rot_out) POSE_HIP(dr.put(nullptr, 3 * np));
+  const int rc = launch_forward<double>(m, B, (const double*)dx.p, (const double*)dfix.p, (double*)dp.p, (double*)dr.p, nullptr);
+  if (rc) return rc;
+  POSE_HIP(hipDeviceSynchronize());
+  POSE_HIP(hipMemcpy(pos_out, dp.p, np, hipMemcpyDeviceToHost));
+  if (rot_out) POSE_HIP(hipMemcpy(rot_out, dr.p, 3 * np, hipMemcpyDeviceToHost));
+  return DEXR_OK;
+}
+
+int dexr_link_poses_vjp(const dexr_pose_model* m, int64_t B, const double* x, const double* fixed, const double* grad_pos,
+                        const double* grad_rot, double* grad_x_out) {
+  if (m && !grad_pos && !grad_rot) return dexr_set_error(DEXR_ERR_INVALID, "grad_pos and grad_rot are both NULL");
+  const int c = check_call(m, B, x, fixed);
+  if (c) return c < 0 ? c : DEXR_OK;
+  if (!grad_x_out && m->h.n_in > 0) return dexr_set_error(DEXR_ERR_INVALID, "grad_x_out is NULL");
+  const size_t nx = (size_t)B * m->h.n_in * sizeof(double), nf = (size_t)B * m->h.n_fixed * sizeof(double);
+  const size_t np = (size_t)B * m->h.n_link * 3 * sizeof(double);
+  DevBuf dx, dfix, dgp, dgr, dgx;
+  POSE_HIP(dx.put(x, nx));
+  POSE_HIP(dfix.put(fixed, nf));
+  if (grad_pos) POSE_HIP(dgp.put(grad_pos, np));
+  if (grad_rot) POSE_HIP(dgr.put(grad_rot, 3 * np));
+  POSE_HIP(dgx.put(nullptr, nx));
+  const int rc = launch_vjp<double>(m, B, (const double*)dx.p, (const double*)dfix.p, (const double*)dgp.p, (const double*)dgr.p,
+                                    (double*)dgx.p, nullptr);
+  if (rc) return rc;
+  POSE_HIP(hipDeviceSynchronize());
+  if (nx) POSE_HIP(hipMemcpy(grad_x_out, dgx.p, nx, hipMemcpyDeviceToHost));
+  return DEXR_OK;
+}
+
+}  // extern "C"

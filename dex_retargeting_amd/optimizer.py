@@ -78,6 +78,7 @@ class Optimizer:
         self._model: Optional[_lib.Model] = None
         self._compiled: Optional[mc.CompiledModel] = None
         self._vjp_model: Optional[_lib.Model] = None  # vjp_model(): the same problem on generic tables
+        self._pose_models: dict = {}  # pose_model(): per link tuple
         # True: compile to the generic table format even when the model fits the fixed-size records (the general kernel
         # then serves it; used by the tests that cross-check that kernel on the shipped robots)
         self.use_generic_tables = False
@@ -109,6 +110,7 @@ class Optimizer:
             self.idx_pin2fixed = np.array([x for x in fixed_idx if x not in mimic_idx], dtype=int)
         self._model = None
         self._vjp_model = None
+        self._pose_models = {}
 
     @property
     def fixed_joint_names(self):
@@ -166,6 +168,28 @@ class Optimizer:
         if self._vjp_model is None:
             self._vjp_model = _lib.Model(self._compile(True).to_blob())
         return self._vjp_model
+
+    def pose_source_map(self):
+        """Where each joint value of the robot comes from in OPTIMIZER order (pose_tables.SourceMap): target joints from
+        the (B, n_opt) rows retarget_batch / autograd.retarget return, fixed joints from fixed_qpos, mimic joints folded onto
+        their source's column as mult * x[source] + off (kinematics_adaptor.py:102-105)."""
+        from .pose_tables import SourceMap
+
+        mimic = []
+        if isinstance(self.adaptor, MimicJointKinematicAdaptor):
+            a = self.adaptor
+            mimic = list(zip(a.idx_pin2mimic, a.idx_pin2source, a.multipliers, a.offsets))
+        return SourceMap.optimizer_order(self.robot.kin, self.idx_pin2target, self.idx_pin2fixed, mimic)
+
+    def pose_model(self, link_names) -> _lib.PoseModel:
+        """Pose table of `link_names` (at most 64) on pose_source_map() (dexr_link_poses_dev / _vjp_dev): the VJP lands on
+        the optimiser's variables.  Cached per link tuple; dropped by set_kinematic_adaptor."""
+        from .pose_tables import compile_poses
+
+        key = tuple(link_names)
+        if key not in self._pose_models:
+            self._pose_models[key] = _lib.PoseModel(compile_poses(self.robot.kin, list(key), self.pose_source_map()))
+        return self._pose_models[key]
 
     def _options(self) -> Optional[_lib.SolveOptions]:
         if all(v is None for v in self.solve_options.values()):

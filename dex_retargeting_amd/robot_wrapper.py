@@ -10,6 +10,7 @@ import numpy.typing as npt
 
 from . import _lib
 from .model_compiler import compile_fk
+from .pose_tables import compile_poses
 from .urdf import KinematicModel, parse_urdf
 
 
@@ -35,6 +36,7 @@ class RobotWrapper:
         self.q0 = np.zeros(self.kin.dof)  # pin.neutral for 1-DoF joints
         self._qpos = np.zeros((1, self.kin.dof))
         self._fk_models = {}
+        self._pose_models = {}
 
     # ---- properties (robot_wrapper.py:28-52) ------------------------------------------------------
     @property
@@ -103,6 +105,27 @@ class RobotWrapper:
             self._fk_models[key] = _lib.Model(compile_fk(self.kin, names).to_blob())
         q = np.atleast_2d(np.asarray(qpos, dtype=np.float64))
         return self._fk_models[key].fk(q, len(key))
+
+    def pose_model(self, link_names: Sequence[str]) -> _lib.PoseModel:
+        """Pose table of `link_names` (at most 64) over the full qpos in dof order, cached per link tuple."""
+        key = tuple(link_names)
+        if key not in self._pose_models:
+            self._pose_models[key] = _lib.PoseModel(compile_poses(self.kin, list(key)))
+        return self._pose_models[key]
+
+    def link_poses(self, qpos: npt.NDArray, link_indices: Sequence[int]) -> np.ndarray:
+        """(B, nq) -> (B, L, 4, 4) float64 world poses of the given links (frame ids from get_link_index), positions and
+        rotations from the device (dexr_link_poses: float64 arithmetic over float64 tables)."""
+        ids = [int(i) for i in link_indices]
+        q = np.atleast_2d(np.asarray(qpos, dtype=np.float64))
+        out = np.zeros((q.shape[0], len(ids), 4, 4), dtype=np.float64)
+        out[:, :, 3, 3] = 1.0
+        for c in range(0, len(ids), 64):  # a pose table holds up to 64 links: ask in chunks
+            names = [self.kin.frames[self.kin.body_of_frame_id(i)].name for i in ids[c:c + 64]]
+            pos, rot = self.pose_model(names).poses(q)
+            out[:, c:c + 64, :3, :3] = rot
+            out[:, c:c + 64, :3, 3] = pos
+        return out
 
     def get_link_pose(self, link_id: int) -> npt.NDArray:
         """4x4 pose of one link at the configuration last given to compute_forward_kinematics.  The translation comes
