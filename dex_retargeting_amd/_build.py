@@ -1,7 +1,9 @@
 """Build libdexr.so (hipcc, gfx950) in-tree.  Used by __graft_entry__.build(); hipcc cross-compiles without a GPU."""
 from __future__ import annotations
 
+import functools
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -15,9 +17,6 @@ LIB = os.environ.get("DEXR_LIB_OUT") or os.path.join(HERE, "libdexr.so")
 BUCKETS = (4, 8, 16, 24, 32)
 CHAIN_BUCKETS = (4,)
 VARIANTS = ((0, 0), (1, 0), (1, 1), (1, 2))  # (float64?, mode): f32 solve, f64 solve, f64 eval, f64 fk
-HEADERS = [os.path.join(CSRC, "dexr_kernel.hpp"), os.path.join(CSRC, "dexr_launch.hpp"), os.path.join(CSRC, "dexr_tip.hpp"),
-           os.path.join(CSRC, "dexr_math.hpp"),
-           os.path.join(INCLUDE, "dexr.h"), os.path.join(INCLUDE, "dexr_tables.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", f"-I{CSRC}"] + \
     os.environ.get("DEXR_EXTRA_FLAGS", "").split()
 # The SLP vectoriser turns the 3-vector arithmetic of the register kernels into v_pk_* pairs that it then has to
@@ -28,6 +27,52 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", 
 # rounding or denormal support -- parity is measured against the float64 oracle: 2.5-ulp v_rcp/v_rsq sequences and
 # flushed denormals save another 8 % of the chain kernel's VALU instructions.
 NO_SLP = ["-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-flush-denormals-to-zero"]
+
+
+def _inst(n: int, f64: int, *defs: str) -> list:
+    """Flags of a solve-mode (DEXR_MODE=0) instantiation of dexr_inst.hip."""
+    return NO_SLP + [f"-DDEXR_NMAX={n}", f"-DDEXR_F64={f64}", "-DDEXR_MODE=0", *defs]
+
+
+_INST, _WIDE = "dexr_inst.hip", "dexr_wide_inst.hip"
+_MIMIC, _MODCHOL, _SPRINT = "-DDEXR_MIMIC=1", "-DDEXR_MODCHOL=1", "-DDEXR_SPRINT=1"
+# Everything libdexr.so is made of, in link order: (object file, source file, flags after FLAGS).  Host-side units first;
+# dexr_pose is the link poses + their VJP (include/dexr_pose.h): a unit of its own, in no workload's source hash.
+OBJECTS = [(f"dexr_{u}.o", f"dexr_{u}.hip", []) for u in ("api", "prep", "aux", "comm", "pose")]
+OBJECTS += [("dexr_gen.o", "dexr_gen_inst.hip", [])]
+# register kernel of small components, biggest first so the thread pool stays busy (jobs start in table order);
+# bucket 32 serves float32 requests with its float64 kernel (see dexr_launch.hpp)
+OBJECTS += [(f"dexr_inst_{n}_{f64}_{mode}.o", _INST, NO_SLP + [f"-DDEXR_NMAX={n}", f"-DDEXR_F64={f64}", f"-DDEXR_MODE={mode}"])
+            for n in sorted(BUCKETS, reverse=True) for f64, mode in VARIANTS if (n, f64, mode) != (32, 0, 0)]
+# sixteen-lanes-per-frame kernel for dense components
+# (the 16-row grid fits three waves per SIMD: 168 VGPRs, 18 of them spilled; 11.8 KB of LDS per wave)
+OBJECTS += [(f"dexr_wide_{n}.o", _WIDE, NO_SLP + [f"-DDEXR_NMAX={n}"] + (["-DDEXR_WIDE_MINW=3"] if n == 16 else []))
+            for n in (16, 24, 32)]
+# ... one frame per wave (SPRINT): the launch shape of small batches
+# (register budgets: two waves per SIMD for the 16- / 24-row grids (246 / 256 registers, 3 spilled at n = 24), one for
+# the 32-row grid (272): small batches do not need the occupancy)
+OBJECTS += [(f"dexr_wide_s_{n}.o", _WIDE, NO_SLP + [f"-DDEXR_NMAX={n}", _SPRINT, "-DDEXR_WIDE_MINW=1" if n == 32 else "-DDEXR_WIDE_MINW=2"])
+            for n in (16, 24, 32)]
+# the same kernel on the grid of the optimised variables (mimic joints): one frame per wave, then sixteen lanes per frame;
+# plain / modified Cholesky each
+OBJECTS += [(f"dexr_wide_{tag}_16.o", _WIDE, NO_SLP + ["-DDEXR_NMAX=16", _MIMIC] + defs)
+            for tag, defs in (("s_m", [_SPRINT]), ("s_mc", [_SPRINT, _MODCHOL]), ("m", []), ("mc", [_MODCHOL]))]
+# ... its float64 instantiation (dexr_tuning.kernel_f64): one wave per SIMD, four frames per wave
+OBJECTS += [(f"dexr_wide_d_{tag}.o", _WIDE, NO_SLP + defs + ["-DDEXR_WIDE_F64=1"])
+            for tag, defs in (("16", ["-DDEXR_NMAX=16"]), ("24", ["-DDEXR_NMAX=24"]), ("m_16", ["-DDEXR_NMAX=16", _MIMIC]),
+                              ("mc_16", ["-DDEXR_NMAX=16", _MIMIC, _MODCHOL]))]
+# reduced-variable kernel (mimic models): Hessian of the variables in registers
+OBJECTS += [(f"dexr_red_{nv}.o", "dexr_red_inst.hip", NO_SLP + [f"-DDEXR_NV={nv}"]) for nv in (8, 16)]
+# small components with fleet / sequence addressing (EXT)
+OBJECTS += [(f"dexr_inst_ext_{n}_{f64}_0.o", _INST, _inst(n, f64, "-DDEXR_EXT=1")) for n, f64 in ((4, 0), (8, 0), (4, 1), (8, 1))]
+OBJECTS += [(f"dexr_inst_ext_chain_{n}_0_0.o", _INST, _inst(n, 0, "-DDEXR_CHAIN=1", "-DDEXR_EXT=1")) for n in CHAIN_BUCKETS]
+# tip pass of the serial-chain kernel (dexr_tip.hpp): float32, and float64 (the reference's arithmetic)
+OBJECTS += [(f"dexr_inst_{tag}_4_{f64}_0.o", _INST, _inst(4, f64, "-DDEXR_CHAIN=1", "-DDEXR_TIP=1", *defs))
+            for f64 in (0, 1) for tag, defs in (("tip", []), ("ext_tip", ["-DDEXR_EXT=1"]))]
+# the float32 tip solve as a kernel of its own (dexr_tip_solve.hpp): plain tile launches
+OBJECTS += [("dexr_tip32.o", "dexr_tip_inst.hip", NO_SLP)]
+# serial-chain specialisation, float32 solve only
+OBJECTS += [(f"dexr_inst_chain_{n}_0_0.o", _INST, _inst(n, 0, "-DDEXR_CHAIN=1")) for n in CHAIN_BUCKETS]
 
 
 # Which sources decide the code a bench workload's dominant kernel runs (used to key the committed rocprofv3 PMC
@@ -66,6 +111,34 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found")
 
 
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
+
+
+@functools.lru_cache(maxsize=None)
+def _includes(path: str) -> tuple:
+    """The files `path` names in `#include "..."` lines, each found in csrc/ or include/ (one scan per file)."""
+    with open(path) as f:
+        names = _INCLUDE.findall(f.read())
+    found = []
+    for n in names:
+        hits = [p for p in (os.path.join(CSRC, n), os.path.join(INCLUDE, n)) if os.path.exists(p)]
+        if not hits:
+            raise RuntimeError(f"{path} includes {n!r}, which is in neither csrc/ nor include/")
+        found.append(hits[0])
+    return tuple(found)
+
+
+def _deps(source: str) -> set:
+    """`source` and the transitive closure of its quoted includes: what an object compiled from it depends on."""
+    todo, seen = [source], set()
+    while todo:
+        p = todo.pop()
+        if p not in seen:
+            seen.add(p)
+            todo += _includes(p)
+    return seen
+
+
 def _stale(target: str, deps) -> bool:
     if not os.path.exists(target):
         return True
@@ -73,114 +146,30 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _pool_limit() -> int:
+    """Compile jobs to run at once: MAX_JOBS or CMAKE_BUILD_PARALLEL_LEVEL (the first set to a positive integer), never
+    more than 16 or than this machine's CPUs.  Not os.cpu_count() alone: a shared machine reports CPUs a build may not use."""
+    asked = [int(v) for v in (os.environ.get(k, "").strip() for k in ("MAX_JOBS", "CMAKE_BUILD_PARALLEL_LEVEL")) if v.isdigit() and int(v) > 0]
+    return min(asked[0] if asked else 16, 16, os.cpu_count() or 16)
+
+
 def build_library(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(BUILD, exist_ok=True)
     hipcc = _hipcc()
-    jobs = []
-    objs = []
-    api_s, api_o = os.path.join(CSRC, "dexr_api.hip"), os.path.join(BUILD, "dexr_api.o")
-    objs.append(api_o)
-    if force or _stale(api_o, [api_s, os.path.join(CSRC, "dexr_hostctx.hpp"), os.path.join(CSRC, "dexr_gen.hpp")] + HEADERS):
-        jobs.append((api_s, api_o, []))
-    prep_s, prep_o = os.path.join(CSRC, "dexr_prep.hip"), os.path.join(BUILD, "dexr_prep.o")
-    objs.append(prep_o)
-    if force or _stale(prep_o, [prep_s, os.path.join(INCLUDE, "dexr.h")]):
-        jobs.append((prep_s, prep_o, []))
-    aux_s, aux_o = os.path.join(CSRC, "dexr_aux.hip"), os.path.join(BUILD, "dexr_aux.o")
-    objs.append(aux_o)
-    if force or _stale(aux_o, [aux_s, os.path.join(INCLUDE, "dexr.h")]):
-        jobs.append((aux_s, aux_o, []))
-    comm_s, comm_o = os.path.join(CSRC, "dexr_comm.hip"), os.path.join(BUILD, "dexr_comm.o")
-    objs.append(comm_o)
-    if force or _stale(comm_o, [comm_s, os.path.join(INCLUDE, "dexr.h")]):
-        jobs.append((comm_s, comm_o, []))
-    pose_s, pose_o = os.path.join(CSRC, "dexr_pose.hip"), os.path.join(BUILD, "dexr_pose.o")
-    objs.append(pose_o)  # link poses + their VJP (include/dexr_pose.h): a unit of its own, in no workload's source hash
-    if force or _stale(pose_o, [pose_s, os.path.join(INCLUDE, "dexr_pose.h"), os.path.join(INCLUDE, "dexr.h"),
-                                os.path.join(CSRC, "dexr_math.hpp")]):
-        jobs.append((pose_s, pose_o, []))
-    gen_s, gen_o = os.path.join(CSRC, "dexr_gen_inst.hip"), os.path.join(BUILD, "dexr_gen.o")
-    objs.append(gen_o)
-    if force or _stale(gen_o, [gen_s, os.path.join(CSRC, "dexr_gen.hpp")] + HEADERS):
-        jobs.append((gen_s, gen_o, []))
-    inst_s = os.path.join(CSRC, "dexr_inst.hip")
-    # developer shortcut: DEXR_BUILD_ONLY="4,8" rebuilds only those buckets and reuses the other objects as they are
+    # developer shortcut: DEXR_BUILD_ONLY="4,8" rebuilds only those buckets and reuses the other buckets' objects as they are
     # (only valid while KernelParams / the launcher signature are unchanged)
     only = os.environ.get("DEXR_BUILD_ONLY")
-    only = None if not only else {int(v) for v in only.split(",")}
-    # biggest kernels first so the thread pool stays busy
-    for n in sorted(BUCKETS, reverse=True):
-        for f64, mode in VARIANTS:
-            if n == 32 and (f64, mode) == (0, 0):
-                continue  # bucket 32 serves float32 requests with its float64 kernel (see dexr_launch.hpp)
-            o = os.path.join(BUILD, f"dexr_inst_{n}_{f64}_{mode}.o")
-            objs.append(o)
-            if only is not None and n not in only and os.path.exists(o):
-                continue
-            if force or _stale(o, [inst_s] + HEADERS):
-                jobs.append((inst_s, o, NO_SLP + [f"-DDEXR_NMAX={n}", f"-DDEXR_F64={f64}", f"-DDEXR_MODE={mode}"]))
-    wide_s = os.path.join(CSRC, "dexr_wide_inst.hip")
-    for n in (16, 24, 32):  # sixteen-lanes-per-frame kernel for dense components
-        o = os.path.join(BUILD, f"dexr_wide_{n}.o")
+    reuse = set() if not only else {f"dexr_inst_{n}_{f64}_{mode}.o" for n in set(BUCKETS) - {int(v) for v in only.split(",")}
+                                    for f64, mode in VARIANTS}
+    jobs = []
+    objs = []
+    for name, source, flags in OBJECTS:
+        s, o = os.path.join(CSRC, source), os.path.join(BUILD, name)
         objs.append(o)
-        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp")] + HEADERS):
-            # the 16-row grid fits three waves per SIMD (168 VGPRs, 18 of them spilled; 11.8 KB of LDS per wave)
-            jobs.append((wide_s, o, NO_SLP + [f"-DDEXR_NMAX={n}"] + (["-DDEXR_WIDE_MINW=3"] if n == 16 else [])))
-    for n in (16, 24, 32):  # ... one frame per wave (SPRINT): the launch shape of small batches
-        o = os.path.join(BUILD, f"dexr_wide_s_{n}.o")
-        objs.append(o)
-        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp")] + HEADERS):
-            # (register budgets: two waves per SIMD for the 16- / 24-row grids (246 / 256 registers, 3 spilled at n = 24), one for
-            # the 32-row grid (272): small batches do not need the occupancy)
-            jobs.append((wide_s, o, NO_SLP + [f"-DDEXR_NMAX={n}", "-DDEXR_SPRINT=1", "-DDEXR_WIDE_MINW=1" if n == 32 else "-DDEXR_WIDE_MINW=2"]))
-    for tag, defs in (("s_m", ["-DDEXR_SPRINT=1"]), ("s_mc", ["-DDEXR_SPRINT=1", "-DDEXR_MODCHOL=1"])):  # ... on the variable grid
-        o = os.path.join(BUILD, f"dexr_wide_{tag}_16.o")
-        objs.append(o)
-        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp")] + HEADERS):
-            jobs.append((wide_s, o, NO_SLP + ["-DDEXR_NMAX=16", "-DDEXR_MIMIC=1"] + defs))
-    for tag, defs in (("m", []), ("mc", ["-DDEXR_MODCHOL=1"])):  # the same kernel on the grid of the optimised variables
-        o = os.path.join(BUILD, f"dexr_wide_{tag}_16.o")         # (mimic joints), plain / modified Cholesky
-        objs.append(o)
-        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp")] + HEADERS):
-            jobs.append((wide_s, o, NO_SLP + ["-DDEXR_NMAX=16", "-DDEXR_MIMIC=1"] + defs))
-    for tag, defs in (("16", ["-DDEXR_NMAX=16"]), ("24", ["-DDEXR_NMAX=24"]), ("m_16", ["-DDEXR_NMAX=16", "-DDEXR_MIMIC=1"]),
-                      ("mc_16", ["-DDEXR_NMAX=16", "-DDEXR_MIMIC=1", "-DDEXR_MODCHOL=1"])):
-        # ... its float64 instantiation (dexr_tuning.kernel_f64): one wave per SIMD, four frames per wave
-        o = os.path.join(BUILD, f"dexr_wide_d_{tag}.o")
-        objs.append(o)
-        if force or _stale(o, [wide_s, os.path.join(CSRC, "dexr_wide.hpp")] + HEADERS):
-            jobs.append((wide_s, o, NO_SLP + defs + ["-DDEXR_WIDE_F64=1"]))
-    red_s = os.path.join(CSRC, "dexr_red_inst.hip")
-    for nvb in (8, 16):  # reduced-variable kernel (mimic models): Hessian of the variables in registers
-        o = os.path.join(BUILD, f"dexr_red_{nvb}.o")
-        objs.append(o)
-        if force or _stale(o, [red_s, os.path.join(CSRC, "dexr_red.hpp")] + HEADERS):
-            jobs.append((red_s, o, NO_SLP + [f"-DDEXR_NV={nvb}"]))
-    for n, f64 in ((4, 0), (8, 0), (4, 1), (8, 1)):  # small components with fleet / sequence addressing (EXT)
-        o = os.path.join(BUILD, f"dexr_inst_ext_{n}_{f64}_0.o")
-        objs.append(o)
-        if force or _stale(o, [inst_s] + HEADERS):
-            jobs.append((inst_s, o, NO_SLP + [f"-DDEXR_NMAX={n}", f"-DDEXR_F64={f64}", "-DDEXR_MODE=0", "-DDEXR_EXT=1"]))
-    for n in CHAIN_BUCKETS:
-        o = os.path.join(BUILD, f"dexr_inst_ext_chain_{n}_0_0.o")
-        objs.append(o)
-        if force or _stale(o, [inst_s] + HEADERS):
-            jobs.append((inst_s, o, NO_SLP + [f"-DDEXR_NMAX={n}", "-DDEXR_F64=0", "-DDEXR_MODE=0", "-DDEXR_CHAIN=1", "-DDEXR_EXT=1"]))
-    for f64 in (0, 1):  # tip pass of the serial-chain kernel (dexr_tip.hpp): float32, and float64 (the reference's arithmetic)
-        for tag, defs in (("tip", []), ("ext_tip", ["-DDEXR_EXT=1"])):
-            o = os.path.join(BUILD, f"dexr_inst_{tag}_4_{f64}_0.o")
-            objs.append(o)
-            if force or _stale(o, [inst_s] + HEADERS):
-                jobs.append((inst_s, o, NO_SLP + ["-DDEXR_NMAX=4", f"-DDEXR_F64={f64}", "-DDEXR_MODE=0", "-DDEXR_CHAIN=1", "-DDEXR_TIP=1"] + defs))
-    tip32_s, tip32_o = os.path.join(CSRC, "dexr_tip_inst.hip"), os.path.join(BUILD, "dexr_tip32.o")
-    objs.append(tip32_o)  # the float32 tip solve as a kernel of its own (dexr_tip_solve.hpp): plain tile launches
-    if force or _stale(tip32_o, [tip32_s, os.path.join(CSRC, "dexr_tip_solve.hpp")] + HEADERS):
-        jobs.append((tip32_s, tip32_o, NO_SLP))
-    for n in CHAIN_BUCKETS:  # serial-chain specialisation, float32 solve only
-        o = os.path.join(BUILD, f"dexr_inst_chain_{n}_0_0.o")
-        objs.append(o)
-        if force or _stale(o, [inst_s] + HEADERS):
-            jobs.append((inst_s, o, NO_SLP + [f"-DDEXR_NMAX={n}", "-DDEXR_F64=0", "-DDEXR_MODE=0", "-DDEXR_CHAIN=1"]))
+        if name in reuse and os.path.exists(o):
+            continue
+        if force or _stale(o, _deps(s)):
+            jobs.append((s, o, flags))
 
     def compile_one(job):
         s, o, defs = job
@@ -193,7 +182,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
         return o
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), _pool_limit())) as ex:
             list(ex.map(compile_one, jobs))
     if force or jobs or _stale(LIB, objs):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"]
