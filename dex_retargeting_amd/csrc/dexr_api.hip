@@ -218,8 +218,6 @@ hipError_t dexr_fleet_dexpilot_order_launch(int64_t B, const float* kpts, const 
                                             int n_kp, const int32_t* h_task, const int32_t* h_origin, int F, float project_dist,
                                             float escape_dist, int32_t* xws, const int32_t** out_perm, const int32_t** out_seg,
                                             hipStream_t st);
-hipError_t dexr_lpt_order_launch(int64_t B, const float* f0, const float* sum, float ratio, int32_t* key, int32_t* ws, hipStream_t st);
-hipError_t dexr_tail_list_launch(int64_t B, int32_t* status, float* fval, int32_t* key, int32_t* ws, hipStream_t st);
 hipError_t dexr_dexpilot_order_launch(int64_t B, const float* kpts, const float* ref, const uint32_t* state, int n_kp, int n_ref,
                                       const int32_t* h_task, const int32_t* h_origin, int F, float project_dist, float escape_dist,
                                       int32_t* key, int32_t* ws, hipStream_t st);
@@ -234,7 +232,7 @@ bool wide_modchol_rule(const dexr_model* m) {
 
 // f64: the float64 instantiation (dexr_tuning.kernel_f64 = DEXR_KERNEL_WIDE) -- four frames per wave at every batch size, one
 // wave per SIMD, every step verified (no blind steps)
-int launch_wide_once(const dexr_model* m, dexr::KernelParams kp, hipStream_t st, bool tail_launch = false, bool f64 = false) {
+int launch_wide_once(const dexr_model* m, dexr::KernelParams kp, hipStream_t st, bool f64 = false) {
   const bool modchol = f64 ? wide_modchol_rule(m) : m->wide_modchol;
   const size_t per_wave = f64 ? (m->wide_mimic ? (modchol ? dexr::wide_lds_per_wave_d_mc_16() : dexr::wide_lds_per_wave_d_m_16())
                                                : (m->wbucket == 16 ? dexr::wide_lds_per_wave_d_16() : m->wbucket == 24 ? dexr::wide_lds_per_wave_d_24() : 0))
@@ -247,15 +245,14 @@ int launch_wide_once(const dexr_model* m, dexr::KernelParams kp, hipStream_t st,
   // ONE FRAME PER WAVE for small plain batches (dexr_wide.hpp SPRINT; dexr_tuning.sprint_max_batch):
   // with fewer frames than the chip has row slots a wave's four rows share one frame's term loop instead of idling
   const int64_t sprint_max = m->tune.sprint_max_batch < 0 ? 2048 : m->tune.sprint_max_batch;  // (measured: it wins up to ~2 048 frames = one wave per frame on every SIMD pair, profiles/r05_sprint_one_frame_per_wave.txt)
-  // (tail_launch: the second launch of a large batch, over the device-built list of the frames the first left unfinished)
   // (frame SEQUENCES included: a wave then walks one sequence's T frames with its four rows -- the offline retargeting of one
   // recorded hand is exactly "three rows idle")
   // (... and the buckets of a small FLEET batch: kp.B is then the whole batch, an upper bound of the bucket the kernel reads from
   // device memory -- several robots following one hand, hand_robot_viewer.py:134-181, is a batch of a few rows per model)
-  const bool sprint = !f64 && (tail_launch || (kp.B <= sprint_max && !kp.screen && kp.n_comp == 1));
+  const bool sprint = !f64 && kp.B <= sprint_max && kp.n_comp == 1;
   const int fpw = sprint ? 1 : 4;  // frames per wave
   {
-    const bool ladder = sprint && (tail_launch || m->tune.sprint_ladder != 0);  // (-1: policy = on; the tail launch always)
+    const bool ladder = sprint && m->tune.sprint_ladder != 0;  // (-1: policy = on)
     const float mu_on[4] = {0.03f, 0.3f, 3.f, 30.f};
     for (int r = 0; r < 4; ++r) kp.sprint_mu[r] = ladder ? mu_on[r] : 1.f;
     // THE LADDER TAKES NO BLIND STEPS (round 6).  "A nearly undamped Newton step below blind_tol is the answer" is safe on the
@@ -317,25 +314,21 @@ int launch_wide_once(const dexr_model* m, dexr::KernelParams kp, hipStream_t st,
 
 // LONGEST-FIRST ORDERING.  A launch over many more frames than the GPU holds at once (2 waves x 4 frames per SIMD) is
 // bound by slow frames the queue hands out late: Shadow DexPilot, 65 536 frames = 1.08 ms of throughput + 0.83 ms of
-// tail.  For DexPilot models the objective at the start point predicts the slow frames (top 5 %
-// by F(x0): 91 % of the frames with >= 15 iterations), so: (1) a screening launch of the same kernel evaluates F(x0)
-// (kinematics + terms, ~15 % of one solver pass per frame) and sums it, (2) frames above 1.3 x the batch mean get key 0,
-// the rest key 1, (3) the fleet bucketing kernels turn the keys into an index list, (4) the solve launch walks that
-// list.  Everything is stream-ordered on the caller's stream; the workspace is one of LSLOTS per-model buffers.
-// MEASURED (65 536 frames): with the frames sorted by their true iteration counts (a perfect predictor, tools/
-// prof_config.py DEXR_TOOL_LPT) Shadow DexPilot 1.87 -> 1.35-1.48 ms and LEAP DexPilot 1.21 -> 0.84-0.91 ms; with this
-// predictor the screening + ordering launches cost 0.15-0.25 ms and the frames it misses still run 20-34 passes:
-// Shadow 1.91 -> 2.04 ms, LEAP 1.23 -> 1.53 ms at ratio 2.  Hence opt-in (dexr_tuning.longest_first = 1), off by default;
-// position models have no usable predictor at all (F(x0), |g|, first step, curvature: <= 45 % of the slow frames in the
+// tail.  With the frames sorted by their true iteration counts (a perfect predictor, tools/
+// prof_config.py DEXR_TOOL_LPT) Shadow DexPilot runs 1.87 -> 1.35-1.48 ms and LEAP DexPilot 1.21 -> 0.84-0.91 ms.
+// For DexPilot models the PROJECTION STATE predicts the slow frames (dexr_aux.hip: dexpilot_key_kernel -- "a projection
+// bit changes in this frame": 3 % of the frames, 94 % of those with >= 24 passes; "a projection is active": 14 % /
+// 99.8 %): one elementwise kernel + the fleet bucketing kernels (~25 us) put those frames at the front of an index list,
+// and the solve launch walks that list.  That is the default for DexPilot batches large enough for the tail to matter
+// (dexr_tuning.longest_first = -1: automatic; 0: never; 2: the state keys at any size).  Everything is stream-ordered on
+// the caller's stream; the workspace is one of LSLOTS per-model buffers: key[B], then the bucketing workspace.
+// An earlier mode (1) took the keys from a screening launch that evaluated F(x0); its screening + ordering launches cost
+// more than the order gained (Shadow 1.91 -> 2.04 ms, LEAP 1.23 -> 1.53 ms at 65 536 frames), so it was retired.
+// Position models have no usable predictor at all (F(x0), |g|, first step, curvature: <= 45 % of the slow frames in the
 // top 20 %).
-// Round 4, second session: for DexPilot models the PROJECTION STATE predicts the slow frames better than F(x0) and costs
-// no screening launch (dexr_aux.hip: dexpilot_key_kernel -- "a projection bit changes in this frame": 3 % of the frames, 94 %
-// of those with >= 24 passes; "a projection is active": 14 % / 99.8 %): one elementwise kernel + the bucketing kernels
-// (~25 us) put those frames at the front of the index list.  That IS the default for DexPilot batches large enough for the
-// tail to matter (longest_first = -1: automatic; 0: never; 1: the F(x0) screening above; 2: the state keys at any size).
 size_t lpt_slot_bytes(int64_t B) {
   const size_t b = (size_t)B;
-  return 256 + b * sizeof(float) + b * sizeof(int32_t) + (dexr_fleet_ws_ints() + b) * sizeof(int32_t);
+  return b * sizeof(int32_t) + (dexr_fleet_ws_ints() + b) * sizeof(int32_t);
 }
 int lpt_slot_grow(dexr_model::LptSlot& sl, size_t bytes) {
   if (sl.bytes >= bytes) return DEXR_OK;
@@ -350,71 +343,20 @@ int lpt_slot_grow(dexr_model::LptSlot& sl, size_t bytes) {
   return DEXR_OK;
 }
 
-// TAIL LAUNCH (round 5; dexr_tuning.tail_passes).  A launch over many more frames than the chip holds is bound by its slowest
-// frames: 2-6 % of the frames of a tracking batch need two to six times the mean number of passes, and they finish on a chip
-// that is otherwise idle.  The first launch therefore stops every frame after P passes; the frames left with status MAXITER are
-// listed on the device (one elementwise kernel + the fleet's bucketing kernels) and a second launch in the one-frame-per-wave
-// shape (dexr_wide.hpp SPRINT) continues each from its accepted point with the ladder of damping values -- a pass costs less
-// there and the ladder needs about half as many.  Everything is stream-ordered on the caller's stream; the workspace is one of
-// the model's LSLOTS buffers (dexr_model_reserve sizes them).
-int launch_wide_tail(const dexr_model* m, dexr::KernelParams kp, int P, hipStream_t st) {
-  const size_t B = (size_t)kp.B;
-  const size_t bytes = lpt_slot_bytes(kp.B);
-  dexr_model::LptSlot& sl = m->lpt[m->lnext.fetch_add(1u) % dexr_model::LSLOTS];
-  if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-  else HIP_TRY(hipStreamWaitEvent(st, sl.done, 0));
-  { const int rc = lpt_slot_grow(sl, bytes); if (rc != DEXR_OK) return rc; }
-  unsigned char* base = static_cast<unsigned char*>(sl.buf);
-  int32_t* own_status = reinterpret_cast<int32_t*>(base + 256);  // (the screening values' place: unused on this path)
-  int32_t* key = reinterpret_cast<int32_t*>(base + 256 + B * sizeof(float));
-  int32_t* ws = key + B;
-  dexr::KernelParams k1 = kp;
-  k1.max_iter = P;
-  if (!k1.status) {
-    k1.status = own_status;
-    HIP_TRY(hipMemsetAsync(own_status, 0, B * sizeof(int32_t), st));
-  }
-  int rc = launch_wide_once(m, k1, st);
-  if (rc != DEXR_OK) return rc;
-  hipError_t e = dexr_tail_list_launch(kp.B, k1.status, kp.fval, key, ws, st);
-  if (e != hipSuccess) return fail(DEXR_ERR_HIP, "tail list kernels failed: %s", hipGetErrorString(e));
-  dexr::KernelParams k2 = kp;
-  k2.status = k1.status;
-  k2.perm = ws + dexr_fleet_ws_ints();
-  k2.bucket = ws + 2 * DEXR_FLEET_MAX_MODELS;
-  k2.x0 = kp.qout;  // continue from the accepted point the first launch wrote (the regularisation target stays `last`)
-  k2.iters_base = P;
-  rc = launch_wide_once(m, k2, st, true);
-  HIP_TRY(hipEventRecord(sl.done, st));
-  return rc;
-}
-
 int launch_wide(const dexr_model* m, dexr::KernelParams kp, hipStream_t st, bool f64 = false) {
   const int want = m->tune.longest_first;
   const bool plain = !kp.perm && !kp.bucket && kp.T == 0 && kp.n_comp == 1;
-  if (!f64) {  // (float64: one launch shape at every batch size -- no tail launch)
-    // (policy: OFF.  Measured, 65 536 tracking frames, profiles/r05_tail_launch.txt: LEAP position 1.106 ms in one launch,
-    // 1.18-1.29 ms with caps of 16 ... 6 passes; Shadow DexPilot 1.158 (hard frames first) -> 1.24-1.33.  The capped main launch is
-    // throughput-bound and gets barely shorter, while the handed-over frames then run at a quarter of the occupancy, after it.)
-    const int P = m->tune.tail_passes < 0 ? 0 : m->tune.tail_passes;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (plain && P > 0 && kp.max_iter > P && !kp.x0 && !kp.screen && kp.B >= 16384 &&
-        hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone)
-      return launch_wide_tail(m, kp, P, st);
-  }
   // (automatic: from 9 variables on -- measured on all 13 DexPilot configs, 65 536 frames: Shadow 1.35 -> 1.11 / 1.28 -> 1.07 ms,
   // LEAP 0.90 -> 0.78 / 0.87 -> 0.78, Allegro 0.71 -> 0.60 / 0.63 -> 0.62, SVH 0.93 -> 0.77 / 1.13 -> 1.07; the six-variable
   // Ability / Inspire hands lose 2-7 % to the ~25 us of ordering, their launches are not tail-bound)
   const bool by_state = plain && kp.kind == DEXR_KIND_DEXPILOT &&
                         (want == 2 || (want < 0 && kp.n_opt >= 9 && kp.B >= 4 * (int64_t)m->n_cu * 4 * 2 * 4));
-  const bool on = plain && (want == 1 || by_state);
-  if (!on) return launch_wide_once(m, kp, st, false, f64);
+  if (!by_state) return launch_wide_once(m, kp, st, f64);
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-    return launch_wide_once(m, kp, st, false, f64);  // graph capture: no allocation / cross-stream fencing inside a captured region --
+    return launch_wide_once(m, kp, st, f64);  // graph capture: no allocation / cross-stream fencing inside a captured region --
                                          // a captured graph runs the frames in natural order (same answers, the eager
                                          // call's schedule is the faster one for tail-bound batches; documented in dexr.h)
-  const size_t B = (size_t)kp.B;
   const size_t bytes = lpt_slot_bytes(kp.B);
   dexr_model::LptSlot& sl = m->lpt[m->lnext.fetch_add(1u) % dexr_model::LSLOTS];
   if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
@@ -423,28 +365,13 @@ int launch_wide(const dexr_model* m, dexr::KernelParams kp, hipStream_t st, bool
   // reservation the slot grows here -- hipMalloc on the first ordered call, hipEventSynchronize + hipFree + hipMalloc when a
   // larger batch arrives (the one place a `_dev` entry point may block; call dexr_model_reserve to rule it out).
   { const int rc = lpt_slot_grow(sl, bytes); if (rc != DEXR_OK) return rc; }
-  unsigned char* base = static_cast<unsigned char*>(sl.buf);
-  float* sum = reinterpret_cast<float*>(base);
-  float* f0 = reinterpret_cast<float*>(base + 256);
-  int32_t* key = reinterpret_cast<int32_t*>(base + 256 + B * sizeof(float));
-  int32_t* ws = key + B;
-  int rc = DEXR_OK;
-  if (by_state && want != 1) {
-    hipError_t e = dexr_dexpilot_order_launch(kp.B, kp.kpts, kp.ref, kp.state, kp.n_kp, kp.n_ref, kp.h_task, kp.h_origin, kp.num_fingers,
-                                              kp.project_dist, kp.escape_dist, key, ws, st);
-    if (e != hipSuccess) return fail(DEXR_ERR_HIP, "ordering kernels failed: %s", hipGetErrorString(e));
-  } else {
-    HIP_TRY(hipMemsetAsync(sum, 0, 256, st));
-    dexr::KernelParams ks = kp;
-    ks.screen = f0;
-    ks.screen_sum = sum;
-    rc = launch_wide_once(m, ks, st, false, f64);
-    if (rc != DEXR_OK) return rc;
-    hipError_t e = dexr_lpt_order_launch(kp.B, f0, sum, 1.3f, key, ws, st);
-    if (e != hipSuccess) return fail(DEXR_ERR_HIP, "ordering kernels failed: %s", hipGetErrorString(e));
-  }
+  int32_t* key = static_cast<int32_t*>(sl.buf);
+  int32_t* ws = key + kp.B;
+  hipError_t e = dexr_dexpilot_order_launch(kp.B, kp.kpts, kp.ref, kp.state, kp.n_kp, kp.n_ref, kp.h_task, kp.h_origin, kp.num_fingers,
+                                            kp.project_dist, kp.escape_dist, key, ws, st);
+  if (e != hipSuccess) return fail(DEXR_ERR_HIP, "ordering kernels failed: %s", hipGetErrorString(e));
   kp.perm = ws + dexr_fleet_ws_ints();
-  rc = launch_wide_once(m, kp, st, false, f64);
+  const int rc = launch_wide_once(m, kp, st, f64);
   HIP_TRY(hipEventRecord(sl.done, st));
   return rc;
 }
@@ -612,7 +539,7 @@ int launch(const dexr_model* m, int mode, int f64, dexr::KernelParams kp, hipStr
     // kernel (automatic policy only: dexr_tuning.kernel = DEXR_KERNEL_REDUCED keeps the reduced kernel at every size).
     // Like sprint_max_batch this makes the ITERATION a function of the batch size: same minimiser, same tolerance, and the
     // 16 384 / 16 385 straddle test (tests/test_gpu_all_configs.py) pins how often a multi-modal frame settles elsewhere.
-    if (fam == FAM_RED && m->wide_ok && m->tune.kernel == DEXR_KERNEL_AUTO && kp.B <= DEXR_RED_SMALL_BATCH && !kp.screen) fam = FAM_WIDE;
+    if (fam == FAM_RED && m->wide_ok && m->tune.kernel == DEXR_KERNEL_AUTO && kp.B <= DEXR_RED_SMALL_BATCH) fam = FAM_WIDE;
     kp.lam_jump = family_lam_jump(m, fam);
     kp.lam_fastdec = family_lam_fastdec(m, fam);
     return fam == FAM_RED ? launch_red(m, kp, st) : launch_wide(m, kp, st);
@@ -990,7 +917,6 @@ int dexr_prep_launch(int64_t B, const float* kp, const float* op9, float* out, f
 // dexr_aux.hip
 size_t dexr_fleet_ws_ints();
 hipError_t dexr_fleet_bucket_launch(int n_models, int64_t B, const int32_t* model_id, int32_t* ws, hipStream_t st);
-hipError_t dexr_lpt_order_launch(int64_t B, const float* f0, const float* sum, float ratio, int32_t* key, int32_t* ws, hipStream_t st);
 hipError_t dexr_dexpilot_order_launch(int64_t B, const float* kpts, const float* ref, const uint32_t* state, int n_kp, int n_ref,
                                       const int32_t* h_task, const int32_t* h_origin, int F, float project_dist, float escape_dist,
                                       int32_t* key, int32_t* ws, hipStream_t st);
@@ -1192,11 +1118,13 @@ int dexr_model_set_tuning(dexr_model* m, const dexr_tuning* tuning) {
     return fail(DEXR_ERR_INVALID, "unknown kernel family %d", t.kernel);
   if (t.pivot_rule < -1 || t.pivot_rule > 1) return fail(DEXR_ERR_INVALID, "unknown pivot rule %d", t.pivot_rule);
   if (t.chain < 0 || t.chain > 2) return fail(DEXR_ERR_INVALID, "chain must be 0 (never), 1 (serial-chain kernel + tip pass) or 2 (serial-chain kernel)");
-  if (t.longest_first < -1 || t.longest_first > 2) return fail(DEXR_ERR_INVALID, "longest_first must be -1, 0, 1 or 2");
+  if (t.longest_first == 1) return fail(DEXR_ERR_INVALID, "longest_first = 1 (the F(x0) screening order) is retired; use -1 (policy), 0 or 2");
+  if (t.longest_first < -1 || t.longest_first > 2) return fail(DEXR_ERR_INVALID, "longest_first must be -1, 0 or 2");
   if (t.fork_streams < -1 || t.fork_streams > 1) return fail(DEXR_ERR_INVALID, "fork_streams must be -1, 0 or 1");
   if (t.sprint_max_batch < -1) return fail(DEXR_ERR_INVALID, "sprint_max_batch must be -1 (policy), 0 (off) or a batch size");
   if (t.sprint_ladder < -1 || t.sprint_ladder > 1) return fail(DEXR_ERR_INVALID, "sprint_ladder must be -1, 0 or 1");
-  if (t.tail_passes < -1) return fail(DEXR_ERR_INVALID, "tail_passes must be -1 (policy), 0 (off) or a pass count");
+  if (t.tail_passes > 0) return fail(DEXR_ERR_INVALID, "tail_passes > 0 (the tail launch of large batches) is retired; use -1 (policy) or 0");
+  if (t.tail_passes < -1) return fail(DEXR_ERR_INVALID, "tail_passes must be -1 (policy) or 0");
   if (t.kernel_f64 != DEXR_KERNEL_AUTO && t.kernel_f64 != DEXR_KERNEL_REGISTER && t.kernel_f64 != DEXR_KERNEL_WIDE)
     return fail(DEXR_ERR_INVALID, "kernel_f64 must be DEXR_KERNEL_AUTO, DEXR_KERNEL_REGISTER or DEXR_KERNEL_WIDE (%d)", t.kernel_f64);
   if (t.kernel_f64 == DEXR_KERNEL_WIDE && m->tune.kernel_f64 != DEXR_KERNEL_WIDE) {
@@ -1695,8 +1623,7 @@ int dexr_retarget_multi_dev(const dexr_model* const* models, int32_t n_models, i
       // launch_wide's plain batches): its launch is the step's critical path and ends in the tail of exactly those frames.
       // Gate: the host never learns the bucket sizes, so the model's share is ESTIMATED as an even split B / n_models
       // -- a ~10 000-frame bucket of a 40 000-frame fleet does not pay ~25 us of key / bucketing / gather kernels for a launch
-      // that is not tail-bound; and only the state-key modes ask for it (longest_first -1: automatic, 2: always; 1 is the
-      // F(x0) screening mode of plain batches, 0 is off).
+      // that is not tail-bound; dexr_tuning.longest_first decides as for plain batches (-1: automatic, 2: always, 0: never).
       const int lf = m->tune.longest_first;
       if (!ordered_one && heavy && !m->gen && selected_family(m) == FAM_WIDE && m->h.kind == DEXR_KIND_DEXPILOT && m->h.n_opt >= 9 &&
           (lf == 2 || (lf < 0 && B / n_models >= 4 * (int64_t)m->n_cu * 4 * 2 * 4))) {

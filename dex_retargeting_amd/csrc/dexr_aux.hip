@@ -105,17 +105,8 @@ __global__ void __launch_bounds__(256) fleet_scatter_kernel(const int32_t* __res
   }
 }
 
-// Longest-first ordering of a batch (dexr_api.hip: launch_wide): key 0 = frame whose objective at the start point is
-// above `ratio` x the batch mean (it will need many solver passes), key 1 = everything else.
-__global__ void __launch_bounds__(256) lpt_key_kernel(const float* __restrict__ f0, const float* __restrict__ sum, int64_t B,
-                                                      float ratio, int32_t* __restrict__ key) {
-  const float thr = ratio * (*sum) / (float)B;
-  for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x)
-    key[b] = f0[b] > thr ? 0 : 1;
-}
-
-// Hard-frames-first keys of a DexPilot batch WITHOUT a screening launch (dexr_api.hip: launch_wide).  What makes a DexPilot
-// frame slow is the pinch projection (/root/reference/src/dex_retargeting/optimizer.py:462-508): a pair vector that is
+// Hard-frames-first keys of a DexPilot batch (dexr_api.hip: launch_wide).  What makes a DexPilot
+// frame slow is the pinch projection (the reference's optimizer.py:462-508): a pair vector that is
 // projected carries a 200-400 x weight and a target of fixed length, and the frame in which a projection switches on or off
 // jumps to a different objective.  Measured on the tracking workload (tools/probe_pred.py, 65 536 frames): "a projection bit
 // changed in this frame" flags 3 % of the frames and holds 94 % of those that need >= 24 solver passes (87 % of >= 16); "any
@@ -125,40 +116,46 @@ __global__ void __launch_bounds__(256) lpt_key_kernel(const float* __restrict__ 
 struct DexKeyMap {
   int32_t h_task[16], h_origin[16];  // keypoint indices of the first 16 reference rows (-1: the row is kp[h_task])
 };
+// length of reference row `row` of frame b, formed from the keypoints
+__device__ inline float dexpilot_kpt_dist(const float* __restrict__ kpts, int64_t b, int n_kp, const DexKeyMap& map, int row) {
+  const float* a = kpts + (b * n_kp + map.h_task[row]) * 3;
+  const int o = map.h_origin[row];
+  float v[3];
+  for (int i = 0; i < 3; ++i) v[i] = o >= 0 ? a[i] - kpts[(b * n_kp + o) * 3 + i] : a[i];
+  return sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+}
+// the projection pre-amble of one frame: the new state from the incoming one and the row lengths, and the key
+template <class DistOf>
+__device__ inline int32_t dexpilot_state_key(uint32_t st, int F, float project_dist, float escape_dist, DistOf dist_of) {
+  const int len_s1 = F - 1;
+  uint32_t nst = 0;
+  for (int i = 0; i < len_s1; ++i) {
+    const float d = dist_of(i);
+    bool on = (st >> i) & 1u;
+    if (d < project_dist) on = true;
+    if (d > escape_dist) on = false;
+    nst |= (on ? 1u : 0u) << i;
+  }
+  int idx = len_s1;
+  for (int a = 0; a < F - 2; ++a)
+    for (int b2 = a + 1; b2 < F - 1; ++b2) {
+      const bool on = ((nst >> b2) & 1u) && ((nst >> a) & 1u) && (dist_of(idx) <= 0.03f);
+      nst |= (on ? 1u : 0u) << idx;
+      ++idx;
+    }
+  return nst != st ? 0 : (nst != 0u ? 1 : 2);
+}
 __global__ void __launch_bounds__(256) dexpilot_key_kernel(const float* __restrict__ kpts, const float* __restrict__ ref,
                                                            const uint32_t* __restrict__ state, int64_t B, int n_kp, int n_ref,
                                                            DexKeyMap map, int F, float project_dist, float escape_dist,
                                                            int32_t* __restrict__ key) {
-  const int len_s1 = F - 1;
   for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) {
     auto dist_of = [&](int row) -> float {
-      float v[3];
-      if (kpts) {
-        const float* a = kpts + (b * n_kp + map.h_task[row]) * 3;
-        const int o = map.h_origin[row];
-        for (int i = 0; i < 3; ++i) v[i] = o >= 0 ? a[i] - kpts[(b * n_kp + o) * 3 + i] : a[i];
-      } else {
-        for (int i = 0; i < 3; ++i) v[i] = ref[(b * n_ref + row) * 3 + i];
-      }
+      if (kpts) return dexpilot_kpt_dist(kpts, b, n_kp, map, row);
+      const float* v = ref + (b * n_ref + row) * 3;
       return sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
     };
-    const uint32_t st = state ? state[b] : 0u;
-    uint32_t nst = 0;
-    for (int i = 0; i < len_s1; ++i) {
-      const float d = dist_of(i);
-      bool on = (st >> i) & 1u;
-      if (d < project_dist) on = true;
-      if (d > escape_dist) on = false;
-      nst |= (on ? 1u : 0u) << i;
-    }
-    int idx = len_s1;
-    for (int a = 0; a < F - 2; ++a)
-      for (int b2 = a + 1; b2 < F - 1; ++b2) {
-        const bool on = ((nst >> b2) & 1u) && ((nst >> a) & 1u) && (dist_of(idx) <= 0.03f);
-        nst |= (on ? 1u : 0u) << idx;
-        ++idx;
-      }
-    key[b] = nst != st ? 0 : (nst != 0u ? 1 : 2);
+    key[b] = dexpilot_state_key(state ? state[b] : 0u, F, project_dist, escape_dist, dist_of);
   }
 }
 
@@ -170,37 +167,14 @@ __global__ void __launch_bounds__(256) fleet_segment_key_kernel(const float* __r
                                                                 int64_t B, int n_kp, DexKeyMap map, int F, float project_dist,
                                                                 float escape_dist, int32_t* __restrict__ key) {
   const int64_t off = seg[0], cnt = seg[1];
-  const int len_s1 = F - 1;
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < B; p += (int64_t)gridDim.x * blockDim.x) {
     if (p >= cnt) {
       key[p] = -1;
       continue;
     }
     const int64_t b = perm[off + p];
-    auto dist_of = [&](int row) -> float {
-      const float* a = kpts + (b * n_kp + map.h_task[row]) * 3;
-      const int o = map.h_origin[row];
-      float v[3];
-      for (int i = 0; i < 3; ++i) v[i] = o >= 0 ? a[i] - kpts[(b * n_kp + o) * 3 + i] : a[i];
-      return sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    };
-    const uint32_t st = state[b];
-    uint32_t nst = 0;
-    for (int i = 0; i < len_s1; ++i) {
-      const float d = dist_of(i);
-      bool on = (st >> i) & 1u;
-      if (d < project_dist) on = true;
-      if (d > escape_dist) on = false;
-      nst |= (on ? 1u : 0u) << i;
-    }
-    int idx = len_s1;
-    for (int a = 0; a < F - 2; ++a)
-      for (int b2 = a + 1; b2 < F - 1; ++b2) {
-        const bool on = ((nst >> b2) & 1u) && ((nst >> a) & 1u) && (dist_of(idx) <= 0.03f);
-        nst |= (on ? 1u : 0u) << idx;
-        ++idx;
-      }
-    key[p] = nst != st ? 0 : (nst != 0u ? 1 : 2);
+    key[p] = dexpilot_state_key(state[b], F, project_dist, escape_dist,
+                                [&](int row) -> float { return dexpilot_kpt_dist(kpts, b, n_kp, map, row); });
   }
 }
 
@@ -285,17 +259,6 @@ hipError_t dexr_fleet_bucket_launch(int n_models, int64_t B, const int32_t* mode
   return hipGetLastError();
 }
 
-// keys from the screening launch's F(x0) values, then the index list (hard frames first) through the fleet bucketing
-// kernels; ws: the fleet workspace (perm at ws + dexr_fleet_ws_ints())
-hipError_t dexr_lpt_order_launch(int64_t B, const float* f0, const float* sum, float ratio, int32_t* key, int32_t* ws, hipStream_t st) {
-  const int64_t want = (B + 255) / 256;
-  const unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
-  hipLaunchKernelGGL(lpt_key_kernel, dim3(blocks), dim3(256), 0, st, f0, sum, B, ratio, key);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return dexr_fleet_bucket_launch(2, B, key, ws, st);
-}
-
 // DexPilot batches: keys from the projection state (dexpilot_key_kernel), then the index list through the bucketing kernels
 hipError_t dexr_dexpilot_order_launch(int64_t B, const float* kpts, const float* ref, const uint32_t* state, int n_kp, int n_ref,
                                       const int32_t* h_task, const int32_t* h_origin, int F, float project_dist, float escape_dist,
@@ -312,30 +275,6 @@ hipError_t dexr_dexpilot_order_launch(int64_t B, const float* kpts, const float*
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return dexr_fleet_bucket_launch(3, B, key, ws, st);
-}
-
-// TAIL LIST of a large batch (dexr_api.hip: launch_wide): the frames the first launch left at its pass cap (status MAXITER) become
-// the index list of the second, one-frame-per-wave launch; their status / final-value entries are cleared for it to set.
-namespace {
-__global__ void __launch_bounds__(256) tail_key_kernel(int32_t* __restrict__ status, float* __restrict__ fval, int64_t B,
-                                                       int32_t* __restrict__ key) {
-  for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) {
-    const bool tail = status[b] == 1;  // DEXR_STATUS_MAXITER
-    key[b] = tail ? 0 : -1;
-    if (tail) {
-      status[b] = 0;
-      if (fval) fval[b] = 0.f;
-    }
-  }
-}
-}  // namespace
-hipError_t dexr_tail_list_launch(int64_t B, int32_t* status, float* fval, int32_t* key, int32_t* ws, hipStream_t st) {
-  const int64_t want = (B + 255) / 256;
-  const unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
-  hipLaunchKernelGGL(tail_key_kernel, dim3(blocks), dim3(256), 0, st, status, fval, B, key);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return dexr_fleet_bucket_launch(1, B, key, ws, st);  // (key -1: skipped; bucket 0 = the tail, stable order)
 }
 
 // One DexPilot model's bucket of a fleet batch, hard frames first: extra workspace (int32) = key[B] | bucketing workspace

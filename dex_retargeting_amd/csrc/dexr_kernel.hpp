@@ -74,8 +74,8 @@ struct KernelParams {
   int32_t stall_from;             // termination at the float rounding floor (see "stalled" in the kernels): from this
   float stall_ratio;              // many unverifiable ("blind") steps on, a step that is not < stall_ratio x the
   float stall_cap;                // previous one and is < stall_cap x tol ends the solve
-  float* screen;                  // dexr_wide_kernel, screening launch: F(x0) per row (NULL: solve launch)
-  float* screen_sum;              //   and its sum over the batch
+  float* screen;                  // retired (always NULL, like screen_sum: the F(x0) screening launch of dexr_wide_kernel, whose
+  float* screen_sum;              // branch on it is dead); kept so that the offsets of the fields below stay put
   uint32_t q0;                    // queue mode: frames [0, q0) are handed out statically (wave w starts with tile w),
                                   // the queue counter numbers the frames from q0 on
   uint32_t qchunk;                // frames a wave takes from its component's queue per atomicAdd; 0 = tile mode
@@ -102,7 +102,7 @@ struct KernelParams {
   // rows -- {1, 1, 1, 1}: the rows are copies of one iteration; a ladder such as {0.03, 0.3, 3, 30}: every pass tries four
   // damping values from the accepted point and keeps the best acceptable trial point (dexr_tuning.sprint_ladder).
   float sprint_mu[4];
-  int32_t iters_base;  // passes a frame has already had in an earlier launch (the tail launch of a large batch continues the count)
+  int32_t iters_base;  // retired (always 0: the first pass count of the tail launch of large batches); kept so that the size stays put
 };
 
 // Per-component side table of the sixteen-lanes-per-frame kernel (dexr_wide.hpp), derived from the component's table by

@@ -1480,6 +1480,7 @@ __global__ void __launch_bounds__(256, F64 ? 1 : DEXR_WIDE_MINW) dexr_wide_kerne
     WPROF_STAGE(0)
     fk();
     WPROF_STAGE(1)
+    // DEAD (issue "Retire the tail launch and F(x0) screening order"): the host no longer sets kp.screen; cutting this branch cost dexr_wide_d_24 12 spilled VGPRs
     if (kp.screen) {
       // SCREENING launch (longest-first ordering, dexr_api.hip: launch_wide): F at the start point is all that is
       // wanted of a frame -- large values mark the frames that will need many passes (DexPilot models: the top 5 % by

@@ -99,12 +99,12 @@ typedef struct dexr_tuning {
                            the Rayleigh quotient of the failed step), 1 modified Cholesky (the pivot is reflected, the
                            step judged by the decrease and stretched to the trust radius; lam_jump scales mean diag H),
                            -1 measured policy (1 for DexPilot models with mimic joints)                             */
-  int32_t longest_first; /* sixteen-lane kernel, plain batches: hard frames first (a launch is otherwise bound by slow frames
-                           the queue hands out late).  2: DexPilot models, keys from the projection state -- a projection
-                           bit changes in this frame / a projection is active / neither -- one elementwise kernel, no
-                           screening launch; 1: a screening launch evaluates F at the start points, frames above 1.3 x the
-                           batch mean are solved first (costs more than it gains, see dexr_api.hip launch_wide); 0 off;
-                           -1 measured policy: the state keys for DexPilot batches of >= 32 768 frames, else off      */
+  int32_t longest_first; /* sixteen-lane kernel, plain batches of a DexPilot model: hard frames first (a launch is otherwise bound
+                           by slow frames the queue hands out late).  The keys come from the projection state -- a projection
+                           bit changes in this frame / a projection is active / neither -- by one elementwise kernel.  2: at
+                           any batch size; 0 off; -1 measured policy: batches of >= 32 768 frames, else off.  1 (keys from a
+                           screening launch that evaluated F at the start points) is retired -- it cost more than it gained,
+                           see dexr_api.hip launch_wide -- and refused with DEXR_ERR_INVALID                          */
   float lam_recover;    /* small components: accepted step with rho > 0.9 while lambda > 10 lambda0 and at most two steps of
                            the solve were rejected (the damping a rejection raised is being taken back): lambda *=
                            lam_recover.  0 (default): lam_fastdec there too.  Measured at 0.003 (65 536 tracking frames):
@@ -139,18 +139,14 @@ typedef struct dexr_tuning {
                            (the rows are copies of one iteration), -1 measured policy.  Round 6: with the ladder on EVERY
                            step is verified by an evaluation at the new point (no unverified last step); the pass that
                            confirms convergence costs kinematics + value only.                                          */
-  int32_t tail_passes;  /* sixteen-lane kernel, plain LARGE batches (>= 16 384 frames of a single-component model): the main launch
-                           stops every frame after this many passes; the few per cent still unfinished are listed on the device
-                           and handed to a second launch in the one-frame-per-wave shape with the ladder above -- a launch is
-                           otherwise bound by the passes of its slowest frames, on a chip that is idle by then.  Deterministic
-                           per frame (the cap is fixed), but the handed-over frames follow the ladder's iteration from where
-                           they stood.  0 off, > 0 the cap, -1 measured policy = OFF: at 65 536 frames the capped main launch
-                           is throughput-bound and barely shorter, the second launch comes on top (LEAP position 1.11 ->
-                           1.18-1.29 ms for caps of 16 ... 6; answers equal to 1e-6 rad either way)                      */
+  int32_t tail_passes;  /* retired: -1 or 0, anything else is refused with DEXR_ERR_INVALID; the field keeps its place in the
+                           struct.  It capped the passes of the main launch of a large batch and handed the unfinished frames to
+                           a second, one-frame-per-wave launch, which measured slower at every cap (65 536 frames: LEAP
+                           position 1.11 -> 1.18-1.29 ms, profiles/r05_tail_launch.txt)                              */
   int32_t kernel_f64;   /* family of the float64 SOLVE launches (precision = 1, dexr_retarget_f64, float64 sequences; the
                            polish pass keeps the register kernel).  DEXR_KERNEL_AUTO (default) / DEXR_KERNEL_REGISTER: the
                            register kernel.  DEXR_KERNEL_WIDE: the sixteen-lane kernel's float64 instantiation, four frames
-                           per wave at every batch size (no one-frame-per-wave shape, no tail launch: a frame's answer does
+                           per wave at every batch size (no one-frame-per-wave shape: a frame's answer does
                            not depend on the batch or its row); DEXR_ERR_UNSUPPORTED on a handle the sixteen-lane kernel
                            does not serve (dexr_model_lane_plan), on a generic-table model and on components of more than
                            24 joints without mimic joints.  Any other value: DEXR_ERR_INVALID.  Fleet batches stay float32. */
@@ -180,11 +176,12 @@ int dexr_model_kernel(const dexr_model* m, int32_t* family, int32_t* bucket, int
 int dexr_model_kernel_f64(const dexr_model* m, int32_t* family, int32_t* bucket);
 /* [not-in-ref] Pre-allocate what the `_dev` entry points would otherwise allocate lazily for batches of up to max_batch frames:
  * the hard-frames-first workspaces of the sixteen-lane kernel (dexr_tuning.longest_first; DexPilot batches of >= 32 768 frames
- * by default).  Without it the FIRST such call does a hipMalloc and a call with a larger batch than any before does
- * hipEventSynchronize + hipFree + hipMalloc -- the only place a `_dev` entry point may block on the host; after a reserve()
- * for the largest batch none does.  Under stream capture the ordering is skipped altogether (no allocation, no cross-stream
- * event inside a captured region): a captured graph walks the frames in natural order -- the same answers, bit for bit, on
- * the schedule of longest_first = 0.  No-op for models other kernels serve. */
+ * by default), each one key per frame plus the bucketing workspace that turns the keys into an index list.  Without it the
+ * FIRST such call does a hipMalloc and a call with a larger batch than any before does hipEventSynchronize + hipFree +
+ * hipMalloc -- the only place a `_dev` entry point may block on the host; after a reserve() for the largest batch none does.
+ * Under stream capture the ordering is skipped altogether (no allocation, no cross-stream event inside a captured region): a
+ * captured graph walks the frames in natural order -- the same answers, bit for bit, on the schedule of longest_first = 0.
+ * No-op for models other kernels serve. */
 int dexr_model_reserve(dexr_model* m, int64_t max_batch);
 /* Diagnostics: the lane plan of component `comp` for the sixteen-lane kernel -- chain_out[16][16]: lane l, step s ->
  * local joint (bit 7 set when that lane publishes the joint's frame, 0xFF: none); anc_rev_out[DEXR_MAXJ]: revolute
