@@ -54,6 +54,9 @@ EXPORTS = ["dexr_last_error", "dexr_version", "dexr_device_count", "dexr_default
 # include/dexr_pose.h (link poses and their VJP): a list of its own, EXPORTS mirrors dexr.h alone
 POSE_EXPORTS = ["dexr_pose_model_create", "dexr_pose_model_destroy", "dexr_pose_model_info", "dexr_link_poses_dev",
                 "dexr_link_poses_vjp_dev", "dexr_link_poses", "dexr_link_poses_vjp"]
+# include/dexr_jacobian.h (link Jacobians and link velocities on a pose table): again a list of its own
+JAC_EXPORTS = ["dexr_link_jacobians_dev", "dexr_link_velocities_dev", "dexr_link_jacobians", "dexr_link_velocities"]
+JAC_WORLD_ALIGNED, JAC_LOCAL = 0, 1  # DEXR_JAC_*
 UNIQUE_ID_BYTES = 128
 
 
@@ -127,6 +130,10 @@ def load() -> C.CDLL:
     lib.dexr_link_poses_vjp_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
     lib.dexr_link_poses.argtypes = [vp, i64, f64p, f64p, f64p, f64p]
     lib.dexr_link_poses_vjp.argtypes = [vp, i64, f64p, f64p, f64p, f64p, f64p]
+    lib.dexr_link_jacobians_dev.argtypes = [vp, i64, vp, vp, C.c_int32, vp, vp, vp]
+    lib.dexr_link_velocities_dev.argtypes = [vp, i64, vp, vp, vp, C.c_int32, vp, vp, vp]
+    lib.dexr_link_jacobians.argtypes = [vp, i64, f64p, f64p, C.c_int32, f64p, f64p]
+    lib.dexr_link_velocities.argtypes = [vp, i64, f64p, f64p, f64p, C.c_int32, f64p, f64p]
     _lib = lib
     return lib
 
@@ -398,6 +405,19 @@ class PoseModel:
         check(load().dexr_link_poses_vjp_dev(self._h, B, x_ptr or None, fixed_ptr or None, grad_pos_ptr or None,
                                              grad_rot_ptr or None, grad_x_ptr or None, stream or None))
 
+    def jacobians_dev(self, B: int, x_ptr: int, fixed_ptr: int, jlin_ptr: int, jang_ptr: int, frame: int = 0, stream: int = 0):
+        """x (B, n_in), fixed (B, n_fixed) or 0 -> jlin, jang (B, n_link, 3, n_in), either may be 0, every entry written
+        (dexr_link_jacobians_dev); frame: JAC_WORLD_ALIGNED or JAC_LOCAL."""
+        check(load().dexr_link_jacobians_dev(self._h, B, x_ptr or None, fixed_ptr or None, int(frame), jlin_ptr or None,
+                                             jang_ptr or None, stream or None))
+
+    def velocities_dev(self, B: int, x_ptr: int, fixed_ptr: int, xdot_ptr: int, lin_ptr: int, ang_ptr: int, frame: int = 0,
+                       stream: int = 0):
+        """x, xdot (B, n_in), fixed (B, n_fixed) or 0 -> lin, ang (B, n_link, 3), either may be 0
+        (dexr_link_velocities_dev)."""
+        check(load().dexr_link_velocities_dev(self._h, B, x_ptr or None, fixed_ptr or None, xdot_ptr or None, int(frame),
+                                              lin_ptr or None, ang_ptr or None, stream or None))
+
     # host-pointer entry points: float64 in, float64 arithmetic, float64 out ----------------------------
     def _host_inputs(self, x, fixed):
         x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float64)))
@@ -438,6 +458,27 @@ class PoseModel:
         check(load().dexr_link_poses_vjp(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), _ptr(grad_pos, C.c_double),
                                          _ptr(grad_rot, C.c_double), _ptr(gx, C.c_double)))
         return gx
+
+    def jacobians(self, x, fixed=None, frame: int = 0, angular: bool = True):
+        """-> jlin (B, n_link, 3, n_in), jang (the same shape) or None; float64 (dexr_link_jacobians)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        jlin = np.zeros((B, self.n_link, 3, self.n_in), dtype=np.float64)
+        jang = np.zeros((B, self.n_link, 3, self.n_in), dtype=np.float64) if angular else None
+        check(load().dexr_link_jacobians(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), int(frame),
+                                         _ptr(jlin, C.c_double), _ptr(jang, C.c_double)))
+        return jlin, jang
+
+    def velocities(self, x, xdot, fixed=None, frame: int = 0, angular: bool = True):
+        """-> lin (B, n_link, 3), ang (the same shape) or None; float64 (dexr_link_velocities)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        xdot = np.ascontiguousarray(np.atleast_2d(np.asarray(xdot, dtype=np.float64)))
+        if xdot.shape != x.shape:
+            raise ValueError(f"xdot must have the shape of x {x.shape}, got {xdot.shape}")
+        lin = np.zeros((B, self.n_link, 3), dtype=np.float64)
+        ang = np.zeros((B, self.n_link, 3), dtype=np.float64) if angular else None
+        check(load().dexr_link_velocities(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), _ptr(xdot, C.c_double),
+                                          int(frame), _ptr(lin, C.c_double), _ptr(ang, C.c_double)))
+        return lin, ang
 
 
 def seq_compose_dev(B: int, T: int, dof_kind, dof_idx, dof_mult, dof_off, n_opt: int, n_fixed: int, qraw_ptr: int,

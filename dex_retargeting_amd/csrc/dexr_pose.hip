@@ -21,6 +21,22 @@
 //   dL/dq_k = a_k . (T0 - o_k x F)   (revolute; a_k world axis, o_k world origin)        a_k . F   (prismatic),
 // then grad_x[col_k] (+)= mult_k dL/dq_k with plain loads / stores by the lane that owns the row (the first joint of a column
 // stores, later ones -- mimic joints of the same variable -- read, add, store; columns no joint reads are zeroed).
+//
+// LINK JACOBIANS and LINK VELOCITIES (include/dexr_jacobian.h).  The velocity kernel is the forward walk with the running
+// twist of the current joint frame beside the transform: v at the joint origin and w, carried to each new origin with
+// w x dp, saved with the transform at a fork (six more values per slot, [value][lane] behind the transform slots), and
+// at a joint driven by x advanced by mult xdot[col] a.  The Jacobian kernel has two phases in one block, because its
+// output (n_link x 3 x n_in values per frame and block) dwarfs everything else and a lane-per-frame store loop would put
+// kilobytes between the addresses of neighbouring lanes:
+//   phase A (lane = frame)   walks the joints once and parks a_k, o_k of every joint driven by x and p_l (local frame: and
+//                            R_l) of every link in LDS, laid out [lane][value] with an odd per-lane stride: a fixed value
+//                            over the lanes hits every bank once, and so do consecutive values of one frame;
+//   phase B (lane = element) after the barrier a lane owns the elements e, e + 256, ... of the (n_link, 3, n_in) block (the
+//                            block has four threads per frame; three quarters of it sit out phase A); an
+//                            element map built at create time gives (sorted link, row, column) of e without a division,
+//                            and a CSR list the joints feeding the column.  The lane loops over the frames of the block
+//                            (wave-uniform), sums mult (a x (p - o) | a) over the joints with link_begin <= l < sub_link_end
+//                            and stores: 64 consecutive floats per instruction.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -30,6 +46,7 @@
 
 #include "dexr.h"
 #include "dexr_math.hpp"
+#include "dexr_jacobian.h"
 #include "dexr_pose.h"
 
 int dexr_set_error(int code, const char* fmt, ...);  // dexr_api.hip
@@ -85,12 +102,11 @@ __device__ __forceinline__ void slot_load(const T* lds, int slot, int nl, int la
   for (int i = 0; i < 3; ++i) t.p[i] = s[(9 + i) * nl];
 }
 
-// one joint of the walk: t (transform of the previous joint, or of the fork this joint hangs off) -> transform of joint k;
-// `a` receives the world axis of the joint (its origin is the new t.p for a revolute joint)
+// the three parts of one joint of the walk.  joint_restore: t becomes the transform of the joint's parent (the running one,
+// the identity, or the fork's from its slot); joint_move: t -> transform of joint k, `a` receives the world axis of the joint
+// (its origin is the new t.p); the save of a fork's transform is joint_step's last line
 template <typename T>
-__device__ __forceinline__ void joint_step(const JointD<T>& J, const PoseArgs<T>& P, const T* __restrict__ x,
-                                           const T* __restrict__ fixed, int64_t b, T* slots, int nl, int lane, Xf<T>& t,
-                                           T a[3]) {
+__device__ __forceinline__ void joint_restore(const JointD<T>& J, const T* slots, int nl, int lane, Xf<T>& t) {
   if (J.restore == DEXR_POSE_ROOT) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) t.R[i] = (i % 4 == 0) ? T(1) : T(0);
@@ -98,6 +114,11 @@ __device__ __forceinline__ void joint_step(const JointD<T>& J, const PoseArgs<T>
   } else if (J.restore >= 0) {
     slot_load(slots, J.restore, nl, lane, t);
   }
+}
+
+template <typename T>
+__device__ __forceinline__ void joint_move(const JointD<T>& J, const PoseArgs<T>& P, const T* __restrict__ x,
+                                           const T* __restrict__ fixed, int64_t b, Xf<T>& t, T a[3]) {
   T q = J.off;
   if (J.src_kind == DEXR_POSE_SRC_X) q = fma(J.mult, x[b * P.n_in + J.src_col], J.off);
   else if (J.src_kind == DEXR_POSE_SRC_FIXED) q = fma(J.mult, fixed[b * P.n_fixed + J.src_col], J.off);
@@ -126,6 +147,15 @@ __device__ __forceinline__ void joint_step(const JointD<T>& J, const PoseArgs<T>
       n.R[3 * i + j] = fma(t.R[3 * i + 2], M[6 + j], fma(t.R[3 * i + 1], M[3 + j], t.R[3 * i] * M[j]));
   }
   t = n;
+}
+
+// one joint of the walk: t (transform of the previous joint, or of the fork this joint hangs off) -> transform of joint k
+template <typename T>
+__device__ __forceinline__ void joint_step(const JointD<T>& J, const PoseArgs<T>& P, const T* __restrict__ x,
+                                           const T* __restrict__ fixed, int64_t b, T* slots, int nl, int lane, Xf<T>& t,
+                                           T a[3]) {
+  joint_restore(J, slots, nl, lane, t);
+  joint_move(J, P, x, fixed, b, t, a);
   if (J.save >= 0) slot_store(slots, J.save, nl, lane, t);
 }
 
@@ -280,6 +310,244 @@ __global__ void __launch_bounds__(POSE_BLOCK) pose_vjp_kernel(const JointD<T>* _
   }
 }
 
+// ---- link velocities and link Jacobians (include/dexr_jacobian.h) ------------------------------------------------------
+// a joint driven by x as phase B of the Jacobian kernel reads it: one record per (column, joint), grouped by column (CSR)
+struct JacEnt {
+  int32_t xi;                    // index among the joints driven by x: where phase A parked a, o
+  int32_t link_begin, sub_end;   // sorted links below the joint
+  int32_t type;
+  double mult;
+  float multf;
+  int32_t pad;
+};
+__device__ __forceinline__ float mult_of(const JacEnt& e, float) { return e.multf; }
+__device__ __forceinline__ double mult_of(const JacEnt& e, double) { return e.mult; }
+
+// v (world axes) -> R^T v (the link's own axes)
+template <typename T>
+__device__ __forceinline__ void to_local(const T R[9], T v[3]) {
+  const T v0 = v[0], v1 = v[1], v2 = v[2];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) v[i] = fma(R[6 + i], v2, fma(R[3 + i], v1, R[i] * v0));
+}
+
+template <typename T>
+__global__ void __launch_bounds__(POSE_BLOCK) pose_velocity_kernel(const JointD<T>* __restrict__ joints, const LinkD<T>* __restrict__ links,
+                                                                   PoseArgs<T> P, const T* __restrict__ x, const T* __restrict__ fixed,
+                                                                   const T* __restrict__ xdot, int frame, T* __restrict__ lin,
+                                                                   T* __restrict__ ang) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pose_lds[];
+  const int nl = blockDim.x, lane = threadIdx.x;
+  T* slots = reinterpret_cast<T*>(pose_lds);
+  T* tw = slots + (size_t)P.n_slot * 12 * nl + lane;  // twist of the fork in slot s: tw[(6 s + i) nl], v then w
+  const int64_t b0 = (int64_t)blockIdx.x * nl + lane;
+  const bool live = b0 < P.B;
+  const int64_t b = live ? b0 : P.B - 1;
+  for (int l = 0; l < P.n_base; ++l) {  // links on the fixed base do not move
+    if (live) {
+      const int64_t o = (b * P.n_link + links[l].out) * 3;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        if (lin) lin[o + i] = T(0);
+        if (ang) ang[o + i] = T(0);
+      }
+    }
+  }
+  Xf<T> t;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) t.R[i] = (i % 4 == 0) ? T(1) : T(0);
+  t.p[0] = t.p[1] = t.p[2] = T(0);
+  T v[3] = {T(0), T(0), T(0)}, w[3] = {T(0), T(0), T(0)};  // velocity of the running frame's origin, angular velocity
+  for (int k = 0; k < P.n_joint; ++k) {
+    const JointD<T>& J = joints[k];
+    joint_restore(J, slots, nl, lane, t);
+    if (J.restore == DEXR_POSE_ROOT) {
+      v[0] = v[1] = v[2] = w[0] = w[1] = w[2] = T(0);
+    } else if (J.restore >= 0) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        v[i] = tw[(6 * J.restore + i) * nl];
+        w[i] = tw[(6 * J.restore + 3 + i) * nl];
+      }
+    }
+    const T po[3] = {t.p[0], t.p[1], t.p[2]};
+    T a[3];
+    joint_move(J, P, x, fixed, b, t, a);
+    {  // the parent body's velocity at the new origin
+      const T d0 = t.p[0] - po[0], d1 = t.p[1] - po[1], d2 = t.p[2] - po[2];
+      v[0] += w[1] * d2 - w[2] * d1;
+      v[1] += w[2] * d0 - w[0] * d2;
+      v[2] += w[0] * d1 - w[1] * d0;
+    }
+    if (J.src_kind == DEXR_POSE_SRC_X) {
+      const T qd = J.mult * xdot[b * P.n_in + J.src_col];
+      if (J.type == DEXR_POSE_REVOLUTE) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) w[i] = fma(qd, a[i], w[i]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) v[i] = fma(qd, a[i], v[i]);
+      }
+    }
+    if (J.save >= 0) {
+      slot_store(slots, J.save, nl, lane, t);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        tw[(6 * J.save + i) * nl] = v[i];
+        tw[(6 * J.save + 3 + i) * nl] = w[i];
+      }
+    }
+    for (int l = J.link_begin; l < J.link_end; ++l) {
+      const LinkD<T>& L = links[l];
+      T R[9], p[3];
+      link_pose(L, t, R, p);
+      const T d0 = p[0] - t.p[0], d1 = p[1] - t.p[1], d2 = p[2] - t.p[2];
+      T u[3] = {v[0] + (w[1] * d2 - w[2] * d1), v[1] + (w[2] * d0 - w[0] * d2), v[2] + (w[0] * d1 - w[1] * d0)};
+      T wl[3] = {w[0], w[1], w[2]};
+      if (frame == DEXR_JAC_LOCAL) {
+        to_local(R, u);
+        to_local(R, wl);
+      }
+      if (live) {
+        const int64_t o = (b * P.n_link + L.out) * 3;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          if (lin) lin[o + i] = u[i];
+          if (ang) ang[o + i] = wl[i];
+        }
+      }
+    }
+  }
+}
+
+// one joint's share of element (sorted link ls, row r) of the two blocks, from the values phase A parked for one frame
+// (added to the sums by value: a sum handed down by reference ends up in scratch)
+template <typename T>
+struct JacShare {
+  T lin, ang;
+};
+
+template <typename T>
+__device__ __forceinline__ JacShare<T> jac_share(const JacEnt& e, const T* pk, int lbase, int lstride, int ls, int r, int frame) {
+  JacShare<T> s = {T(0), T(0)};
+  if (ls < e.link_begin || ls >= e.sub_end) return s;
+  const T* a = pk + 6 * e.xi;               // a[0..2] world axis, a[3..5] world origin
+  const T* pl = pk + lbase + ls * lstride;  // p_l, then R_l row-major (local frame only)
+  const bool rev = e.type == DEXR_POSE_REVOLUTE;
+  T lin, ax;  // a x (p - o) and a, row r in the asked frame
+  if (frame == DEXR_JAC_WORLD_ALIGNED) {
+    ax = a[r];
+    lin = ax;
+    if (rev) {
+      const int r1 = r == 2 ? 0 : r + 1, r2 = r == 0 ? 2 : r - 1;
+      const T d1 = pl[r1] - a[3 + r1], d2 = pl[r2] - a[3 + r2];
+      lin = a[r1] * d2 - a[r2] * d1;
+    }
+  } else {
+    const T a0 = a[0], a1 = a[1], a2 = a[2];
+    const T R0 = pl[3 + r], R1 = pl[6 + r], R2 = pl[9 + r];  // column r of R_l
+    ax = fma(R2, a2, fma(R1, a1, R0 * a0));
+    lin = ax;
+    if (rev) {
+      const T d0 = pl[0] - a[3], d1 = pl[1] - a[4], d2 = pl[2] - a[5];
+      lin = fma(R2, a0 * d1 - a1 * d0, fma(R1, a2 * d0 - a0 * d2, R0 * (a1 * d2 - a2 * d1)));
+    }
+  }
+  const T m = mult_of(e, T(0));
+  s.lin = m * lin;
+  s.ang = rev ? m * ax : T(0);
+  return s;
+}
+
+// threads of a Jacobian block per frame it holds: phase A runs on the first quarter of the block (lane = frame), phase B on
+// all of it -- the LDS a block needs is set by its frames, so the three waves that sit out phase A cost none and are what
+// overlaps the LDS reads of phase B
+constexpr int JAC_FANOUT = 4;
+
+template <typename T>
+__global__ void __launch_bounds__(POSE_BLOCK * JAC_FANOUT) pose_jacobian_kernel(const JointD<T>* __restrict__ joints, const LinkD<T>* __restrict__ links,
+                                                                   PoseArgs<T> P, const int32_t* __restrict__ colptr,
+                                                                   const JacEnt* __restrict__ ents, const uint32_t* __restrict__ emap,
+                                                                   int n_jx, int stride, int frame, const T* __restrict__ x,
+                                                                   const T* __restrict__ fixed, T* __restrict__ jlin, T* __restrict__ jang) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pose_lds[];
+  const int nl = blockDim.x / JAC_FANOUT, lane = threadIdx.x;  // nl: frames of this block
+  T* slots = reinterpret_cast<T*>(pose_lds);
+  T* park = slots + (size_t)P.n_slot * 12 * nl;  // [lane][stride], stride odd
+  const int lstride = frame == DEXR_JAC_LOCAL ? 12 : 3, lbase = 6 * n_jx;
+  const int64_t first = (int64_t)blockIdx.x * nl;
+  if (lane < nl) {  // phase A: lane = frame
+    T* pk = park + (size_t)lane * stride;
+    const int64_t b = first + lane < P.B ? first + lane : P.B - 1;  // ragged tail: idle lanes park the last frame again
+    for (int l = 0; l < P.n_base; ++l) {
+      const LinkD<T>& L = links[l];
+      T* d = pk + lbase + l * lstride;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) d[i] = L.p[i];
+      if (frame == DEXR_JAC_LOCAL) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) d[3 + i] = L.R[i];
+      }
+    }
+    Xf<T> t;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) t.R[i] = (i % 4 == 0) ? T(1) : T(0);
+    t.p[0] = t.p[1] = t.p[2] = T(0);
+    int xi = 0;
+    for (int k = 0; k < P.n_joint; ++k) {
+      const JointD<T>& J = joints[k];
+      T a[3];
+      joint_step(J, P, x, fixed, b, slots, nl, lane, t, a);
+      if (J.src_kind == DEXR_POSE_SRC_X) {
+        T* d = pk + 6 * xi;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          d[i] = a[i];
+          d[3 + i] = t.p[i];
+        }
+        ++xi;
+      }
+      for (int l = J.link_begin; l < J.link_end; ++l) {
+        const LinkD<T>& L = links[l];
+        T R[9], p[3];
+        link_pose(L, t, R, p);
+        T* d = pk + lbase + l * lstride;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) d[i] = p[i];
+        if (frame == DEXR_JAC_LOCAL) {
+#pragma unroll
+          for (int i = 0; i < 9; ++i) d[3 + i] = R[i];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // phase B: lane = element of the (n_link, 3, n_in) block, frames of this block one after the other
+  const int E = P.n_link * 3 * P.n_in;
+  const int64_t left = P.B - first;
+  const int frames = left < nl ? (int)left : nl;
+  for (int e = lane; e < E; e += nl * JAC_FANOUT) {
+    const uint32_t u = emap[e];
+    const int ls = u & 63, r = (u >> 6) & 3, c = u >> 8;
+    const int i0 = colptr[c], i1 = colptr[c + 1];
+    JacEnt e0 = {0, 0, 0, 0, 0.0, 0.f, 0};  // the first joint of the column stays in registers over the frames (more: mimic joints)
+    if (i0 < i1) e0 = ents[i0];
+    for (int f = 0; f < frames; ++f) {
+      const T* pk = park + (size_t)f * stride;
+      const JacShare<T> s0 = jac_share(e0, pk, lbase, lstride, ls, r, frame);
+      T sl = s0.lin, sa = s0.ang;
+      for (int i = i0 + 1; i < i1; ++i) {
+        const JacShare<T> si = jac_share(ents[i], pk, lbase, lstride, ls, r, frame);
+        sl += si.lin;
+        sa += si.ang;
+      }
+      const int64_t o = (first + f) * E + e;
+      if (jlin) jlin[o] = sl;
+      if (jang) jang[o] = sa;
+    }
+  }
+}
+
 template <typename T>
 struct DevTables {
   JointD<T>* joints = nullptr;
@@ -294,6 +562,11 @@ struct dexr_pose_model {
   uint64_t unused[4] = {0, 0, 0, 0};
   DevTables<float> f32;
   DevTables<double> f64;
+  // index data of the Jacobian kernel, derived from the joint records at create time
+  int n_jx = 0;                // joints driven by x
+  int32_t* jac_colptr = nullptr;  // (n_in + 1)
+  JacEnt* jac_ents = nullptr;     // (n_jx), grouped by column
+  uint32_t* jac_emap = nullptr;   // (n_link 3 n_in): sorted link | row << 6 | column << 8 of an output element
 };
 
 namespace {
@@ -431,6 +704,82 @@ int launch_vjp(const dexr_pose_model* m, int64_t B, const T* x, const T* fixed, 
   return DEXR_OK;
 }
 
+// the Jacobian kernel's index data: the joints feeding each column of x (CSR, joints in walk order) and, per element of a
+// frame's (n_link, 3, n_in) output block, its sorted link, row and column
+hipError_t upload_jacobian_index(const dexr_pose_header& h, const std::vector<dexr_pose_joint>& js, const std::vector<dexr_pose_link>& ls,
+                                 dexr_pose_model* m) {
+  std::vector<int32_t> xi(js.size(), -1), colptr((size_t)h.n_in + 1, 0), sorted_of(ls.size(), 0);
+  int n_jx = 0;
+  for (size_t k = 0; k < js.size(); ++k)
+    if (js[k].src_kind == DEXR_POSE_SRC_X) xi[k] = n_jx++;
+  std::vector<JacEnt> ents;
+  for (int c = 0; c < h.n_in; ++c) {
+    for (size_t k = 0; k < js.size(); ++k) {
+      if (js[k].src_kind != DEXR_POSE_SRC_X || js[k].src_col != c) continue;
+      JacEnt e = {xi[k], js[k].link_begin, js[k].sub_link_end, js[k].type, js[k].mult, (float)js[k].mult, 0};
+      ents.push_back(e);
+    }
+    colptr[c + 1] = (int32_t)ents.size();
+  }
+  for (size_t l = 0; l < ls.size(); ++l) sorted_of[ls[l].out] = (int32_t)l;
+  std::vector<uint32_t> emap((size_t)h.n_link * 3 * h.n_in);
+  for (int lo = 0; lo < h.n_link; ++lo)
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < h.n_in; ++c)
+        emap[((size_t)lo * 3 + r) * h.n_in + c] = (uint32_t)sorted_of[lo] | ((uint32_t)r << 6) | ((uint32_t)c << 8);
+  m->n_jx = n_jx;
+  hipError_t e = hipMalloc((void**)&m->jac_colptr, colptr.size() * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&m->jac_ents, (ents.size() + 1) * sizeof(JacEnt));
+  if (e == hipSuccess) e = hipMalloc((void**)&m->jac_emap, (emap.size() + 1) * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemcpy(m->jac_colptr, colptr.data(), colptr.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !ents.empty()) e = hipMemcpy(m->jac_ents, ents.data(), ents.size() * sizeof(JacEnt), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !emap.empty()) e = hipMemcpy(m->jac_emap, emap.data(), emap.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  return e;
+}
+
+// checks shared by the four entry points of dexr_jacobian.h: < 0 error, 1 nothing to do, 0 go on
+int check_jacobian_call(const dexr_pose_model* m, int64_t B, const void* x, const void* fixed, int32_t frame, const void* out_a,
+                        const void* out_b) {
+  if (!m) return dexr_set_error(DEXR_ERR_INVALID, "null pose model");
+  if (B < 0) return dexr_set_error(DEXR_ERR_INVALID, "negative batch size");
+  if (frame != DEXR_JAC_WORLD_ALIGNED && frame != DEXR_JAC_LOCAL) return dexr_set_error(DEXR_ERR_INVALID, "unknown frame %d (0: world aligned, 1: local)", frame);
+  if (B == 0) return 1;
+  if (!out_a && !out_b) return dexr_set_error(DEXR_ERR_INVALID, "the linear and the angular output are both NULL");
+  return check_call(m, B, x, fixed);
+}
+
+template <typename T>
+int launch_velocities(const dexr_pose_model* m, int64_t B, const T* x, const T* fixed, const T* xdot, int frame, T* lin, T* ang,
+                      hipStream_t st) {
+  const size_t per_lane = (size_t)m->h.n_slot * 18 * sizeof(T);  // a fork keeps its twist beside its transform
+  const int nl = block_lanes(per_lane);
+  const int64_t blocks = (B + nl - 1) / nl;
+  if (blocks > 0x7fffffffLL) return dexr_set_error(DEXR_ERR_INVALID, "batch too large for one launch");
+  hipLaunchKernelGGL(pose_velocity_kernel<T>, dim3((unsigned)blocks), dim3(nl), per_lane * nl, st, (const JointD<T>*)tables_of<T>(m).joints,
+                     (const LinkD<T>*)tables_of<T>(m).links, args_of<T>(m, B), x, fixed, xdot, frame, lin, ang);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "link velocity kernel launch failed: %s", hipGetErrorString(e));
+  return DEXR_OK;
+}
+
+template <typename T>
+int launch_jacobians(const dexr_pose_model* m, int64_t B, const T* x, const T* fixed, int frame, T* jlin, T* jang, hipStream_t st) {
+  // values a lane parks for phase B: a, o per joint driven by x, p (local frame: and R) per link; odd, so that neither phase
+  // meets a bank twice
+  const int stride = (6 * m->n_jx + (frame == DEXR_JAC_LOCAL ? 12 : 3) * m->h.n_link) | 1;
+  const size_t per_lane = ((size_t)m->h.n_slot * 12 + (size_t)stride) * sizeof(T);
+  int nl = block_lanes(per_lane);
+  while (nl > 1 && per_lane * nl > 64 * 1024) nl /= 2;  // (float64, local frame, 64 joints and 64 links: 4 lanes)
+  const int64_t blocks = (B + nl - 1) / nl;
+  if (blocks > 0x7fffffffLL) return dexr_set_error(DEXR_ERR_INVALID, "batch too large for one launch");
+  hipLaunchKernelGGL(pose_jacobian_kernel<T>, dim3((unsigned)blocks), dim3(nl * JAC_FANOUT), per_lane * nl, st, (const JointD<T>*)tables_of<T>(m).joints,
+                     (const LinkD<T>*)tables_of<T>(m).links, args_of<T>(m, B), (const int32_t*)m->jac_colptr, (const JacEnt*)m->jac_ents,
+                     (const uint32_t*)m->jac_emap, m->n_jx, stride, frame, x, fixed, jlin, jang);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "link Jacobian kernel launch failed: %s", hipGetErrorString(e));
+  return DEXR_OK;
+}
+
 // device staging of the host-pointer entry points
 struct DevBuf {
   void* p = nullptr;
@@ -545,6 +894,7 @@ int dexr_pose_model_create(const void* blob, size_t nbytes, dexr_pose_model** ou
   build_tables<double>(h, js, ls, jd, ld);
   hipError_t e = upload(jf, lf, m->f32);
   if (e == hipSuccess) e = upload(jd, ld, m->f64);
+  if (e == hipSuccess) e = upload_jacobian_index(h, js, ls, m);
   if (e != hipSuccess) {
     dexr_pose_model_destroy(m);
     return dexr_set_error(DEXR_ERR_HIP, "uploading pose tables failed: %s", hipGetErrorString(e));
@@ -559,6 +909,9 @@ void dexr_pose_model_destroy(dexr_pose_model* m) {
   if (m->f32.links) (void)hipFree(m->f32.links);
   if (m->f64.joints) (void)hipFree(m->f64.joints);
   if (m->f64.links) (void)hipFree(m->f64.links);
+  if (m->jac_colptr) (void)hipFree(m->jac_colptr);
+  if (m->jac_ents) (void)hipFree(m->jac_ents);
+  if (m->jac_emap) (void)hipFree(m->jac_emap);
   delete m;
 }
 
@@ -626,6 +979,63 @@ int dexr_link_poses_vjp(const dexr_pose_model* m, int64_t B, const double* x, co
   if (rc) return rc;
   POSE_HIP(hipDeviceSynchronize());
   if (nx) POSE_HIP(hipMemcpy(grad_x_out, dgx.p, nx, hipMemcpyDeviceToHost));
+  return DEXR_OK;
+}
+
+// ---- include/dexr_jacobian.h -----------------------------------------------------------------------------------------------
+int dexr_link_jacobians_dev(const dexr_pose_model* m, int64_t B, const float* x, const float* fixed, int32_t frame, float* jlin_out,
+                            float* jang_out, void* stream) {
+  const int c = check_jacobian_call(m, B, x, fixed, frame, jlin_out, jang_out);
+  if (c) return c < 0 ? c : DEXR_OK;
+  return launch_jacobians<float>(m, B, x, fixed, frame, jlin_out, jang_out, (hipStream_t)stream);
+}
+
+int dexr_link_velocities_dev(const dexr_pose_model* m, int64_t B, const float* x, const float* fixed, const float* xdot,
+                             int32_t frame, float* lin_out, float* ang_out, void* stream) {
+  const int c = check_jacobian_call(m, B, x, fixed, frame, lin_out, ang_out);
+  if (c) return c < 0 ? c : DEXR_OK;
+  if (!xdot && m->h.n_in > 0) return dexr_set_error(DEXR_ERR_INVALID, "xdot is NULL");
+  return launch_velocities<float>(m, B, x, fixed, xdot, frame, lin_out, ang_out, (hipStream_t)stream);
+}
+
+int dexr_link_jacobians(const dexr_pose_model* m, int64_t B, const double* x, const double* fixed, int32_t frame, double* jlin_out,
+                        double* jang_out) {
+  const int c = check_jacobian_call(m, B, x, fixed, frame, jlin_out, jang_out);
+  if (c) return c < 0 ? c : DEXR_OK;
+  const size_t nx = (size_t)B * m->h.n_in * sizeof(double), nf = (size_t)B * m->h.n_fixed * sizeof(double);
+  const size_t nj = (size_t)B * m->h.n_link * 3 * m->h.n_in * sizeof(double);
+  DevBuf dx, dfix, dl, da;
+  POSE_HIP(dx.put(x, nx));
+  POSE_HIP(dfix.put(fixed, nf));
+  if (jlin_out) POSE_HIP(dl.put(nullptr, nj));
+  if (jang_out) POSE_HIP(da.put(nullptr, nj));
+  const int rc = launch_jacobians<double>(m, B, (const double*)dx.p, (const double*)dfix.p, frame, (double*)dl.p, (double*)da.p, nullptr);
+  if (rc) return rc;
+  POSE_HIP(hipDeviceSynchronize());
+  if (jlin_out && nj) POSE_HIP(hipMemcpy(jlin_out, dl.p, nj, hipMemcpyDeviceToHost));
+  if (jang_out && nj) POSE_HIP(hipMemcpy(jang_out, da.p, nj, hipMemcpyDeviceToHost));
+  return DEXR_OK;
+}
+
+int dexr_link_velocities(const dexr_pose_model* m, int64_t B, const double* x, const double* fixed, const double* xdot, int32_t frame,
+                         double* lin_out, double* ang_out) {
+  const int c = check_jacobian_call(m, B, x, fixed, frame, lin_out, ang_out);
+  if (c) return c < 0 ? c : DEXR_OK;
+  if (!xdot && m->h.n_in > 0) return dexr_set_error(DEXR_ERR_INVALID, "xdot is NULL");
+  const size_t nx = (size_t)B * m->h.n_in * sizeof(double), nf = (size_t)B * m->h.n_fixed * sizeof(double);
+  const size_t nv = (size_t)B * m->h.n_link * 3 * sizeof(double);
+  DevBuf dx, dfix, dxd, dl, da;
+  POSE_HIP(dx.put(x, nx));
+  POSE_HIP(dfix.put(fixed, nf));
+  POSE_HIP(dxd.put(xdot, nx));
+  if (lin_out) POSE_HIP(dl.put(nullptr, nv));
+  if (ang_out) POSE_HIP(da.put(nullptr, nv));
+  const int rc = launch_velocities<double>(m, B, (const double*)dx.p, (const double*)dfix.p, (const double*)dxd.p, frame, (double*)dl.p,
+                                           (double*)da.p, nullptr);
+  if (rc) return rc;
+  POSE_HIP(hipDeviceSynchronize());
+  if (lin_out) POSE_HIP(hipMemcpy(lin_out, dl.p, nv, hipMemcpyDeviceToHost));
+  if (ang_out) POSE_HIP(hipMemcpy(ang_out, da.p, nv, hipMemcpyDeviceToHost));
   return DEXR_OK;
 }
 

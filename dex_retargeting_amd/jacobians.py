@@ -1,0 +1,137 @@
+"""Batched link Jacobians and link velocities on the GPU (include/dexr_jacobian.h, csrc/dexr_pose.hip), for torch tensors.
+
+``link_jacobians(optimizer, q, link_names)`` gives ``J = d(pose)/dq`` of any links at the optimiser's variables -- the matrix a
+differential-IK or impedance step, a null-space projector, a manipulability measure or a contact Jacobian needs -- and
+``link_velocities`` the contraction ``J qdot`` without forming the matrix.  Both run one kernel per table of 64 links on the
+current torch stream.
+
+    jlin[b, l, :, c] = sum_k mult_k (a_k x (p_l - o_k) | a_k)        jang[b, l, :, c] = sum_k mult_k (a_k | 0)
+                                     revolute            prismatic                                  revolute prismatic
+
+over the joints k on the chain of link l that column c drives: a mimic joint lands on the column of its source with its
+multiplier.  ``frame="world"`` is the velocity of the link origin and the angular velocity in world axes (pinocchio's
+LOCAL_WORLD_ALIGNED), ``frame="local"`` rotates both into the link's own axes (pinocchio's LOCAL, what
+``RobotWrapper.compute_single_link_local_jacobian`` returns).
+
+The outputs carry NO autograd graph: they are first derivatives of the link poses, and their own derivative (the kinematic
+Hessian) is not built.  Differentiate through ``autograd.link_poses`` instead where a loss needs gradients.
+"""
+from __future__ import annotations
+
+from . import _lib
+from .autograd import _check_poses
+
+_FRAMES = {"world": _lib.JAC_WORLD_ALIGNED, "local": _lib.JAC_LOCAL}
+
+
+def _check(n_in, n_fixed, q, qdot, fixed_qpos, link_names, frame, kin, what="q"):
+    """Every argument rule -- the frame, types, dtypes, shapes, the link names and last the device -- before anything
+    touches the GPU.  Returns the DEXR_JAC_* value of `frame`.  `qdot`: False where the call takes none."""
+    import torch
+
+    if not isinstance(frame, str) or frame not in _FRAMES:
+        raise ValueError(f"frame must be 'world' or 'local', got {frame!r}")
+    if qdot is not False:
+        if not isinstance(qdot, torch.Tensor):
+            raise ValueError(f"the rate of {what} must be a torch tensor")
+        if qdot.dtype != torch.float32:
+            raise ValueError(f"the rate of {what} must be float32, got {qdot.dtype}")
+        if isinstance(q, torch.Tensor) and tuple(qdot.shape) != tuple(q.shape):
+            raise ValueError(f"the rate of {what} must have its shape {tuple(q.shape)}, got {tuple(qdot.shape)}")
+    if not isinstance(link_names, str):
+        for n in link_names:
+            kin.body_frame_index(n)  # ValueError on an unknown link
+    _check_poses(n_in, n_fixed, q, fixed_qpos, link_names, what=what)  # (ends with the device)
+    if qdot is not False and qdot.device != q.device:
+        raise ValueError(f"the rate is on {qdot.device}, {what} on {q.device}: all tensors must be on one CUDA device")
+    return _FRAMES[frame]
+
+
+def _chunks(names):
+    names = list(names)
+    return [names[c:c + 64] for c in range(0, len(names), 64)]
+
+
+def _cat(parts):
+    import torch
+
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+
+def _jacobians(model_of, x, fixed_qpos, link_names, frame, angular):
+    """chunks of 64 links -> one table and one launch each, results concatenated along the link axis."""
+    import torch
+
+    B = x.shape[0]
+    xc = x.detach().contiguous()
+    fixed = None if fixed_qpos is None or fixed_qpos.shape[1] == 0 else fixed_qpos.detach().contiguous()
+    lin, ang = [], []
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        for names in _chunks(link_names):
+            model = model_of(names)
+            jl = torch.empty((B, model.n_link, 3, model.n_in), dtype=torch.float32, device=x.device)
+            ja = torch.empty_like(jl) if angular else None
+            if B > 0:
+                model.jacobians_dev(B, xc.data_ptr(), 0 if fixed is None else fixed.data_ptr(), jl.data_ptr(),
+                                    0 if ja is None else ja.data_ptr(), frame=frame, stream=stream)
+            lin.append(jl)
+            ang.append(ja)
+    return _cat(lin), (_cat(ang) if angular else None)
+
+
+def _velocities(model_of, x, xdot, fixed_qpos, link_names, frame, angular):
+    import torch
+
+    B = x.shape[0]
+    xc, xd = x.detach().contiguous(), xdot.detach().contiguous()
+    fixed = None if fixed_qpos is None or fixed_qpos.shape[1] == 0 else fixed_qpos.detach().contiguous()
+    lin, ang = [], []
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        for names in _chunks(link_names):
+            model = model_of(names)
+            vl = torch.empty((B, model.n_link, 3), dtype=torch.float32, device=x.device)
+            va = torch.empty_like(vl) if angular else None
+            if B > 0:
+                model.velocities_dev(B, xc.data_ptr(), 0 if fixed is None else fixed.data_ptr(), xd.data_ptr(), vl.data_ptr(),
+                                     0 if va is None else va.data_ptr(), frame=frame, stream=stream)
+            lin.append(vl)
+            ang.append(va)
+    return _cat(lin), (_cat(ang) if angular else None)
+
+
+def link_jacobians(optimizer, q, link_names, fixed_qpos=None, frame="world", angular=True):
+    """Jacobians of `link_names` with respect to the optimiser's variables: q (B, n_opt) float32 CUDA -- what `retarget`
+    returns --, fixed_qpos (B, n_fixed) or None -> (jlin (B, L, 3, n_opt), jang of the same shape or None), float32.  Mimic
+    joints are folded onto their source's column; columns that move no joint above a link are exact zeros.
+    `angular=False` neither computes nor allocates `jang`.  The outputs carry no autograd graph (first derivatives; their
+    own derivative is not built)."""
+    n_fixed = len(optimizer.idx_pin2fixed)
+    f = _check(optimizer.opt_dof, n_fixed, q, False, fixed_qpos, link_names, frame, optimizer.robot.kin)
+    return _jacobians(optimizer.pose_model, q, fixed_qpos, link_names, f, angular)
+
+
+def link_velocities(optimizer, q, qdot, link_names, fixed_qpos=None, frame="world", angular=True):
+    """Velocities of `link_names` for the rate qdot (B, n_opt) of the optimiser's variables at q: (lin (B, L, 3) velocity of
+    the link origin, ang (B, L, 3) angular velocity or None), float32, = link_jacobians(...) @ qdot without the matrix.  Fixed
+    joints are held still.  No autograd graph."""
+    n_fixed = len(optimizer.idx_pin2fixed)
+    f = _check(optimizer.opt_dof, n_fixed, q, qdot, fixed_qpos, link_names, frame, optimizer.robot.kin)
+    return _velocities(optimizer.pose_model, q, qdot, fixed_qpos, link_names, f, angular)
+
+
+def robot_link_jacobians(robot, qpos, link_names, frame="world", angular=True):
+    """The same for a full robot qpos (B, robot.dof) in dof order: (jlin (B, L, 3, dof), jang or None).  Every joint is a
+    column of its own here, mimic joints included (RobotWrapper does not know about them)."""
+    f = _check(robot.dof, 0, qpos, False, None, link_names, frame, robot.kin, what="qpos")
+    return _jacobians(robot.pose_model, qpos, None, link_names, f, angular)
+
+
+def robot_link_velocities(robot, qpos, qvel, link_names, frame="world", angular=True):
+    """(lin (B, L, 3), ang or None) for a full robot qpos and its rate qvel, both (B, robot.dof) in dof order."""
+    f = _check(robot.dof, 0, qpos, qvel, None, link_names, frame, robot.kin, what="qpos")
+    return _velocities(robot.pose_model, qpos, qvel, None, link_names, f, angular)
+
+
+__all__ = ["link_jacobians", "link_velocities", "robot_link_jacobians", "robot_link_velocities"]

@@ -127,6 +127,20 @@ class RobotWrapper:
             out[:, c:c + 64, :3, 3] = pos
         return out
 
+    def link_jacobians(self, qpos: npt.NDArray, link_indices: Sequence[int], local: bool = True) -> np.ndarray:
+        """(B, nq) -> (B, L, 6, dof) float64 frame Jacobians of the given links (frame ids from get_link_index), rows 0-2
+        linear, 3-5 angular, from the device (dexr_link_jacobians: float64 arithmetic): the batched sibling of
+        compute_single_link_local_jacobian.  local=True is that function's LOCAL frame, False the world-aligned one."""
+        ids = [int(i) for i in link_indices]
+        q = np.atleast_2d(np.asarray(qpos, dtype=np.float64))
+        out = np.zeros((q.shape[0], len(ids), 6, self.dof), dtype=np.float64)
+        for c in range(0, len(ids), 64):
+            names = [self.kin.frames[self.kin.body_of_frame_id(i)].name for i in ids[c:c + 64]]
+            jlin, jang = self.pose_model(names).jacobians(q, frame=_lib.JAC_LOCAL if local else _lib.JAC_WORLD_ALIGNED)
+            out[:, c:c + 64, :3] = jlin
+            out[:, c:c + 64, 3:] = jang
+        return out
+
     def get_link_pose(self, link_id: int) -> npt.NDArray:
         """4x4 pose of one link at the configuration last given to compute_forward_kinematics.  The translation comes
         from the device path (that is all the retargeting objectives read, optimizer.py:157-159,260,521); the rotation
