@@ -37,8 +37,8 @@ def _inst(n: int, f64: int, *defs: str) -> list:
 _INST, _WIDE = "dexr_inst.hip", "dexr_wide_inst.hip"
 _MIMIC, _MODCHOL, _SPRINT = "-DDEXR_MIMIC=1", "-DDEXR_MODCHOL=1", "-DDEXR_SPRINT=1"
 # Everything libdexr.so is made of, in link order: (object file, source file, flags after FLAGS).  Host-side units first;
-# dexr_pose is the link poses + their VJP (include/dexr_pose.h) and the link Jacobians / velocities (include/dexr_jacobian.h):
-# a unit of its own, in no workload's source hash.
+# dexr_pose is the link poses + their VJP (include/dexr_pose.h), the link Jacobians / velocities (include/dexr_jacobian.h) and
+# the link wrenches / velocity VJP (include/dexr_wrench.h): a unit of its own, in no workload's source hash.
 OBJECTS = [(f"dexr_{u}.o", f"dexr_{u}.hip", []) for u in ("api", "prep", "aux", "comm", "pose")]
 OBJECTS += [("dexr_gen.o", "dexr_gen_inst.hip", [])]
 # register kernel of small components, biggest first so the thread pool stays busy (jobs start in table order);

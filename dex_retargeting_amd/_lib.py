@@ -57,6 +57,8 @@ POSE_EXPORTS = ["dexr_pose_model_create", "dexr_pose_model_destroy", "dexr_pose_
 # include/dexr_jacobian.h (link Jacobians and link velocities on a pose table): again a list of its own
 JAC_EXPORTS = ["dexr_link_jacobians_dev", "dexr_link_velocities_dev", "dexr_link_jacobians", "dexr_link_velocities"]
 JAC_WORLD_ALIGNED, JAC_LOCAL = 0, 1  # DEXR_JAC_*
+# include/dexr_wrench.h (J^T on a pose table: link wrenches and the VJP of the link velocities): a list of its own
+WRENCH_EXPORTS = ["dexr_link_wrenches_dev", "dexr_link_velocities_vjp_dev", "dexr_link_wrenches", "dexr_link_velocities_vjp"]
 UNIQUE_ID_BYTES = 128
 
 
@@ -134,6 +136,10 @@ def load() -> C.CDLL:
     lib.dexr_link_velocities_dev.argtypes = [vp, i64, vp, vp, vp, C.c_int32, vp, vp, vp]
     lib.dexr_link_jacobians.argtypes = [vp, i64, f64p, f64p, C.c_int32, f64p, f64p]
     lib.dexr_link_velocities.argtypes = [vp, i64, f64p, f64p, f64p, C.c_int32, f64p, f64p]
+    lib.dexr_link_wrenches_dev.argtypes = [vp, i64, vp, vp, C.c_int32, vp, vp, vp, vp]
+    lib.dexr_link_velocities_vjp_dev.argtypes = [vp, i64, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
+    lib.dexr_link_wrenches.argtypes = [vp, i64, f64p, f64p, C.c_int32, f64p, f64p, f64p]
+    lib.dexr_link_velocities_vjp.argtypes = [vp, i64, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p]
     _lib = lib
     return lib
 
@@ -418,6 +424,21 @@ class PoseModel:
         check(load().dexr_link_velocities_dev(self._h, B, x_ptr or None, fixed_ptr or None, xdot_ptr or None, int(frame),
                                               lin_ptr or None, ang_ptr or None, stream or None))
 
+    def wrenches_dev(self, B: int, x_ptr: int, fixed_ptr: int, force_ptr: int, torque_ptr: int, tau_ptr: int, frame: int = 0,
+                     stream: int = 0):
+        """force, torque (B, n_link, 3), either may be 0 -> tau (B, n_in) = J^T (force, torque), every entry written
+        (dexr_link_wrenches_dev)."""
+        check(load().dexr_link_wrenches_dev(self._h, B, x_ptr or None, fixed_ptr or None, int(frame), force_ptr or None,
+                                            torque_ptr or None, tau_ptr or None, stream or None))
+
+    def velocities_vjp_dev(self, B: int, x_ptr: int, fixed_ptr: int, xdot_ptr: int, grad_lin_ptr: int, grad_ang_ptr: int,
+                           grad_x_ptr: int, grad_xdot_ptr: int, frame: int = 0, stream: int = 0):
+        """cotangents grad_lin, grad_ang (B, n_link, 3) of velocities_dev's outputs, either may be 0 -> grad_x, grad_xdot
+        (B, n_in), either may be 0 (dexr_link_velocities_vjp_dev)."""
+        check(load().dexr_link_velocities_vjp_dev(self._h, B, x_ptr or None, fixed_ptr or None, xdot_ptr or None, int(frame),
+                                                  grad_lin_ptr or None, grad_ang_ptr or None, grad_x_ptr or None,
+                                                  grad_xdot_ptr or None, stream or None))
+
     # host-pointer entry points: float64 in, float64 arithmetic, float64 out ----------------------------
     def _host_inputs(self, x, fixed):
         x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float64)))
@@ -479,6 +500,39 @@ class PoseModel:
         check(load().dexr_link_velocities(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), _ptr(xdot, C.c_double),
                                           int(frame), _ptr(lin, C.c_double), _ptr(ang, C.c_double)))
         return lin, ang
+
+    def _host_link_rows(self, a, B, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (B, self.n_link, 3):
+            raise ValueError(f"{what} must have shape ({B}, {self.n_link}, 3), got {a.shape}")
+        return a
+
+    def wrenches(self, x, fixed=None, force=None, torque=None, frame: int = 0):
+        """-> tau (B, n_in) float64 (dexr_link_wrenches); at least one of force, torque (B, n_link, 3) is required."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        force, torque = self._host_link_rows(force, B, "force"), self._host_link_rows(torque, B, "torque")
+        tau = np.zeros((B, self.n_in), dtype=np.float64)
+        check(load().dexr_link_wrenches(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), int(frame),
+                                        _ptr(force, C.c_double), _ptr(torque, C.c_double), _ptr(tau, C.c_double)))
+        return tau
+
+    def velocities_vjp(self, x, xdot, fixed=None, grad_lin=None, grad_ang=None, frame: int = 0, want_x: bool = True,
+                       want_xdot: bool = True):
+        """-> (grad_x, grad_xdot) (B, n_in) float64, None where not wanted (dexr_link_velocities_vjp); at least one of
+        grad_lin, grad_ang (B, n_link, 3) is required."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        xdot = np.ascontiguousarray(np.atleast_2d(np.asarray(xdot, dtype=np.float64)))
+        if xdot.shape != x.shape:
+            raise ValueError(f"xdot must have the shape of x {x.shape}, got {xdot.shape}")
+        grad_lin, grad_ang = self._host_link_rows(grad_lin, B, "grad_lin"), self._host_link_rows(grad_ang, B, "grad_ang")
+        gx = np.zeros((B, self.n_in), dtype=np.float64) if want_x else None
+        gxd = np.zeros((B, self.n_in), dtype=np.float64) if want_xdot else None
+        check(load().dexr_link_velocities_vjp(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), _ptr(xdot, C.c_double),
+                                              int(frame), _ptr(grad_lin, C.c_double), _ptr(grad_ang, C.c_double),
+                                              _ptr(gx, C.c_double), _ptr(gxd, C.c_double)))
+        return gx, gxd
 
 
 def seq_compose_dev(B: int, T: int, dof_kind, dof_idx, dof_mult, dof_off, n_opt: int, n_fixed: int, qraw_ptr: int,

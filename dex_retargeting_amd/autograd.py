@@ -16,7 +16,10 @@ zero gradients.
 
 The task-space half: ``link_poses(optimizer, q, link_names)`` gives positions and rotations of any links at q
 (``dexr_link_poses_dev``) and back-propagates through them with the closed-form VJP kernel (``dexr_link_poses_vjp_dev``), so
-``keypoints -> retarget -> link_poses -> loss -> backward`` stays on the GPU.
+``keypoints -> retarget -> link_poses -> loss -> backward`` stays on the GPU.  ``link_velocities(optimizer, q, qdot,
+link_names)`` does the same for the link velocities J(q) qdot: the forward is ``jacobians.link_velocities``, the backward one
+kernel per 64 links (``dexr_link_velocities_vjp_dev``, include/dexr_wrench.h) that gives the gradient in qdot (J^T applied to
+the cotangents) and in q (the kinematic Hessian contracted on both sides) without forming a matrix.
 """
 from __future__ import annotations
 
@@ -277,4 +280,99 @@ def robot_link_poses(robot, qpos, link_names, rotations=True):
     return _link_poses(robot.pose_model, qpos, None, link_names, rotations)
 
 
-__all__ = ["retarget", "ref_value_from_keypoints", "link_poses", "robot_link_poses"]
+# ---- task space: link velocities of (q, qdot), differentiable in both ----------------------------------------------------
+def _make_velocity_function():
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _LinkVelocities(torch.autograd.Function):
+        """One chunk of at most 64 links (one pose table).  Saves x, xdot (and fixed): the VJP kernel recomputes the walk."""
+
+        @staticmethod
+        def forward(ctx, x, xdot, fixed_qpos, model, frame, angular):
+            B = x.shape[0]
+            xc, xd = x.detach().contiguous(), xdot.detach().contiguous()
+            fixed = None if fixed_qpos is None or fixed_qpos.shape[1] == 0 else fixed_qpos.detach().contiguous()
+            lin = torch.empty((B, model.n_link, 3), dtype=torch.float32, device=x.device)
+            ang = torch.empty_like(lin) if angular else None
+            if B > 0:
+                model.velocities_dev(B, xc.data_ptr(), 0 if fixed is None else fixed.data_ptr(), xd.data_ptr(), lin.data_ptr(),
+                                     0 if ang is None else ang.data_ptr(), frame=frame,
+                                     stream=torch.cuda.current_stream(x.device).cuda_stream)
+            ctx.model, ctx.frame = model, frame
+            ctx.has_fixed = fixed is not None
+            ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None -> NULL for the kernel
+            ctx.save_for_backward(*([xc, xd] + ([fixed] if fixed is not None else [])))
+            if ang is None:
+                return lin
+            return lin, ang
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_lin, grad_ang=None):
+            want_x, want_xd = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            if not (want_x or want_xd) or (grad_lin is None and grad_ang is None):
+                return None, None, None, None, None, None
+            saved = list(ctx.saved_tensors)
+            x, xd = saved[0], saved[1]
+            fixed = saved[2] if ctx.has_fixed else None
+            B = x.shape[0]
+            gl = None if grad_lin is None else grad_lin.detach().to(torch.float32).contiguous()
+            ga = None if grad_ang is None else grad_ang.detach().to(torch.float32).contiguous()
+            gx = torch.empty_like(x) if want_x else None  # (the kernel writes every entry)
+            gxd = torch.empty_like(x) if want_xd else None
+            if B > 0:
+                ctx.model.velocities_vjp_dev(B, x.data_ptr(), 0 if fixed is None else fixed.data_ptr(), xd.data_ptr(),
+                                             0 if gl is None else gl.data_ptr(), 0 if ga is None else ga.data_ptr(),
+                                             0 if gx is None else gx.data_ptr(), 0 if gxd is None else gxd.data_ptr(),
+                                             frame=ctx.frame, stream=torch.cuda.current_stream(x.device).cuda_stream)
+            return gx, gxd, None, None, None, None
+
+    return _LinkVelocities
+
+
+_VEL_FN = None
+
+
+def _link_velocities(model_of, x, xdot, fixed_qpos, link_names, frame, angular):
+    """chunks of 64 links -> one table each, results concatenated along the link axis (autograd sums the chunks' gradients)."""
+    global _VEL_FN
+    import torch
+
+    if _VEL_FN is None:
+        _VEL_FN = _make_velocity_function()
+    names = list(link_names)
+    lin, ang = [], []
+    with torch.cuda.device(x.device):
+        for c in range(0, len(names), 64):
+            out = _VEL_FN.apply(x, xdot, fixed_qpos, model_of(names[c:c + 64]), frame, bool(angular))
+            if angular:
+                lin.append(out[0])
+                ang.append(out[1])
+            else:
+                lin.append(out)
+    if len(lin) == 1:
+        return lin[0], (ang[0] if angular else None)
+    return torch.cat(lin, dim=1), (torch.cat(ang, dim=1) if angular else None)
+
+
+def link_velocities(optimizer, q, qdot, link_names, fixed_qpos=None, frame="world", angular=True):
+    """`jacobians.link_velocities` with an autograd graph: (lin (B, L, 3), ang (B, L, 3) or None) of `link_names` for the rate
+    qdot (B, n_opt) at q (B, n_opt), the same bits, and gradients flow to q and to qdot (not to fixed_qpos; once
+    differentiable).  `frame="local"` expresses the velocities -- and hence their cotangents -- in the link's own axes."""
+    from . import jacobians
+
+    n_fixed = len(optimizer.idx_pin2fixed)
+    f = jacobians._check(optimizer.opt_dof, n_fixed, q, qdot, fixed_qpos, link_names, frame, optimizer.robot.kin)
+    return _link_velocities(optimizer.pose_model, q, qdot, fixed_qpos, link_names, f, angular)
+
+
+def robot_link_velocities(robot, qpos, qvel, link_names, frame="world", angular=True):
+    """The same for a full robot qpos and its rate qvel, both (B, robot.dof) float32 in dof order."""
+    from . import jacobians
+
+    f = jacobians._check(robot.dof, 0, qpos, qvel, None, link_names, frame, robot.kin, what="qpos")
+    return _link_velocities(robot.pose_model, qpos, qvel, None, link_names, f, angular)
+
+
+__all__ = ["retarget", "ref_value_from_keypoints", "link_poses", "robot_link_poses", "link_velocities", "robot_link_velocities"]

@@ -37,6 +37,16 @@
 //                            and a CSR list the joints feeding the column.  The lane loops over the frames of the block
 //                            (wave-uniform), sums mult (a x (p - o) | a) over the joints with link_begin <= l < sub_link_end
 //                            and stores: 64 consecutive floats per instruction.
+//
+// LINK WRENCHES and the VJP of the LINK VELOCITIES (include/dexr_wrench.h): J^T applied to per-link cotangents, and the
+// kinematic Hessian contracted on both sides, again without a matrix.  One kernel, two forms (pose_wrench_kernel<T, VEL>):
+//   wrench form (VEL = false)  the pose VJP's two sweeps with other cargo: sweep 1 parks f_l and p_l x f_l + m_l (6 values per
+//                              sorted link, [value][lane]), sweep 2 sums the range below each joint and projects it;
+//   VJP form    (VEL = true)   both sweeps are the velocity walk (18 values per fork slot); sweep 1 parks f_l, m_l, p_l x f_l and
+//                              A_l = v_l x f_l + w_l x m_l (12 values per link; 9 in the local frame, where A_l = 0), sweep 2
+//                              takes both gradients of a joint from the five range sums and its own twist.
+// The rate gradient of the VJP form is the wrench form's arithmetic operation by operation (rate_grad, cross_fma: explicit
+// fma, nothing left to contraction), so the two agree bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -48,6 +58,7 @@
 #include "dexr_math.hpp"
 #include "dexr_jacobian.h"
 #include "dexr_pose.h"
+#include "dexr_wrench.h"
 
 int dexr_set_error(int code, const char* fmt, ...);  // dexr_api.hip
 
@@ -420,6 +431,216 @@ __global__ void __launch_bounds__(POSE_BLOCK) pose_velocity_kernel(const JointD<
   }
 }
 
+// ---- link wrenches and the VJP of the link velocities (include/dexr_wrench.h) ------------------------------------------------
+// R v (the link's own axes -> world axes)
+template <typename T>
+__device__ __forceinline__ void to_world(const T R[9], T v[3]) {
+  const T v0 = v[0], v1 = v[1], v2 = v[2];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) v[i] = fma(R[3 * i + 2], v2, fma(R[3 * i + 1], v1, R[3 * i] * v0));
+}
+
+// c = a x b with the roundings spelled out (both forms of the kernel must round alike)
+template <typename T>
+__device__ __forceinline__ void cross_fma(const T a[3], const T b[3], T c[3]) {
+  c[0] = fma(a[1], b[2], -(a[2] * b[1]));
+  c[1] = fma(a[2], b[0], -(a[0] * b[2]));
+  c[2] = fma(a[0], b[1], -(a[1] * b[0]));
+}
+
+template <typename T>
+__device__ __forceinline__ T dot_fma(const T a[3], const T b[3]) {
+  return fma(a[2], b[2], fma(a[1], b[1], a[0] * b[0]));
+}
+
+// dL/dqd of one joint from the sums over the links below it: F = sum f, M = sum (p x f + m); oxF = o x F
+template <typename T>
+__device__ __forceinline__ T rate_grad(int type, const T a[3], const T F[3], const T M[3], const T oxF[3]) {
+  if (type != DEXR_POSE_REVOLUTE) return dot_fma(a, F);
+  const T r[3] = {M[0] - oxF[0], M[1] - oxF[1], M[2] - oxF[2]};
+  return dot_fma(a, r);
+}
+
+// the lane that owns row b adds a joint's share to its column: the first joint of a column stores, later ones (mimic joints
+// of the same variable) read, add, store
+template <typename T>
+__device__ __forceinline__ void column_add(T* __restrict__ row, int col, int first, T g) {
+  T* dst = row + col;
+  if (first) *dst = g;
+  else *dst = *dst + g;
+}
+
+// one joint of the velocity walk: joint_step with the twist (v at the running origin, w) carried, advanced and saved along
+template <typename T>
+__device__ __forceinline__ void joint_step_twist(const JointD<T>& J, const PoseArgs<T>& P, const T* __restrict__ x,
+                                                 const T* __restrict__ fixed, const T* __restrict__ xdot, int64_t b, T* slots,
+                                                 T* tw, int nl, int lane, Xf<T>& t, T a[3], T v[3], T w[3]) {
+  joint_restore(J, slots, nl, lane, t);
+  if (J.restore == DEXR_POSE_ROOT) {
+    v[0] = v[1] = v[2] = w[0] = w[1] = w[2] = T(0);
+  } else if (J.restore >= 0) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      v[i] = tw[(6 * J.restore + i) * nl];
+      w[i] = tw[(6 * J.restore + 3 + i) * nl];
+    }
+  }
+  const T po[3] = {t.p[0], t.p[1], t.p[2]};
+  joint_move(J, P, x, fixed, b, t, a);
+  const T d[3] = {t.p[0] - po[0], t.p[1] - po[1], t.p[2] - po[2]};
+  T wd[3];
+  cross_fma(w, d, wd);  // the parent body's velocity at the new origin
+#pragma unroll
+  for (int i = 0; i < 3; ++i) v[i] += wd[i];
+  if (J.src_kind == DEXR_POSE_SRC_X) {
+    const T qd = J.mult * xdot[b * P.n_in + J.src_col];
+    if (J.type == DEXR_POSE_REVOLUTE) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) w[i] = fma(qd, a[i], w[i]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) v[i] = fma(qd, a[i], v[i]);
+    }
+  }
+  if (J.save >= 0) {
+    slot_store(slots, J.save, nl, lane, t);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      tw[(6 * J.save + i) * nl] = v[i];
+      tw[(6 * J.save + 3 + i) * nl] = w[i];
+    }
+  }
+}
+
+// VEL = false: tau = sum_l Jlin_l^T gl_l + Jang_l^T ga_l -> gxd (xdot and gx are not touched).
+// VEL = true:  the VJP of (lin, ang) = link velocities at (x, xdot) for the cotangents (gl, ga): gx (never NULL here: a call
+//              that asks for the rate gradient alone is served by the wrench form) and gxd (may be NULL).
+template <typename T, bool VEL>
+__global__ void __launch_bounds__(POSE_BLOCK) pose_wrench_kernel(const JointD<T>* __restrict__ joints, const LinkD<T>* __restrict__ links,
+                                                                 PoseArgs<T> P, const T* __restrict__ x, const T* __restrict__ fixed,
+                                                                 const T* __restrict__ xdot, int frame, const T* __restrict__ gl,
+                                                                 const T* __restrict__ ga, T* __restrict__ gx, T* __restrict__ gxd) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pose_lds[];
+  const int nl = blockDim.x, lane = threadIdx.x;
+  const bool local = frame == DEXR_JAC_LOCAL;
+  const int per_link = VEL ? (local ? 9 : 12) : 6;  // f, then p x f + m (wrench form) | m, p x f, A (VJP form; no A in the local frame)
+  T* slots = reinterpret_cast<T*>(pose_lds);
+  T* tw = slots + (size_t)P.n_slot * 12 * nl + lane;                     // VJP form: twist of the fork in slot s, v then w
+  T* park = slots + (size_t)P.n_slot * (VEL ? 18 : 12) * nl + lane;      // record of sorted link l: park[(per_link l + i) nl]
+  const int64_t b0 = (int64_t)blockIdx.x * nl + lane;
+  const bool live = b0 < P.B;
+  const int64_t b = live ? b0 : P.B - 1;  // ragged tail: idle lanes recompute the last frame and store nothing
+  Xf<T> t;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) t.R[i] = (i % 4 == 0) ? T(1) : T(0);
+  t.p[0] = t.p[1] = t.p[2] = T(0);
+  T v[3] = {T(0), T(0), T(0)}, w[3] = {T(0), T(0), T(0)};
+  // sweep 1: per link the cotangents as a force and a moment in world axes, and what sweep 2 needs of the link beside them
+  for (int k = 0; k < P.n_joint; ++k) {
+    const JointD<T>& J = joints[k];
+    T a[3];
+    if (VEL) joint_step_twist(J, P, x, fixed, xdot, b, slots, tw, nl, lane, t, a, v, w);
+    else joint_step(J, P, x, fixed, b, slots, nl, lane, t, a);
+    for (int l = J.link_begin; l < J.link_end; ++l) {
+      const LinkD<T>& L = links[l];
+      T R[9], p[3], f[3] = {T(0), T(0), T(0)}, m[3] = {T(0), T(0), T(0)}, c[3];
+      link_pose(L, t, R, p);
+      const int64_t o = (b * P.n_link + L.out) * 3;
+      if (gl) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) f[i] = gl[o + i];
+        if (local) to_world(R, f);
+      }
+      if (ga) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) m[i] = ga[o + i];
+        if (local) to_world(R, m);
+      }
+      cross_fma(p, f, c);
+      T* rec = park + (size_t)per_link * l * nl;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) rec[i * nl] = f[i];
+      if (!VEL) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) rec[(3 + i) * nl] = c[i] + m[i];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          rec[(3 + i) * nl] = m[i];
+          rec[(6 + i) * nl] = c[i];
+        }
+        if (!local) {  // A_l = v_l x f_l + w_l x m_l, v_l the velocity of the link origin
+          const T d[3] = {p[0] - t.p[0], p[1] - t.p[1], p[2] - t.p[2]};
+          T u[3], uf[3], wm[3];
+          cross_fma(w, d, u);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) u[i] += v[i];
+          cross_fma(u, f, uf);
+          cross_fma(w, m, wm);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) rec[(9 + i) * nl] = uf[i] + wm[i];
+        }
+      }
+    }
+  }
+  // columns of x that no joint reads: zero gradient
+  for (int c = 0; c < P.n_in; ++c) {
+    const uint64_t u = c < 64 ? P.unused_lo : (c < 128 ? P.unused_hi : (c < 192 ? P.unused_2 : P.unused_3));
+    if (((u >> (c & 63)) & 1ull) && live) {
+      if (VEL) gx[b * P.n_in + c] = T(0);
+      if (gxd) gxd[b * P.n_in + c] = T(0);
+    }
+  }
+  // sweep 2: per joint the sums over the links below it, projected on the joint's motion and on its motion's rate of change
+  for (int k = 0; k < P.n_joint; ++k) {
+    const JointD<T>& J = joints[k];
+    T a[3];
+    if (VEL) joint_step_twist(J, P, x, fixed, xdot, b, slots, tw, nl, lane, t, a, v, w);
+    else joint_step(J, P, x, fixed, b, slots, nl, lane, t, a);
+    if (J.src_kind != DEXR_POSE_SRC_X) continue;
+    T F[3] = {T(0), T(0), T(0)}, M[3] = {T(0), T(0), T(0)};                             // sum f, sum (p x f + m)
+    T G[3] = {T(0), T(0), T(0)}, C[3] = {T(0), T(0), T(0)}, A[3] = {T(0), T(0), T(0)};  // VJP form: sum m, sum p x f, sum A
+    for (int l = J.link_begin; l < J.sub_link_end; ++l) {
+      const T* rec = park + (size_t)per_link * l * nl;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        F[i] += rec[i * nl];
+        if (!VEL) {
+          M[i] += rec[(3 + i) * nl];
+        } else {
+          const T mi = rec[(3 + i) * nl], ci = rec[(6 + i) * nl];
+          M[i] += ci + mi;
+          G[i] += mi;
+          C[i] += ci;
+          if (!local) A[i] += rec[(9 + i) * nl];
+        }
+      }
+    }
+    T oxF[3];
+    cross_fma(t.p, F, oxF);
+    if (gxd) {
+      const T g = J.mult * rate_grad(J.type, a, F, M, oxF);
+      if (live) column_add(gxd + b * P.n_in, J.src_col, J.first_of_col, g);
+    }
+    if (VEL) {
+      T wa[3], g;
+      cross_fma(w, a, wa);
+      if (J.type == DEXR_POSE_REVOLUTE) {
+        T vf[3], wg[3];
+        cross_fma(v, F, vf);
+        cross_fma(w, G, wg);
+        const T r[3] = {A[0] - vf[0] - wg[0], A[1] - vf[1] - wg[1], A[2] - vf[2] - wg[2]};
+        const T arm[3] = {C[0] - oxF[0], C[1] - oxF[1], C[2] - oxF[2]};
+        g = dot_fma(a, r) + dot_fma(wa, arm);
+      } else {
+        g = dot_fma(wa, F);
+      }
+      g *= J.mult;
+      if (live) column_add(gx + b * P.n_in, J.src_col, J.first_of_col, g);
+    }
+  }
+}
+
 // one joint's share of element (sorted link ls, row r) of the two blocks, from the values phase A parked for one frame
 // (added to the sums by value: a sum handed down by reference ends up in scratch)
 template <typename T>
@@ -780,6 +1001,43 @@ int launch_jacobians(const dexr_pose_model* m, int64_t B, const T* x, const T* f
   return DEXR_OK;
 }
 
+// checks shared by the four entry points of dexr_wrench.h: < 0 error, 1 nothing to do, 0 go on
+int check_wrench_call(const dexr_pose_model* m, int64_t B, const void* x, const void* fixed, int32_t frame, const void* in_a,
+                      const void* in_b, const void* out_a, const void* out_b) {
+  if (!m) return dexr_set_error(DEXR_ERR_INVALID, "null pose model");
+  if (B < 0) return dexr_set_error(DEXR_ERR_INVALID, "negative batch size");
+  if (frame != DEXR_JAC_WORLD_ALIGNED && frame != DEXR_JAC_LOCAL) return dexr_set_error(DEXR_ERR_INVALID, "unknown frame %d (0: world aligned, 1: local)", frame);
+  if (B == 0) return 1;
+  if (!in_a && !in_b) return dexr_set_error(DEXR_ERR_INVALID, "the linear and the angular input are both NULL");
+  if (!out_a && !out_b) return dexr_set_error(DEXR_ERR_INVALID, "every output is NULL");
+  return check_call(m, B, x, fixed);
+}
+
+// gx == NULL: the wrench form (xdot is not read); otherwise the VJP form, gxd may be NULL
+template <typename T>
+int launch_wrench(const dexr_pose_model* m, int64_t B, const T* x, const T* fixed, const T* xdot, int frame, const T* gl, const T* ga,
+                  T* gx, T* gxd, hipStream_t st) {
+  const bool vel = gx != nullptr;
+  const size_t per_link = vel ? (frame == DEXR_JAC_LOCAL ? 9 : 12) : 6;
+  const size_t per_lane = ((size_t)m->h.n_slot * (vel ? 18 : 12) + (size_t)m->h.n_link * per_link) * sizeof(T);
+  const int nl = block_lanes(per_lane);
+  if (per_lane * nl > 64 * 1024)
+    return dexr_set_error(DEXR_ERR_UNSUPPORTED, "the table needs %zu B of LDS per frame: %d frames do not fit one block", per_lane, nl);
+  const int64_t blocks = (B + nl - 1) / nl;
+  if (blocks > 0x7fffffffLL) return dexr_set_error(DEXR_ERR_INVALID, "batch too large for one launch");
+  const JointD<T>* js = tables_of<T>(m).joints;
+  const LinkD<T>* ls = tables_of<T>(m).links;
+  if (vel)
+    hipLaunchKernelGGL((pose_wrench_kernel<T, true>), dim3((unsigned)blocks), dim3(nl), per_lane * nl, st, js, ls, args_of<T>(m, B), x, fixed,
+                       xdot, frame, gl, ga, gx, gxd);
+  else
+    hipLaunchKernelGGL((pose_wrench_kernel<T, false>), dim3((unsigned)blocks), dim3(nl), per_lane * nl, st, js, ls, args_of<T>(m, B), x, fixed,
+                       xdot, frame, gl, ga, gx, gxd);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "link wrench kernel launch failed: %s", hipGetErrorString(e));
+  return DEXR_OK;
+}
+
 // device staging of the host-pointer entry points
 struct DevBuf {
   void* p = nullptr;
@@ -798,6 +1056,28 @@ struct DevBuf {
     hipError_t e_ = (expr);                                                                                    \
     if (e_ != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
+
+// the float64 host twin of both entry-point pairs of dexr_wrench.h: copy, run, synchronise
+int host_wrench(const dexr_pose_model* m, int64_t B, const double* x, const double* fixed, const double* xdot, int32_t frame,
+                const double* gl, const double* ga, double* gx_out, double* gxd_out) {
+  const size_t nx = (size_t)B * m->h.n_in * sizeof(double), nf = (size_t)B * m->h.n_fixed * sizeof(double);
+  const size_t nv = (size_t)B * m->h.n_link * 3 * sizeof(double);
+  DevBuf dx, dfix, dxd, dl, da, dgx, dgxd;
+  POSE_HIP(dx.put(x, nx));
+  POSE_HIP(dfix.put(fixed, nf));
+  if (gx_out) POSE_HIP(dxd.put(xdot, nx));
+  if (gl) POSE_HIP(dl.put(gl, nv));
+  if (ga) POSE_HIP(da.put(ga, nv));
+  if (gx_out) POSE_HIP(dgx.put(nullptr, nx));
+  if (gxd_out) POSE_HIP(dgxd.put(nullptr, nx));
+  const int rc = launch_wrench<double>(m, B, (const double*)dx.p, (const double*)dfix.p, (const double*)dxd.p, frame, (const double*)dl.p,
+                                       (const double*)da.p, (double*)dgx.p, (double*)dgxd.p, nullptr);
+  if (rc) return rc;
+  POSE_HIP(hipDeviceSynchronize());
+  if (gx_out && nx) POSE_HIP(hipMemcpy(gx_out, dgx.p, nx, hipMemcpyDeviceToHost));
+  if (gxd_out && nx) POSE_HIP(hipMemcpy(gxd_out, dgxd.p, nx, hipMemcpyDeviceToHost));
+  return DEXR_OK;
+}
 
 }  // namespace
 
@@ -1037,6 +1317,38 @@ int dexr_link_velocities(const dexr_pose_model* m, int64_t B, const double* x, c
   if (lin_out) POSE_HIP(hipMemcpy(lin_out, dl.p, nv, hipMemcpyDeviceToHost));
   if (ang_out) POSE_HIP(hipMemcpy(ang_out, da.p, nv, hipMemcpyDeviceToHost));
   return DEXR_OK;
+}
+
+// ---- include/dexr_wrench.h -------------------------------------------------------------------------------------------------
+int dexr_link_wrenches_dev(const dexr_pose_model* m, int64_t B, const float* x, const float* fixed, int32_t frame, const float* force,
+                           const float* torque, float* tau_out, void* stream) {
+  const int c = check_wrench_call(m, B, x, fixed, frame, force, torque, tau_out, nullptr);
+  if (c) return c < 0 ? c : DEXR_OK;
+  return launch_wrench<float>(m, B, x, fixed, nullptr, frame, force, torque, nullptr, tau_out, (hipStream_t)stream);
+}
+
+int dexr_link_velocities_vjp_dev(const dexr_pose_model* m, int64_t B, const float* x, const float* fixed, const float* xdot,
+                                 int32_t frame, const float* grad_lin, const float* grad_ang, float* grad_x_out, float* grad_xdot_out,
+                                 void* stream) {
+  const int c = check_wrench_call(m, B, x, fixed, frame, grad_lin, grad_ang, grad_x_out, grad_xdot_out);
+  if (c) return c < 0 ? c : DEXR_OK;
+  if (grad_x_out && !xdot && m->h.n_in > 0) return dexr_set_error(DEXR_ERR_INVALID, "xdot is NULL");
+  return launch_wrench<float>(m, B, x, fixed, xdot, frame, grad_lin, grad_ang, grad_x_out, grad_xdot_out, (hipStream_t)stream);
+}
+
+int dexr_link_wrenches(const dexr_pose_model* m, int64_t B, const double* x, const double* fixed, int32_t frame, const double* force,
+                       const double* torque, double* tau_out) {
+  const int c = check_wrench_call(m, B, x, fixed, frame, force, torque, tau_out, nullptr);
+  if (c) return c < 0 ? c : DEXR_OK;
+  return host_wrench(m, B, x, fixed, nullptr, frame, force, torque, nullptr, tau_out);
+}
+
+int dexr_link_velocities_vjp(const dexr_pose_model* m, int64_t B, const double* x, const double* fixed, const double* xdot, int32_t frame,
+                             const double* grad_lin, const double* grad_ang, double* grad_x_out, double* grad_xdot_out) {
+  const int c = check_wrench_call(m, B, x, fixed, frame, grad_lin, grad_ang, grad_x_out, grad_xdot_out);
+  if (c) return c < 0 ? c : DEXR_OK;
+  if (grad_x_out && !xdot && m->h.n_in > 0) return dexr_set_error(DEXR_ERR_INVALID, "xdot is NULL");
+  return host_wrench(m, B, x, fixed, xdot, frame, grad_lin, grad_ang, grad_x_out, grad_xdot_out);
 }
 
 }  // extern "C"

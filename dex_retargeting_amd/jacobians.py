@@ -1,4 +1,5 @@
-"""Batched link Jacobians and link velocities on the GPU (include/dexr_jacobian.h, csrc/dexr_pose.hip), for torch tensors.
+"""Batched link Jacobians, link velocities and link wrenches on the GPU (include/dexr_jacobian.h, include/dexr_wrench.h,
+csrc/dexr_pose.hip), for torch tensors.
 
 ``link_jacobians(optimizer, q, link_names)`` gives ``J = d(pose)/dq`` of any links at the optimiser's variables -- the matrix a
 differential-IK or impedance step, a null-space projector, a manipulability measure or a contact Jacobian needs -- and
@@ -13,8 +14,12 @@ multiplier.  ``frame="world"`` is the velocity of the link origin and the angula
 LOCAL_WORLD_ALIGNED), ``frame="local"`` rotates both into the link's own axes (pinocchio's LOCAL, what
 ``RobotWrapper.compute_single_link_local_jacobian`` returns).
 
-The outputs carry NO autograd graph: they are first derivatives of the link poses, and their own derivative (the kinematic
-Hessian) is not built.  Differentiate through ``autograd.link_poses`` instead where a loss needs gradients.
+``link_wrenches(optimizer, q, link_names, force, torque)`` is the transposed product ``tau = sum_l Jlin_l^T force_l +
+Jang_l^T torque_l`` -- joint torques of contact forces, a differential-IK step of the J^T kind -- again without the matrix.
+
+The outputs carry NO autograd graph: the functions of this module build no derivative of theirs.  Where a loss needs
+gradients, differentiate through ``autograd.link_poses`` (poses) or ``autograd.link_velocities`` (velocities, in q and qdot:
+the kinematic Hessian contracted on both sides by a kernel of its own).
 """
 from __future__ import annotations
 
@@ -24,9 +29,10 @@ from .autograd import _check_poses
 _FRAMES = {"world": _lib.JAC_WORLD_ALIGNED, "local": _lib.JAC_LOCAL}
 
 
-def _check(n_in, n_fixed, q, qdot, fixed_qpos, link_names, frame, kin, what="q"):
+def _check(n_in, n_fixed, q, qdot, fixed_qpos, link_names, frame, kin, what="q", rows=()):
     """Every argument rule -- the frame, types, dtypes, shapes, the link names and last the device -- before anything
-    touches the GPU.  Returns the DEXR_JAC_* value of `frame`.  `qdot`: False where the call takes none."""
+    touches the GPU.  Returns the DEXR_JAC_* value of `frame`.  `qdot`: False where the call takes none.  `rows`: (name,
+    tensor) pairs that must be float32 (B, L, 3) tensors on q's device, one row per link."""
     import torch
 
     if not isinstance(frame, str) or frame not in _FRAMES:
@@ -38,12 +44,23 @@ def _check(n_in, n_fixed, q, qdot, fixed_qpos, link_names, frame, kin, what="q")
             raise ValueError(f"the rate of {what} must be float32, got {qdot.dtype}")
         if isinstance(q, torch.Tensor) and tuple(qdot.shape) != tuple(q.shape):
             raise ValueError(f"the rate of {what} must have its shape {tuple(q.shape)}, got {tuple(qdot.shape)}")
+    for name, t in rows:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if isinstance(q, torch.Tensor) and q.ndim == 2 and not isinstance(link_names, str) and \
+                tuple(t.shape) != (q.shape[0], len(link_names), 3):
+            raise ValueError(f"{name} must have shape ({q.shape[0]}, {len(link_names)}, 3), got {tuple(t.shape)}")
     if not isinstance(link_names, str):
         for n in link_names:
             kin.body_frame_index(n)  # ValueError on an unknown link
     _check_poses(n_in, n_fixed, q, fixed_qpos, link_names, what=what)  # (ends with the device)
     if qdot is not False and qdot.device != q.device:
         raise ValueError(f"the rate is on {qdot.device}, {what} on {q.device}: all tensors must be on one CUDA device")
+    for name, t in rows:
+        if t.device != q.device:
+            raise ValueError(f"{name} is on {t.device}, {what} on {q.device}: all tensors must be on one CUDA device")
     return _FRAMES[frame]
 
 
@@ -101,6 +118,35 @@ def _velocities(model_of, x, xdot, fixed_qpos, link_names, frame, angular):
     return _cat(lin), (_cat(ang) if angular else None)
 
 
+def _wrench_rows(force, torque):
+    if force is None and torque is None:
+        raise ValueError("force and torque are both None: at least one of them is required")
+    return [(n, t) for n, t in (("force", force), ("torque", torque)) if t is not None]
+
+
+def _wrenches(model_of, x, fixed_qpos, link_names, frame, force, torque):
+    """chunks of 64 links -> one table and one launch each, the chunks' torques summed."""
+    import torch
+
+    B = x.shape[0]
+    xc = x.detach().contiguous()
+    fixed = None if fixed_qpos is None or fixed_qpos.shape[1] == 0 else fixed_qpos.detach().contiguous()
+    tau = None
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        at = 0
+        for names in _chunks(link_names):
+            model = model_of(names)
+            f, t = (None if a is None else a.detach()[:, at:at + len(names)].contiguous() for a in (force, torque))
+            at += len(names)
+            part = torch.empty((B, model.n_in), dtype=torch.float32, device=x.device)
+            if B > 0:
+                model.wrenches_dev(B, xc.data_ptr(), 0 if fixed is None else fixed.data_ptr(), 0 if f is None else f.data_ptr(),
+                                   0 if t is None else t.data_ptr(), part.data_ptr(), frame=frame, stream=stream)
+            tau = part if tau is None else tau + part
+    return tau
+
+
 def link_jacobians(optimizer, q, link_names, fixed_qpos=None, frame="world", angular=True):
     """Jacobians of `link_names` with respect to the optimiser's variables: q (B, n_opt) float32 CUDA -- what `retarget`
     returns --, fixed_qpos (B, n_fixed) or None -> (jlin (B, L, 3, n_opt), jang of the same shape or None), float32.  Mimic
@@ -115,10 +161,21 @@ def link_jacobians(optimizer, q, link_names, fixed_qpos=None, frame="world", ang
 def link_velocities(optimizer, q, qdot, link_names, fixed_qpos=None, frame="world", angular=True):
     """Velocities of `link_names` for the rate qdot (B, n_opt) of the optimiser's variables at q: (lin (B, L, 3) velocity of
     the link origin, ang (B, L, 3) angular velocity or None), float32, = link_jacobians(...) @ qdot without the matrix.  Fixed
-    joints are held still.  No autograd graph."""
+    joints are held still.  No autograd graph: `autograd.link_velocities` is the same forward, differentiable in q and qdot."""
     n_fixed = len(optimizer.idx_pin2fixed)
     f = _check(optimizer.opt_dof, n_fixed, q, qdot, fixed_qpos, link_names, frame, optimizer.robot.kin)
     return _velocities(optimizer.pose_model, q, qdot, fixed_qpos, link_names, f, angular)
+
+
+def link_wrenches(optimizer, q, link_names, force=None, torque=None, fixed_qpos=None, frame="world"):
+    """Joint torques of forces and torques on `link_names` at q: force, torque (B, L, 3) float32 or None (not both), in world
+    axes at the link origin (`frame="world"`) or in the link's own axes (`"local"`) -> tau (B, n_opt) float32,
+    = einsum(jlin, force) + einsum(jang, torque) of `link_jacobians` without the matrix.  Mimic joints add to their source's
+    column, fixed joints take no torque.  The output carries no autograd graph (no gradient reaches q, force or torque)."""
+    n_fixed = len(optimizer.idx_pin2fixed)
+    f = _check(optimizer.opt_dof, n_fixed, q, False, fixed_qpos, link_names, frame, optimizer.robot.kin,
+               rows=_wrench_rows(force, torque))
+    return _wrenches(optimizer.pose_model, q, fixed_qpos, link_names, f, force, torque)
 
 
 def robot_link_jacobians(robot, qpos, link_names, frame="world", angular=True):
@@ -134,4 +191,11 @@ def robot_link_velocities(robot, qpos, qvel, link_names, frame="world", angular=
     return _velocities(robot.pose_model, qpos, qvel, None, link_names, f, angular)
 
 
-__all__ = ["link_jacobians", "link_velocities", "robot_link_jacobians", "robot_link_velocities"]
+def robot_link_wrenches(robot, qpos, link_names, force=None, torque=None, frame="world"):
+    """tau (B, robot.dof) for a full robot qpos in dof order; every joint is a column of its own."""
+    f = _check(robot.dof, 0, qpos, False, None, link_names, frame, robot.kin, what="qpos", rows=_wrench_rows(force, torque))
+    return _wrenches(robot.pose_model, qpos, None, link_names, f, force, torque)
+
+
+__all__ = ["link_jacobians", "link_velocities", "link_wrenches", "robot_link_jacobians", "robot_link_velocities",
+           "robot_link_wrenches"]
