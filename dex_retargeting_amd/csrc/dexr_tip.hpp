@@ -78,27 +78,134 @@ struct TipTabT {
   __device__ __forceinline__ v2 XA(int k1, int j) const { return xl[6 * k1 + j]; }
   __device__ __forceinline__ v2 XB(int k1, int j) const { return xl[6 * k1 + 3 + j]; }
 
+  // float32: what load() takes from the table, as it comes -- plain scalar registers, nothing pinned yet
+  struct Stage {
+    float X0[12], lo[4], hi[4];  // joint 0's placement, the box
+    float ot[3], oo[3];          // frame_off of the task frame / of the origin frame (row 0 where there is none)
+    float fill;                  // the lane's value of the 36 LDS constants (lanes 0..35)
+  };
+
   // `ft`: task frame (on joint 3); `fo`: origin frame on the base, or -1; `lds`: 36 reals of the wave's LDS
   __device__ __forceinline__ void load(const dexr_comp_table& tb, int ft, int fo, R* lds, int lane) {
-    if (lane < 36) {
-      const int q = lane >> 1, h = lane & 1, k = q / 6 + 1, jj = q % 6;
-      const int src = jj < 3 ? 3 * jj + h : (h == 0 ? 3 * (jj - 3) + 2 : 9 + (jj - 3));
-      lds[lane] = (R)(&tb.X[0][0])[k * 12 + src];
+    if constexpr (sizeof(R) == 4) {
+      // float32: the same values by the same operations, fetched as two batches (see fetch / hold below) instead of one
+      // scalar round trip per pinned value
+      Stage st;
+      fetch(tb, lane, st);
+      hold(st, ft, fo);
+      place_lds(st, lds, lane);
+      pin_joint0<false>(st);
+      fetch_off(tb, ft, fo, st);
+      hold_off(st);
+      pin_off(st, fo);
+    } else {
+      if (lane < 36) lds[lane] = (R)(&tb.X[0][0])[fill_index(lane)];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      xl = reinterpret_cast<const v2*>(lds);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        A0[i] = v2{tip_const<R>(tb.X[0][3 * i]), tip_const<R>(tb.X[0][3 * i + 1])};
+        c0[i] = tip_const<R>(tb.X[0][3 * i + 2]);
+        p0[i] = tip_const<R>(tb.X[0][9 + i] - (fo >= 0 ? tb.frame_off[fo][i] : 0.f));
+        off[i] = tip_const<R>(tb.frame_off[ft][i]);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        lo[k] = tip_const<R>(tb.lo[k]);
+        hi[k] = tip_const<R>(tb.hi[k]);
+      }
     }
+  }
+  // which float of tb.X lane `lane` (< 36) copies into the wave's LDS: the pair layout of xl
+  static __device__ __forceinline__ int fill_index(int lane) {
+    const int q = lane >> 1, h = lane & 1, k = q / 6 + 1, jj = q % 6;
+    const int src = jj < 3 ? 3 * jj + h : (h == 0 ? 3 * (jj - 3) + 2 : 9 + (jj - 3));
+    return k * 12 + src;
+  }
+
+  // ---- float32: load() in steps, so that a kernel can put loads of its own into the same batches (dexr_tip32_kernel).
+  // tip_pin is an `asm volatile`: pins stay in program order, and a table value read inside a pin's argument is loaded right
+  // in front of that pin -- one scalar load in flight at a time, a wait per value (about thirty dependent round trips through
+  // the scalar cache in front of pass 0).  Here every value a batch needs is read into a plain local first and ONE empty asm
+  // takes them all as scalar-register operands: the loads have to be complete there, so the compiler issues them together (as
+  // s_load_dwordx2 / x4 / x8 where they are contiguous) behind one s_waitcnt.  The pins follow, on registers.
+  //
+  // batch 1, issue: joint 0's placement and the box (contiguous in the table), and the lane's LDS constant as a vector load
+  __device__ __forceinline__ void fetch(const dexr_comp_table& tb, int lane, Stage& st) const {
+    st.fill = (&tb.X[0][0])[fill_index(lane < 36 ? lane : 0)];  // (every lane loads: no branch around the issue)
+#pragma unroll
+    for (int i = 0; i < 12; ++i) st.X0[i] = tb.X[0][i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      st.lo[k] = tb.lo[k];
+      st.hi[k] = tb.hi[k];
+    }
+  }
+  // batch 1, wait: ... together with integers of the caller's that were read along with it (load(): the frame indices)
+#define DEXR_TIP_BATCH1(st)                                                                                                      \
+  "+s"(st.X0[0]), "+s"(st.X0[1]), "+s"(st.X0[2]), "+s"(st.X0[3]), "+s"(st.X0[4]), "+s"(st.X0[5]), "+s"(st.X0[6]), "+s"(st.X0[7]), \
+      "+s"(st.X0[8]), "+s"(st.X0[9]), "+s"(st.X0[10]), "+s"(st.X0[11]), "+s"(st.lo[0]), "+s"(st.lo[1]), "+s"(st.lo[2]),           \
+      "+s"(st.lo[3]), "+s"(st.hi[0]), "+s"(st.hi[1]), "+s"(st.hi[2]), "+s"(st.hi[3]), "+v"(st.fill)
+  __device__ __forceinline__ void hold(Stage& st, int& a, int& b) const { asm volatile("" : DEXR_TIP_BATCH1(st), "+s"(a), "+s"(b)); }
+  __device__ __forceinline__ void hold(Stage& st, int& a, int& b, int& c, int& d) const {
+    asm volatile("" : DEXR_TIP_BATCH1(st), "+s"(a), "+s"(b), "+s"(c), "+s"(d));
+  }
+#undef DEXR_TIP_BATCH1
+  // batch 2 (its addresses depend on batch 1): the two frame offsets ...
+  __device__ __forceinline__ void fetch_off(const dexr_comp_table& tb, int ft, int fo, Stage& st) const {
+    const int fo0 = fo >= 0 ? fo : 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      st.ot[i] = tb.frame_off[ft][i];
+      st.oo[i] = tb.frame_off[fo0][i];
+    }
+  }
+  // ... together with two integers of the caller's, if it has any
+#define DEXR_TIP_BATCH2(st) "+s"(st.ot[0]), "+s"(st.ot[1]), "+s"(st.ot[2]), "+s"(st.oo[0]), "+s"(st.oo[1]), "+s"(st.oo[2])
+  __device__ __forceinline__ void hold_off(Stage& st) const { asm volatile("" : DEXR_TIP_BATCH2(st)); }
+  __device__ __forceinline__ void hold_off(Stage& st, int& a, int& b) const { asm volatile("" : DEXR_TIP_BATCH2(st), "+s"(a), "+s"(b)); }
+#undef DEXR_TIP_BATCH2
+  // the LDS constants to their places, then the pins (the subtraction of the origin frame stays the float32 operation on the
+  // device it was: x - 0.f is x bit for bit where there is no origin frame)
+  __device__ __forceinline__ void place(const Stage& st, int fo, R* lds, int lane) {
+    place_lds(st, lds, lane);
+    pin_joint0(st);
+    pin_off(st, fo);
+  }
+  __device__ __forceinline__ void place_lds(const Stage& st, R* lds, int lane) {
+    if (lane < 36) lds[lane] = st.fill;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     xl = reinterpret_cast<const v2*>(lds);
+  }
+  // what batch 1 brought.  ROT = false leaves joint 0's rotation as hold() returned it: the empty asm there already is a pin (its
+  // outputs are scalar registers of unknown contents), the second one through a VGPR is redundant.  Who drops it is decided by
+  // the census of the code objects: dexr_kernel's chain instantiations (plain / EXT) spill 30 / 33 SGPRs without it and 38 / 39
+  // with it (34 / 42 before the batches), dexr_tip32_kernel's loop comes out instruction for instruction as it was with it.
+  template <bool ROT = true>
+  __device__ __forceinline__ void pin_joint0(const Stage& st) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      A0[i] = v2{tip_const<R>(tb.X[0][3 * i]), tip_const<R>(tb.X[0][3 * i + 1])};
-      c0[i] = tip_const<R>(tb.X[0][3 * i + 2]);
-      p0[i] = tip_const<R>(tb.X[0][9 + i] - (fo >= 0 ? tb.frame_off[fo][i] : 0.f));
-      off[i] = tip_const<R>(tb.frame_off[ft][i]);
+      if constexpr (ROT) {
+        A0[i] = v2{tip_pin(st.X0[3 * i]), tip_pin(st.X0[3 * i + 1])};
+        c0[i] = tip_pin(st.X0[3 * i + 2]);
+      } else {
+        A0[i] = v2{st.X0[3 * i], st.X0[3 * i + 1]};
+        c0[i] = st.X0[3 * i + 2];
+      }
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      lo[k] = tip_const<R>(tb.lo[k]);
-      hi[k] = tip_const<R>(tb.hi[k]);
+      lo[k] = tip_pin(st.lo[k]);
+      hi[k] = tip_pin(st.hi[k]);
+    }
+  }
+  __device__ __forceinline__ void pin_off(const Stage& st, int fo) {  // ... and batch 2
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      p0[i] = tip_pin(st.X0[9 + i] - (fo >= 0 ? st.oo[i] : 0.f));
+      off[i] = tip_pin(st.ot[i]);
     }
   }
 };

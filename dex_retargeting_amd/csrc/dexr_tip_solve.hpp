@@ -6,8 +6,10 @@
 // objective-value output as live branches and live scalar registers.  A plain tile launch of a tip model -- the headline: every
 // lane gets its one frame before the first pass and never another -- needs none of it.  This kernel is that launch written
 // straight:
-//   prologue  table pin, the lane's frame (same loads, same LDS layout as dexr_kernel), clamp to the box, evaluation of the
-//             start point (dexr_kernel's pass 0), whose model is adopted;
+//   prologue  table pin, the lane's frame (same values, same LDS layout as dexr_kernel), clamp to the box, evaluation of the
+//             start point (dexr_kernel's pass 0), whose model is adopted.  Its loads go out in batches, one wait per level
+//             of their dependency chain, and the frame's own loads are in flight while the constants are pinned -- at every
+//             launch size, each issued once (they replace the early touch of the frame's lines that small launches had);
 //   loop      (a) damped 4 x 4 step from the kept model, (b) tip_eval at the trial point unless every live lane takes its
 //             blind last step, (c) accept / reject / damping / termination, (d) finished lanes store and drop out;
 //             the wave leaves when no lane holds a frame.
@@ -72,6 +74,24 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
   extern __shared__ __align__(16) unsigned char lds_raw[];
   using RT = RealTraits<float, true>;
   constexpr auto hidx = [](int r, int c) constexpr { return r * (r + 1) / 2 + c; };
+  // The prologue is a few batches of loads, one wait per level of the dependency chain
+  //   kernel arguments -> the component's table (+ the lane's LDS constant) -> frame offsets, keypoint indices -> the frame
+  // instead of a round trip per value: see TipTabT<float>::fetch / hold (dexr_tip.hpp).
+  // Level 0: the options of the solve, all of them kernel arguments, behind one wait -- and with them (as inputs only: the
+  // pointers keep what the compiler knows about them) the arguments the index arithmetic and the addresses below need, which
+  // would otherwise be fetched one by one where they are first used.
+  float a_delta = kp.norm_delta, a_lam0 = kp.lam0, a_tol = kp.tol, a_blind_tol = kp.blind_tol, a_step_cap = kp.step_cap;
+  float a_huber = kp.huber_delta, a_inv_norm = kp.inv_norm, a_lam_fastdec = kp.lam_fastdec, a_lam_jump = kp.lam_jump;
+  float a_lam_recover = kp.lam_recover, a_stall_ratio = kp.stall_ratio, a_stall_cap = kp.stall_cap;
+  float a_scaling = kp.scaling;
+  int a_newton = kp.newton, a_stall_from = kp.stall_from, a_max_blind = kp.max_blind, a_max_iter = kp.max_iter;
+  asm volatile(""
+               : "+s"(a_delta), "+s"(a_lam0), "+s"(a_tol), "+s"(a_blind_tol), "+s"(a_step_cap), "+s"(a_huber), "+s"(a_inv_norm),
+                 "+s"(a_lam_fastdec), "+s"(a_lam_jump), "+s"(a_lam_recover), "+s"(a_stall_ratio), "+s"(a_stall_cap), "+s"(a_newton),
+                 "+s"(a_stall_from), "+s"(a_max_blind), "+s"(a_max_iter), "+s"(a_scaling)
+               : "s"((int)blockDim.x), "s"(kp.last), "s"(kp.kpts), "s"(kp.ref), "s"(kp.B), "s"(kp.n_comp), "s"(kp.n_opt), "s"(kp.n_kp), "s"(kp.n_ref),
+                 "s"(kp.lds_frames), "s"(kp.lds_terms));
+
   const int lane = threadIdx.x & 63;
   const int wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int waves_per_block = blockDim.x >> 6;
@@ -89,72 +109,78 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
   float* T = P + 64 * 3 * kp.lds_frames;
   float* W = T + 64 * 3 * kp.lds_terms;
 
+  // Level 1: the component's table -- joint 0, the box, the lane's LDS constant, and the four integers the addresses below hang on
   const dexr_comp_table& tb = comps[comp];
-  const int api0 = tip_pin((int)tb.api[0]);  // a tip component's four joints are consecutive columns of last_qpos / qpos_out
-  const int row = tb.term_ref[0];
-
-  // launches that do not fill the chip: touch the lines of the lane's frame before the constants of the pass are fetched
-  // and pinned (see dexr_kernel: the HBM round trip overlaps the table set-up)
-  float touch0 = 0.f, touch1 = 0.f, touch2 = 0.f;
-  const bool touch = kp.kpts != nullptr && has && (int64_t)gridDim.x * waves_per_block < 4096;
-  if (touch) {
-    touch0 = kp.last[item * ld + api0];
-    touch1 = kp.kpts[(item * kp.n_kp + kp.h_task[row]) * 3];
-    const int o = kp.h_origin[row];
-    touch2 = kp.kpts[(item * kp.n_kp + (o >= 0 ? o : 0)) * 3];
-  }
   TipTabT<float> tt;
-  tt.load(tb, tb.term_task[0], tb.term_origin[0], W + 64 * kp.lds_terms, lane);
-  if (touch) asm volatile("" ::"v"(touch0), "v"(touch1), "v"(touch2));
+  TipTabT<float>::Stage st;
+  int api0 = tb.api[0];  // a tip component's four joints are consecutive columns of last_qpos / qpos_out
+  int row = tb.term_ref[0], ft = tb.term_task[0], fo = tb.term_origin[0];
+  tt.fetch(tb, lane, st);
+  tt.hold(st, api0, row, ft, fo);
+  // Level 2: the frame offsets, and which keypoints the term's target is made of
+  const int hrow = row < DEXR_MAXT ? row : DEXR_MAXT - 1;  // (keypoint input: row itself; ref_value rows may number more)
+  int h_t = kp.h_task[hrow], h_o = kp.h_origin[hrow];
+  tt.fetch_off(tb, ft, fo, st);
+  tt.hold_off(st, h_t, h_o);
+  api0 = tip_pin(api0);
+
+  // Level 3, the lane's frame: start point / regularisation target from last_qpos, the term's target from the keypoints or the
+  // ref_value row -- every load issued here, waited for once, behind the pins
+  float x[4] = {0.f, 0.f, 0.f, 0.f}, xl[4] = {0.f, 0.f, 0.f, 0.f};
+  float fl[4], ra[3], rb[3];  // (set and read by lanes that hold a frame only)
+  // the target is keypoint h_t minus keypoint h_o, or keypoint h_t alone, or the ready-made ref_value row: the wave-uniform
+  // choice is made on the ADDRESSES (without an origin keypoint rb re-reads ra's line and is not used), so that each load is
+  // issued exactly once and no loaded value has to be merged with another or moved between registers before the pins are through
+  const bool sub = kp.kpts != nullptr && h_o >= 0;
+  if (has) {
+    const float* pa = kp.kpts ? kp.kpts + (item * kp.n_kp + h_t) * 3 : kp.ref + (item * kp.n_ref + row) * 3;
+    const float* pb = sub ? kp.kpts + (item * kp.n_kp + h_o) * 3 : pa;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) fl[k] = kp.last[item * ld + api0 + k];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      ra[i] = pa[i];
+      rb[i] = pb[i];
+    }
+  }
+
+  tt.place(st, fo, W + 64 * kp.lds_terms, lane);
 
   // constants of the pass, pinned in SGPRs (the values read by every pass first)
-  const float k_delta = tip_pin(kp.norm_delta), k_lam0 = tip_pin(kp.lam0), k_tol = tip_pin(kp.tol), k_blind_tol = tip_pin(kp.blind_tol);
-  const float k_step_cap = tip_pin(kp.step_cap);
-  const float tip_beta = tip_pin(kp.huber_delta), tip_ibeta = tip_pin(1.f / kp.huber_delta);
-  const float tip_w = tip_pin(kp.inv_norm), tip_nw = tip_pin(kp.newton != 0 ? 1.f : 0.f);
-  const float k_lam_fastdec = tip_pin(kp.lam_fastdec), k_lam_jump = tip_pin(kp.lam_jump), k_lam_recover = tip_pin(kp.lam_recover);
-  const float k_stall_ratio = tip_pin(kp.stall_ratio);
-  const int k_stall_from = tip_pin(kp.stall_from), k_max_blind = tip_pin(kp.max_blind), k_max_iter = tip_pin(kp.max_iter);
+  const float k_delta = tip_pin(a_delta), k_lam0 = tip_pin(a_lam0), k_tol = tip_pin(a_tol), k_blind_tol = tip_pin(a_blind_tol);
+  const float k_step_cap = tip_pin(a_step_cap);
+  const float tip_beta = tip_pin(a_huber), tip_ibeta = tip_pin(1.f / a_huber);
+  const float tip_w = tip_pin(a_inv_norm), tip_nw = tip_pin(a_newton != 0 ? 1.f : 0.f);
+  const float k_lam_fastdec = tip_pin(a_lam_fastdec), k_lam_jump = tip_pin(a_lam_jump), k_lam_recover = tip_pin(a_lam_recover);
+  const float k_stall_ratio = tip_pin(a_stall_ratio);
+  const int k_stall_from = tip_pin(a_stall_from), k_max_blind = tip_pin(a_max_blind), k_max_iter = tip_pin(a_max_iter);
   // ... and what the pass derives from them, formed once (the same single multiplications dexr_kernel does) and pinned as
   // well: left to the compiler each becomes a VGPR that is live through the whole loop
   const float k_2delta = tip_pin(2.f * k_delta), k_10tol = tip_pin(10.f * k_tol);
-  const float k_stall_max = tip_pin(kp.stall_cap * k_tol);
+  const float k_stall_max = tip_pin(a_stall_cap * k_tol);
   const float k_lam_ok = tip_pin(fmax(2.f * k_delta, 10.f * k_lam0)), k_lam_ok_half = tip_pin(0.5f * fmax(2.f * k_delta, 10.f * k_lam0));
   // options as thresholds (a comparison with +inf is never true): "lam_fastdec > 0 and rho > 0.9" is rho > k_rho_fast,
   // "lam_recover > 0 and lambda > 10 lam0" is lambda > k_lam_rec_from -- one SGPR each instead of a hoisted lane mask
   const float k_inf = __builtin_inff();
-  const float k_rho_fast = tip_pin(kp.lam_fastdec > 0 ? 0.9f : k_inf), k_lam_rec_from = tip_pin(kp.lam_recover > 0 ? 10.f * kp.lam0 : k_inf);
+  const float k_rho_fast = tip_pin(a_lam_fastdec > 0 ? 0.9f : k_inf), k_lam_rec_from = tip_pin(a_lam_recover > 0 ? 10.f * a_lam0 : k_inf);
 
-  // ---- the lane's frame: start point / regularisation target from last_qpos, the term's target into the lane's LDS column
-  float x[4] = {0.f, 0.f, 0.f, 0.f}, xl[4] = {0.f, 0.f, 0.f, 0.f};
+  // ---- the frame has arrived: the term's target into the lane's LDS column, the start point into the box
   if (has) {
+    float rv[3];
+    if (sub) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) rv[i] = ra[i] - rb[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) rv[i] = ra[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) T[i * 64 + lane] = rv[i] * a_scaling;  // f32 multiply: optimizer.py:246
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float v = kp.last[item * ld + api0 + k];
-      xl[k] = v;
-      x[k] = v;
+      xl[k] = fl[k];
+      x[k] = RT::clamp(fl[k], tt.lo[k], tt.hi[k]);
     }
-    float rv[3];
-    if (kp.kpts) {
-      const float* a = kp.kpts + (item * kp.n_kp + kp.h_task[row]) * 3;
-      const int o = kp.h_origin[row];
-      if (o >= 0) {
-        const float* b = kp.kpts + (item * kp.n_kp + o) * 3;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) rv[i] = a[i] - b[i];
-      } else {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) rv[i] = a[i];
-      }
-    } else {
-      const float* r = kp.ref + (item * kp.n_ref + row) * 3;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) rv[i] = r[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) T[i * 64 + lane] = rv[i] * kp.scaling;  // f32 multiply: optimizer.py:246
-#pragma unroll
-    for (int k = 0; k < 4; ++k) x[k] = RT::clamp(x[k], tt.lo[k], tt.hi[k]);
   }
 
   // kept model: data term + regulariser at the accepted point x
