@@ -59,6 +59,8 @@ JAC_EXPORTS = ["dexr_link_jacobians_dev", "dexr_link_velocities_dev", "dexr_link
 JAC_WORLD_ALIGNED, JAC_LOCAL = 0, 1  # DEXR_JAC_*
 # include/dexr_wrench.h (J^T on a pose table: link wrenches and the VJP of the link velocities): a list of its own
 WRENCH_EXPORTS = ["dexr_link_wrenches_dev", "dexr_link_velocities_vjp_dev", "dexr_link_wrenches", "dexr_link_velocities_vjp"]
+# include/dexr_ik.h (one damped least-squares IK step on a pose table): a list of its own
+IK_EXPORTS = ["dexr_link_ik_step_dev", "dexr_link_ik_step"]
 UNIQUE_ID_BYTES = 128
 
 
@@ -140,6 +142,8 @@ def load() -> C.CDLL:
     lib.dexr_link_velocities_vjp_dev.argtypes = [vp, i64, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
     lib.dexr_link_wrenches.argtypes = [vp, i64, f64p, f64p, C.c_int32, f64p, f64p, f64p]
     lib.dexr_link_velocities_vjp.argtypes = [vp, i64, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p]
+    lib.dexr_link_ik_step_dev.argtypes = [vp, i64, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_float, vp, vp]
+    lib.dexr_link_ik_step.argtypes = [vp, i64, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, f64p]
     _lib = lib
     return lib
 
@@ -439,6 +443,14 @@ class PoseModel:
                                                   grad_lin_ptr or None, grad_ang_ptr or None, grad_x_ptr or None,
                                                   grad_xdot_ptr or None, stream or None))
 
+    def ik_step_dev(self, B: int, x_ptr: int, fixed_ptr: int, err_lin_ptr: int, err_ang_ptr: int, w_lin_ptr: int, w_ang_ptr: int,
+                    damping: float, dx_ptr: int, frame: int = 0, stream: int = 0):
+        """err_lin, err_ang (B, n_link, 3), either may be 0; w_lin, w_ang (B, n_link) or 0 (weights of 1) -> dx (B, n_in), the
+        damped least-squares step, every entry written (dexr_link_ik_step_dev)."""
+        check(load().dexr_link_ik_step_dev(self._h, B, x_ptr or None, fixed_ptr or None, int(frame), err_lin_ptr or None,
+                                           err_ang_ptr or None, w_lin_ptr or None, w_ang_ptr or None, float(damping),
+                                           dx_ptr or None, stream or None))
+
     # host-pointer entry points: float64 in, float64 arithmetic, float64 out ----------------------------
     def _host_inputs(self, x, fixed):
         x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float64)))
@@ -508,6 +520,28 @@ class PoseModel:
         if a.shape != (B, self.n_link, 3):
             raise ValueError(f"{what} must have shape ({B}, {self.n_link}, 3), got {a.shape}")
         return a
+
+    def _host_link_weights(self, a, B, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (B, self.n_link):
+            raise ValueError(f"{what} must have shape ({B}, {self.n_link}), got {a.shape}")
+        return a
+
+    def ik_step(self, x, fixed=None, err_lin=None, err_ang=None, w_lin=None, w_ang=None, damping=None, frame: int = 0):
+        """-> dx (B, n_in) float64 (dexr_link_ik_step); at least one of err_lin, err_ang (B, n_link, 3) is required, w_lin,
+        w_ang (B, n_link) or None weigh them, damping > 0 is required."""
+        if damping is None:
+            raise ValueError("damping is required")
+        x, fixed, B = self._host_inputs(x, fixed)
+        err_lin, err_ang = self._host_link_rows(err_lin, B, "err_lin"), self._host_link_rows(err_ang, B, "err_ang")
+        w_lin, w_ang = self._host_link_weights(w_lin, B, "w_lin"), self._host_link_weights(w_ang, B, "w_ang")
+        dx = np.zeros((B, self.n_in), dtype=np.float64)
+        check(load().dexr_link_ik_step(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), int(frame),
+                                       _ptr(err_lin, C.c_double), _ptr(err_ang, C.c_double), _ptr(w_lin, C.c_double),
+                                       _ptr(w_ang, C.c_double), float(damping), _ptr(dx, C.c_double)))
+        return dx
 
     def wrenches(self, x, fixed=None, force=None, torque=None, frame: int = 0):
         """-> tau (B, n_in) float64 (dexr_link_wrenches); at least one of force, torque (B, n_link, 3) is required."""

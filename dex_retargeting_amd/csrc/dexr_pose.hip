@@ -47,15 +47,27 @@
 //                              takes both gradients of a joint from the five range sums and its own twist.
 // The rate gradient of the VJP form is the wrench form's arithmetic operation by operation (rate_grad, cross_fma: explicit
 // fma, nothing left to contraction), so the two agree bit for bit.
+//
+// DAMPED LEAST-SQUARES IK STEP (include/dexr_ik.h): dx = (J^T W J + lambda I)^-1 J^T W e of the Jacobians above, with neither J
+// nor the normal matrix written to memory.  One kernel (pose_ik_kernel<T>), two phases in one block like the Jacobian kernel:
+//   phase A (lane = frame)          the Jacobian kernel's walk: a_k, o_k per joint driven by x, and per sorted link p_l, the weighted
+//                                   errors as a force and a moment in world axes and the two weights, in the frame's region of LDS;
+//   phase B (16 threads per frame)  the packed lower triangle of H over the ACTIVE columns (those some joint reads: at most 64
+//                                   whatever n_in is) and g, each entry summed by one thread over the joints of its columns and the
+//                                   links below both; then a Cholesky factorisation and two triangular solves in LDS, one barrier
+//                                   per column, and the scatter to dx with zeros in the columns no joint reads.
+// Every sum has a fixed order that does not depend on the frames per block: a frame's row is the same bits at every B.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <vector>
 
 #include "dexr.h"
 #include "dexr_math.hpp"
+#include "dexr_ik.h"
 #include "dexr_jacobian.h"
 #include "dexr_pose.h"
 #include "dexr_wrench.h"
@@ -769,6 +781,201 @@ __global__ void __launch_bounds__(POSE_BLOCK * JAC_FANOUT) pose_jacobian_kernel(
   }
 }
 
+// ---- damped least-squares IK step (include/dexr_ik.h) --------------------------------------------------------------------------
+// threads of an IK block per frame it holds, and the most frames it holds (256 threads).  Phase A runs on the first
+// IK_FRAMES lanes at most (lane = frame), phase B on all of the block: the IK_FANOUT threads of a frame sit in one wave
+constexpr int IK_FANOUT = 16;
+constexpr int IK_FRAMES = 16;
+constexpr int IK_LINK = 11;  // values parked per sorted link: p_l, f_l, m_l (world axes, weighted), w_lin, w_ang
+
+// c = a x (p - o) (revolute) | a (prismatic): the linear column of one joint at one link, world axes, before its multiplier
+template <typename T>
+__device__ __forceinline__ void ik_column(const T* a, bool rev, const T* p, T c[3]) {
+  if (rev) {
+    const T d[3] = {p[0] - a[3], p[1] - a[4], p[2] - a[5]};
+    const T ax[3] = {a[0], a[1], a[2]};
+    cross_fma(ax, d, c);
+  } else {
+    c[0] = a[0];
+    c[1] = a[1];
+    c[2] = a[2];
+  }
+}
+
+// Per frame one region of LDS, [frame][stride] with an odd stride: a, o per joint driven by x | IK_LINK values per sorted link |
+// H, the packed lower triangle over the active columns (row i starts at i (i + 1) / 2), overwritten by its Cholesky factor below
+// the diagonal | g (later dx) | y | the factor's diagonal.  Every entry of H and g is summed by one thread in table order, and
+// the factorisation and the solves walk the columns in order with one barrier each: no sum depends on the launch shape.
+template <typename T>
+__global__ void __launch_bounds__(IK_FANOUT * IK_FRAMES) pose_ik_kernel(const JointD<T>* __restrict__ joints, const LinkD<T>* __restrict__ links,
+                                                                       PoseArgs<T> P, const JacEnt* __restrict__ ents,
+                                                                       const uint32_t* __restrict__ act_rng,
+                                                                       const int32_t* __restrict__ col_act, const uint2* __restrict__ tri,
+                                                                       int n_jx, int n_act, int stride, int frame, const T* __restrict__ x,
+                                                                       const T* __restrict__ fixed, const T* __restrict__ el,
+                                                                       const T* __restrict__ ea, const T* __restrict__ wl,
+                                                                       const T* __restrict__ wa, T lambda, T* __restrict__ dx) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pose_lds[];
+  const int nl = blockDim.x / IK_FANOUT, tid = threadIdx.x;  // nl: frames of this block
+  T* slots = reinterpret_cast<T*>(pose_lds);
+  T* park = slots + (size_t)P.n_slot * 12 * nl;
+  const int lbase = 6 * n_jx, n_tri = n_act * (n_act + 1) / 2;
+  const int hbase = lbase + IK_LINK * P.n_link, gbase = hbase + n_tri, ybase = gbase + n_act, dbase = ybase + n_act;
+  const int64_t first = (int64_t)blockIdx.x * nl;
+  if (tid < nl) {  // phase A: lane = frame
+    const int lane = tid;
+    const bool local = frame == DEXR_JAC_LOCAL;
+    T* pk = park + (size_t)lane * stride;
+    const int64_t b = first + lane < P.B ? first + lane : P.B - 1;  // ragged tail: idle lanes park the last frame again
+    Xf<T> t;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) t.R[i] = (i % 4 == 0) ? T(1) : T(0);
+    t.p[0] = t.p[1] = t.p[2] = T(0);
+    int xi = 0;
+    for (int k = 0; k < P.n_joint; ++k) {  // (links on the fixed base are below no joint: phase B never reads their records)
+      const JointD<T>& J = joints[k];
+      T a[3];
+      joint_step(J, P, x, fixed, b, slots, nl, lane, t, a);
+      if (J.src_kind == DEXR_POSE_SRC_X) {
+        T* d = pk + 6 * xi;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          d[i] = a[i];
+          d[3 + i] = t.p[i];
+        }
+        ++xi;
+      }
+      for (int l = J.link_begin; l < J.link_end; ++l) {
+        const LinkD<T>& L = links[l];
+        T R[9], p[3], f[3] = {T(0), T(0), T(0)}, m[3] = {T(0), T(0), T(0)}, wf = T(0), wm = T(0);
+        link_pose(L, t, R, p);
+        const int64_t row = b * P.n_link + L.out;
+        if (el) {
+          wf = wl ? wl[row] : T(1);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) f[i] = el[row * 3 + i];
+          if (local) to_world(R, f);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) f[i] *= wf;
+        }
+        if (ea) {
+          wm = wa ? wa[row] : T(1);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) m[i] = ea[row * 3 + i];
+          if (local) to_world(R, m);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) m[i] *= wm;
+        }
+        T* d = pk + lbase + IK_LINK * l;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          d[i] = p[i];
+          d[3 + i] = f[i];
+          d[6 + i] = m[i];
+        }
+        d[9] = wf;
+        d[10] = wm;
+      }
+    }
+  }
+  __syncthreads();
+  // phase B: IK_FANOUT threads per frame
+  const int fr = tid / IK_FANOUT, t = tid % IK_FANOUT;
+  T* pk = park + (size_t)fr * stride;
+  T* H = pk + hbase;
+  T* g = pk + gbase;
+  T* y = pk + ybase;
+  T* dg = pk + dbase;
+  for (int e = t; e < n_tri; e += IK_FANOUT) {  // H[i, j], i >= j: the joints of the two columns, the links below both
+    const uint2 d = tri[e];  // x: i | j << 6; y: the entries of column i, of column j (both empty where no link is below both)
+    const int i = d.x & 63, j = d.x >> 6;
+    const int i0 = d.y & 255, i1 = (d.y >> 8) & 255, j0 = (d.y >> 16) & 255, j1 = d.y >> 24;
+    T s = T(0);
+    for (int ii = i0; ii < i1; ++ii) {
+      const JacEnt A = ents[ii];
+      const T* a = pk + 6 * A.xi;
+      const bool arev = A.type == DEXR_POSE_REVOLUTE;
+      for (int jj = j0; jj < j1; ++jj) {
+        const JacEnt Bn = ents[jj];
+        const int lo = A.link_begin > Bn.link_begin ? A.link_begin : Bn.link_begin;
+        const int hi = A.sub_end < Bn.sub_end ? A.sub_end : Bn.sub_end;
+        if (lo >= hi) continue;
+        const T* c = pk + 6 * Bn.xi;
+        const bool brev = Bn.type == DEXR_POSE_REVOLUTE;
+        const T mm = mult_of(A, T(0)) * mult_of(Bn, T(0));
+        const T aa = (arev && brev) ? dot_fma(a, c) : T(0);
+        T sl = T(0);
+        for (int l = lo; l < hi; ++l) {
+          const T* q = pk + lbase + IK_LINK * l;
+          T u[3], v[3];
+          ik_column(a, arev, q, u);
+          ik_column(c, brev, q, v);
+          sl = fma(q[9], dot_fma(u, v), fma(q[10], aa, sl));
+        }
+        s = fma(mm, sl, s);
+      }
+    }
+    H[e] = i == j ? s + lambda : s;
+  }
+  for (int i = t; i < n_act; i += IK_FANOUT) {  // g[i]
+    const uint32_t r = act_rng[i];
+    T s = T(0);
+    for (int ii = r & 255; ii < (int)(r >> 8); ++ii) {
+      const JacEnt A = ents[ii];
+      const T* a = pk + 6 * A.xi;
+      const bool arev = A.type == DEXR_POSE_REVOLUTE;
+      T sl = T(0);
+      for (int l = A.link_begin; l < A.sub_end; ++l) {
+        const T* q = pk + lbase + IK_LINK * l;
+        T u[3];
+        ik_column(a, arev, q, u);
+        sl += dot_fma(u, q + 3);
+        if (arev) sl += dot_fma(a, q + 6);
+      }
+      s = fma(mult_of(A, T(0)), sl, s);
+    }
+    g[i] = s;
+  }
+  __syncthreads();
+  // Cholesky, one column per step: every thread of the frame forms the pivot itself (row k is complete), then its rows
+  for (int k = 0; k < n_act; ++k) {
+    const T* rk = H + k * (k + 1) / 2;
+    T skk = rk[k];
+    for (int p = 0; p < k; ++p) skk = fma(-rk[p], rk[p], skk);
+    const T d = sqrt(skk);
+    if (t == 0) dg[k] = d;
+    for (int i = k + 1 + t; i < n_act; i += IK_FANOUT) {
+      T* ri = H + i * (i + 1) / 2;
+      T s = ri[k];
+      for (int p = 0; p < k; ++p) s = fma(-ri[p], rk[p], s);
+      ri[k] = s / d;
+    }
+    __syncthreads();
+  }
+  // L y = g, by columns
+  for (int k = 0; k < n_act; ++k) {
+    const T yk = g[k] / dg[k];
+    if (t == 0) y[k] = yk;
+    for (int i = k + 1 + t; i < n_act; i += IK_FANOUT) g[i] = fma(-H[i * (i + 1) / 2 + k], yk, g[i]);
+    __syncthreads();
+  }
+  // L^T dx = y, by rows of L from the last; dx takes the place of g
+  for (int k = n_act - 1; k >= 0; --k) {
+    const T zk = y[k] / dg[k];
+    if (t == 0) g[k] = zk;
+    const T* rk = H + k * (k + 1) / 2;
+    for (int p = t; p < k; p += IK_FANOUT) y[p] = fma(-rk[p], zk, y[p]);
+    __syncthreads();
+  }
+  if (first + fr < P.B) {
+    T* o = dx + (first + fr) * P.n_in;
+    for (int c = t; c < P.n_in; c += IK_FANOUT) {
+      const int a = col_act[c];
+      o[c] = a >= 0 ? g[a] : T(0);
+    }
+  }
+}
+
 template <typename T>
 struct DevTables {
   JointD<T>* joints = nullptr;
@@ -788,6 +995,13 @@ struct dexr_pose_model {
   int32_t* jac_colptr = nullptr;  // (n_in + 1)
   JacEnt* jac_ents = nullptr;     // (n_jx), grouped by column
   uint32_t* jac_emap = nullptr;   // (n_link 3 n_in): sorted link | row << 6 | column << 8 of an output element
+  // index data of the IK kernel: the active columns (those some joint reads), in column order
+  int n_act = 0;
+  uint32_t* ik_act_rng = nullptr;  // (n_act): the entries of active column i in jac_ents, first | end << 8
+  int32_t* ik_col_act = nullptr;   // (n_in): active index of column c, -1: no joint reads it
+  uint2* ik_tri = nullptr;         // (n_act (n_act + 1) / 2), packed lower-triangle entry (i, j), i >= j: x = i | j << 6,
+                                   // y = the entry ranges of the two columns, first_i | end_i << 8 | first_j << 16 | end_j << 24,
+                                   // all 0 where no link is below a joint of each (the entry of H is a structural zero)
 };
 
 namespace {
@@ -955,6 +1169,36 @@ hipError_t upload_jacobian_index(const dexr_pose_header& h, const std::vector<de
   if (e == hipSuccess) e = hipMemcpy(m->jac_colptr, colptr.data(), colptr.size() * sizeof(int32_t), hipMemcpyHostToDevice);
   if (e == hipSuccess && !ents.empty()) e = hipMemcpy(m->jac_ents, ents.data(), ents.size() * sizeof(JacEnt), hipMemcpyHostToDevice);
   if (e == hipSuccess && !emap.empty()) e = hipMemcpy(m->jac_emap, emap.data(), emap.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return e;
+  // the IK kernel's: active columns (n_act <= n_jx <= DEXR_POSE_MAXJ) and the (row, column) of each packed triangle entry
+  // (at most DEXR_POSE_MAXJ entries in all, so an index and an end fit eight bits)
+  std::vector<int32_t> act_col, col_act((size_t)h.n_in + 1, -1);
+  std::vector<uint32_t> act_rng;
+  for (int c = 0; c < h.n_in; ++c)
+    if (colptr[c + 1] > colptr[c]) {
+      col_act[c] = (int32_t)act_col.size();
+      act_col.push_back(c);
+      act_rng.push_back((uint32_t)colptr[c] | ((uint32_t)colptr[c + 1] << 8));
+    }
+  std::vector<uint2> tri;
+  for (size_t i = 0; i < act_col.size(); ++i)
+    for (size_t j = 0; j <= i; ++j) {
+      bool shared = false;  // is some link below a joint of column i and a joint of column j?
+      for (int a = colptr[act_col[i]]; a < colptr[act_col[i] + 1]; ++a)
+        for (int b = colptr[act_col[j]]; b < colptr[act_col[j] + 1]; ++b)
+          if (std::max(ents[a].link_begin, ents[b].link_begin) < std::min(ents[a].sub_end, ents[b].sub_end)) shared = true;
+      uint2 d;
+      d.x = (uint32_t)(i | (j << 6));
+      d.y = shared ? (act_rng[i] | (act_rng[j] << 16)) : 0u;
+      tri.push_back(d);
+    }
+  m->n_act = (int)act_col.size();
+  e = hipMalloc((void**)&m->ik_act_rng, (act_rng.size() + 1) * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&m->ik_col_act, col_act.size() * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&m->ik_tri, (tri.size() + 1) * sizeof(uint2));
+  if (e == hipSuccess && !act_rng.empty()) e = hipMemcpy(m->ik_act_rng, act_rng.data(), act_rng.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(m->ik_col_act, col_act.data(), col_act.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !tri.empty()) e = hipMemcpy(m->ik_tri, tri.data(), tri.size() * sizeof(uint2), hipMemcpyHostToDevice);
   return e;
 }
 
@@ -1035,6 +1279,44 @@ int launch_wrench(const dexr_pose_model* m, int64_t B, const T* x, const T* fixe
                        xdot, frame, gl, ga, gx, gxd);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "link wrench kernel launch failed: %s", hipGetErrorString(e));
+  return DEXR_OK;
+}
+
+// checks shared by the two entry points of dexr_ik.h: < 0 error, 1 nothing to do, 0 go on
+int check_ik_call(const dexr_pose_model* m, int64_t B, const void* x, const void* fixed, int32_t frame, const void* el, const void* ea,
+                  const void* wl, const void* wa, double damping, const void* dx) {
+  if (!m) return dexr_set_error(DEXR_ERR_INVALID, "null pose model");
+  if (B < 0) return dexr_set_error(DEXR_ERR_INVALID, "negative batch size");
+  if (frame != DEXR_JAC_WORLD_ALIGNED && frame != DEXR_JAC_LOCAL) return dexr_set_error(DEXR_ERR_INVALID, "unknown frame %d (0: world aligned, 1: local)", frame);
+  if (!(damping > 0.0) || damping > 1.7976931348623157e308) return dexr_set_error(DEXR_ERR_INVALID, "damping must be finite and > 0, got %g", damping);
+  if (B == 0) return 1;
+  if (!el && !ea) return dexr_set_error(DEXR_ERR_INVALID, "the linear and the angular error are both NULL");
+  if (wl && !el) return dexr_set_error(DEXR_ERR_INVALID, "w_lin given without err_lin");
+  if (wa && !ea) return dexr_set_error(DEXR_ERR_INVALID, "w_ang given without err_ang");
+  if (!dx && m->h.n_in > 0) return dexr_set_error(DEXR_ERR_INVALID, "dx_out is NULL");
+  return check_call(m, B, x, fixed);
+}
+
+template <typename T>
+int launch_ik(const dexr_pose_model* m, int64_t B, const T* x, const T* fixed, int frame, const T* el, const T* ea, const T* wl, const T* wa,
+              T lambda, T* dx, hipStream_t st) {
+  // values of a frame's region: a, o per joint driven by x | IK_LINK per link | packed H | g, y, the factor's diagonal; odd, so
+  // that the frames of a wave start in different banks
+  const int n_act = m->n_act;
+  const int stride = (6 * m->n_jx + IK_LINK * m->h.n_link + n_act * (n_act + 1) / 2 + 3 * n_act) | 1;
+  const size_t per_frame = ((size_t)m->h.n_slot * 12 + (size_t)stride) * sizeof(T);
+  int nl = IK_FRAMES;
+  while (nl > 1 && per_frame * nl > 64 * 1024) nl /= 2;  // (float64, 64 active columns and 64 links: 2 frames)
+  if (per_frame * nl > 64 * 1024)
+    return dexr_set_error(DEXR_ERR_UNSUPPORTED, "the table needs %zu B of LDS per frame: one frame does not fit a block", per_frame);
+  const int64_t blocks = (B + nl - 1) / nl;
+  if (blocks > 0x7fffffffLL) return dexr_set_error(DEXR_ERR_INVALID, "batch too large for one launch");
+  hipLaunchKernelGGL(pose_ik_kernel<T>, dim3((unsigned)blocks), dim3(nl * IK_FANOUT), per_frame * nl, st, (const JointD<T>*)tables_of<T>(m).joints,
+                     (const LinkD<T>*)tables_of<T>(m).links, args_of<T>(m, B), (const JacEnt*)m->jac_ents,
+                     (const uint32_t*)m->ik_act_rng, (const int32_t*)m->ik_col_act, (const uint2*)m->ik_tri, m->n_jx, n_act, stride, frame, x,
+                     fixed, el, ea, wl, wa, lambda, dx);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "link IK step kernel launch failed: %s", hipGetErrorString(e));
   return DEXR_OK;
 }
 
@@ -1192,6 +1474,9 @@ void dexr_pose_model_destroy(dexr_pose_model* m) {
   if (m->jac_colptr) (void)hipFree(m->jac_colptr);
   if (m->jac_ents) (void)hipFree(m->jac_ents);
   if (m->jac_emap) (void)hipFree(m->jac_emap);
+  if (m->ik_act_rng) (void)hipFree(m->ik_act_rng);
+  if (m->ik_col_act) (void)hipFree(m->ik_col_act);
+  if (m->ik_tri) (void)hipFree(m->ik_tri);
   delete m;
 }
 
@@ -1349,6 +1634,36 @@ int dexr_link_velocities_vjp(const dexr_pose_model* m, int64_t B, const double* 
   if (c) return c < 0 ? c : DEXR_OK;
   if (grad_x_out && !xdot && m->h.n_in > 0) return dexr_set_error(DEXR_ERR_INVALID, "xdot is NULL");
   return host_wrench(m, B, x, fixed, xdot, frame, grad_lin, grad_ang, grad_x_out, grad_xdot_out);
+}
+
+// ---- include/dexr_ik.h -------------------------------------------------------------------------------------------------------
+int dexr_link_ik_step_dev(const dexr_pose_model* m, int64_t B, const float* x, const float* fixed, int32_t frame, const float* err_lin,
+                          const float* err_ang, const float* w_lin, const float* w_ang, float damping, float* dx_out, void* stream) {
+  const int c = check_ik_call(m, B, x, fixed, frame, err_lin, err_ang, w_lin, w_ang, (double)damping, dx_out);
+  if (c) return c < 0 ? c : DEXR_OK;
+  return launch_ik<float>(m, B, x, fixed, frame, err_lin, err_ang, w_lin, w_ang, damping, dx_out, (hipStream_t)stream);
+}
+
+int dexr_link_ik_step(const dexr_pose_model* m, int64_t B, const double* x, const double* fixed, int32_t frame, const double* err_lin,
+                      const double* err_ang, const double* w_lin, const double* w_ang, double damping, double* dx_out) {
+  const int c = check_ik_call(m, B, x, fixed, frame, err_lin, err_ang, w_lin, w_ang, damping, dx_out);
+  if (c) return c < 0 ? c : DEXR_OK;
+  const size_t nx = (size_t)B * m->h.n_in * sizeof(double), nf = (size_t)B * m->h.n_fixed * sizeof(double);
+  const size_t nw = (size_t)B * m->h.n_link * sizeof(double);
+  DevBuf dx, dfix, dl, da, dwl, dwa, dout;
+  POSE_HIP(dx.put(x, nx));
+  POSE_HIP(dfix.put(fixed, nf));
+  if (err_lin) POSE_HIP(dl.put(err_lin, 3 * nw));
+  if (err_ang) POSE_HIP(da.put(err_ang, 3 * nw));
+  if (w_lin) POSE_HIP(dwl.put(w_lin, nw));
+  if (w_ang) POSE_HIP(dwa.put(w_ang, nw));
+  POSE_HIP(dout.put(nullptr, nx));
+  const int rc = launch_ik<double>(m, B, (const double*)dx.p, (const double*)dfix.p, frame, (const double*)dl.p, (const double*)da.p,
+                                   (const double*)dwl.p, (const double*)dwa.p, damping, (double*)dout.p, nullptr);
+  if (rc) return rc;
+  POSE_HIP(hipDeviceSynchronize());
+  if (nx) POSE_HIP(hipMemcpy(dx_out, dout.p, nx, hipMemcpyDeviceToHost));
+  return DEXR_OK;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-"""Batched link Jacobians, link velocities and link wrenches on the GPU (include/dexr_jacobian.h, include/dexr_wrench.h,
-csrc/dexr_pose.hip), for torch tensors.
+"""Batched link Jacobians, link velocities, link wrenches and damped least-squares IK steps on the GPU
+(include/dexr_jacobian.h, include/dexr_wrench.h, include/dexr_ik.h, csrc/dexr_pose.hip), for torch tensors.
 
 ``link_jacobians(optimizer, q, link_names)`` gives ``J = d(pose)/dq`` of any links at the optimiser's variables -- the matrix a
 differential-IK or impedance step, a null-space projector, a manipulability measure or a contact Jacobian needs -- and
@@ -17,7 +17,15 @@ LOCAL_WORLD_ALIGNED), ``frame="local"`` rotates both into the link's own axes (p
 ``link_wrenches(optimizer, q, link_names, force, torque)`` is the transposed product ``tau = sum_l Jlin_l^T force_l +
 Jang_l^T torque_l`` -- joint torques of contact forces, a differential-IK step of the J^T kind -- again without the matrix.
 
-The outputs carry NO autograd graph: the functions of this module build no derivative of theirs.  Where a loss needs
+``link_ik_step(optimizer, q, link_names, pos_err, rot_err, ..., damping=lam)`` is one damped least-squares
+(Levenberg-Marquardt) step towards per-link displacements and small rotations,
+
+    dq = (sum_l w_pos Jlin_l^T Jlin_l + w_rot Jang_l^T Jang_l + lam I)^-1 (sum_l w_pos Jlin_l^T pos_err_l + w_rot Jang_l^T rot_err_l),
+
+built, factorised (Cholesky) and solved inside one kernel: neither J nor the normal matrix reaches memory.
+
+The outputs carry NO autograd graph: the functions of this module build no derivative of theirs (a VJP of the IK step is not
+built either).  Where a loss needs
 gradients, differentiate through ``autograd.link_poses`` (poses) or ``autograd.link_velocities`` (velocities, in q and qdot:
 the kinematic Hessian contracted on both sides by a kernel of its own).
 """
@@ -27,12 +35,14 @@ from . import _lib
 from .autograd import _check_poses
 
 _FRAMES = {"world": _lib.JAC_WORLD_ALIGNED, "local": _lib.JAC_LOCAL}
+_REQUIRED = object()  # damping of an IK step: an argument without a default that may still be passed by position
 
 
-def _check(n_in, n_fixed, q, qdot, fixed_qpos, link_names, frame, kin, what="q", rows=()):
+def _check(n_in, n_fixed, q, qdot, fixed_qpos, link_names, frame, kin, what="q", rows=(), weights=()):
     """Every argument rule -- the frame, types, dtypes, shapes, the link names and last the device -- before anything
     touches the GPU.  Returns the DEXR_JAC_* value of `frame`.  `qdot`: False where the call takes none.  `rows`: (name,
-    tensor) pairs that must be float32 (B, L, 3) tensors on q's device, one row per link."""
+    tensor) pairs that must be float32 (B, L, 3) tensors on q's device, one row per link; `weights`: the same for (B, L)
+    tensors, one value per link."""
     import torch
 
     if not isinstance(frame, str) or frame not in _FRAMES:
@@ -52,13 +62,21 @@ def _check(n_in, n_fixed, q, qdot, fixed_qpos, link_names, frame, kin, what="q",
         if isinstance(q, torch.Tensor) and q.ndim == 2 and not isinstance(link_names, str) and \
                 tuple(t.shape) != (q.shape[0], len(link_names), 3):
             raise ValueError(f"{name} must have shape ({q.shape[0]}, {len(link_names)}, 3), got {tuple(t.shape)}")
+    for name, t in weights:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if isinstance(q, torch.Tensor) and q.ndim == 2 and not isinstance(link_names, str) and \
+                tuple(t.shape) != (q.shape[0], len(link_names)):
+            raise ValueError(f"{name} must have shape ({q.shape[0]}, {len(link_names)}), got {tuple(t.shape)}")
     if not isinstance(link_names, str):
         for n in link_names:
             kin.body_frame_index(n)  # ValueError on an unknown link
     _check_poses(n_in, n_fixed, q, fixed_qpos, link_names, what=what)  # (ends with the device)
     if qdot is not False and qdot.device != q.device:
         raise ValueError(f"the rate is on {qdot.device}, {what} on {q.device}: all tensors must be on one CUDA device")
-    for name, t in rows:
+    for name, t in tuple(rows) + tuple(weights):
         if t.device != q.device:
             raise ValueError(f"{name} is on {t.device}, {what} on {q.device}: all tensors must be on one CUDA device")
     return _FRAMES[frame]
@@ -147,6 +165,47 @@ def _wrenches(model_of, x, fixed_qpos, link_names, frame, force, torque):
     return tau
 
 
+def _ik_rows(pos_err, rot_err, pos_weight, rot_weight, damping, link_names):
+    """the rules of an IK step that need no tensor looked at -> (rows, weights) for _check."""
+    import math
+
+    if pos_err is None and rot_err is None:
+        raise ValueError("pos_err and rot_err are both None: at least one of them is required")
+    if pos_weight is not None and pos_err is None:
+        raise ValueError("pos_weight given without pos_err")
+    if rot_weight is not None and rot_err is None:
+        raise ValueError("rot_weight given without rot_err")
+    if damping is _REQUIRED:
+        raise ValueError("damping is required: a positive finite Python float (there is no default)")
+    if isinstance(damping, bool) or not isinstance(damping, (int, float)) or not math.isfinite(damping) or damping <= 0:
+        raise ValueError(f"damping must be a positive finite Python float, got {damping!r}")
+    if not isinstance(link_names, str) and len(link_names) > 64:
+        raise ValueError(f"an IK step takes at most 64 links (one pose table), got {len(link_names)}: the normal matrix "
+                         "cannot be split across tables")
+    rows = [(n, t) for n, t in (("pos_err", pos_err), ("rot_err", rot_err)) if t is not None]
+    weights = [(n, t) for n, t in (("pos_weight", pos_weight), ("rot_weight", rot_weight)) if t is not None]
+    return rows, weights
+
+
+def _ik_step(model_of, x, fixed_qpos, link_names, frame, pos_err, rot_err, pos_weight, rot_weight, damping):
+    """one table, one launch."""
+    import torch
+
+    B = x.shape[0]
+    xc = x.detach().contiguous()
+    fixed = None if fixed_qpos is None or fixed_qpos.shape[1] == 0 else fixed_qpos.detach().contiguous()
+    el, ea, wl, wa = (None if a is None else a.detach().contiguous() for a in (pos_err, rot_err, pos_weight, rot_weight))
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        model = model_of(list(link_names))
+        dq = torch.empty((B, model.n_in), dtype=torch.float32, device=x.device)
+        if B > 0:
+            model.ik_step_dev(B, xc.data_ptr(), 0 if fixed is None else fixed.data_ptr(), 0 if el is None else el.data_ptr(),
+                              0 if ea is None else ea.data_ptr(), 0 if wl is None else wl.data_ptr(),
+                              0 if wa is None else wa.data_ptr(), float(damping), dq.data_ptr(), frame=frame, stream=stream)
+    return dq
+
+
 def link_jacobians(optimizer, q, link_names, fixed_qpos=None, frame="world", angular=True):
     """Jacobians of `link_names` with respect to the optimiser's variables: q (B, n_opt) float32 CUDA -- what `retarget`
     returns --, fixed_qpos (B, n_fixed) or None -> (jlin (B, L, 3, n_opt), jang of the same shape or None), float32.  Mimic
@@ -178,6 +237,23 @@ def link_wrenches(optimizer, q, link_names, force=None, torque=None, fixed_qpos=
     return _wrenches(optimizer.pose_model, q, fixed_qpos, link_names, f, force, torque)
 
 
+def link_ik_step(optimizer, q, link_names, pos_err=None, rot_err=None, pos_weight=None, rot_weight=None,
+                 damping=_REQUIRED, fixed_qpos=None, frame="world"):
+    """One damped least-squares step of the optimiser's variables at q (B, n_opt) float32 CUDA towards pos_err (B, L, 3), the
+    desired displacement of each link origin, and / or rot_err (B, L, 3), a small rotation vector -- in world axes at the link
+    origin (`frame="world"`) or in the link's own axes (`"local"`) -- weighted per frame and link by pos_weight, rot_weight
+    (B, L) float32 >= 0 (None: 1) -> dq (B, n_opt) float32, the minimiser of
+    1/2 sum_l (w_pos |Jlin_l dq - pos_err_l|^2 + w_rot |Jang_l dq - rot_err_l|^2) + 1/2 damping |dq|^2.
+    `damping` is required: a positive finite Python float (there is no default on purpose).  Mimic joints fold onto their
+    source's column, fixed joints do not move, columns no joint reads are exact zeros.  At most 64 links: the normal matrix
+    lives in one kernel and cannot be split across tables.  The output carries no autograd graph (a VJP of the step is not
+    built); clamp q + dq to the joint limits in torch."""
+    rows, weights = _ik_rows(pos_err, rot_err, pos_weight, rot_weight, damping, link_names)
+    n_fixed = len(optimizer.idx_pin2fixed)
+    f = _check(optimizer.opt_dof, n_fixed, q, False, fixed_qpos, link_names, frame, optimizer.robot.kin, rows=rows, weights=weights)
+    return _ik_step(optimizer.pose_model, q, fixed_qpos, link_names, f, pos_err, rot_err, pos_weight, rot_weight, damping)
+
+
 def robot_link_jacobians(robot, qpos, link_names, frame="world", angular=True):
     """The same for a full robot qpos (B, robot.dof) in dof order: (jlin (B, L, 3, dof), jang or None).  Every joint is a
     column of its own here, mimic joints included (RobotWrapper does not know about them)."""
@@ -197,5 +273,13 @@ def robot_link_wrenches(robot, qpos, link_names, force=None, torque=None, frame=
     return _wrenches(robot.pose_model, qpos, None, link_names, f, force, torque)
 
 
-__all__ = ["link_jacobians", "link_velocities", "link_wrenches", "robot_link_jacobians", "robot_link_velocities",
-           "robot_link_wrenches"]
+def robot_link_ik_step(robot, qpos, link_names, pos_err=None, rot_err=None, pos_weight=None, rot_weight=None,
+                       damping=_REQUIRED, frame="world"):
+    """dq (B, robot.dof) for a full robot qpos in dof order; every joint is a column of its own.  At most 64 links."""
+    rows, weights = _ik_rows(pos_err, rot_err, pos_weight, rot_weight, damping, link_names)
+    f = _check(robot.dof, 0, qpos, False, None, link_names, frame, robot.kin, what="qpos", rows=rows, weights=weights)
+    return _ik_step(robot.pose_model, qpos, None, link_names, f, pos_err, rot_err, pos_weight, rot_weight, damping)
+
+
+__all__ = ["link_jacobians", "link_velocities", "link_wrenches", "link_ik_step", "robot_link_jacobians",
+           "robot_link_velocities", "robot_link_wrenches", "robot_link_ik_step"]
