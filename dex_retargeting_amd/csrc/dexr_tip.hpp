@@ -168,10 +168,12 @@ struct TipTabT {
 #undef DEXR_TIP_BATCH2
   // the LDS constants to their places, then the pins (the subtraction of the origin frame stays the float32 operation on the
   // device it was: x - 0.f is x bit for bit where there is no origin frame)
+  // VIA_VGPR = false: what hold() / hold_off() returned in scalar registers is taken as it is (see pin_joint0)
+  template <bool VIA_VGPR = true>
   __device__ __forceinline__ void place(const Stage& st, int fo, R* lds, int lane) {
     place_lds(st, lds, lane);
-    pin_joint0(st);
-    pin_off(st, fo);
+    pin_joint0<VIA_VGPR, VIA_VGPR>(st);
+    pin_off<VIA_VGPR>(st, fo);
   }
   __device__ __forceinline__ void place_lds(const Stage& st, R* lds, int lane) {
     if (lane < 36) lds[lane] = st.fill;
@@ -183,7 +185,9 @@ struct TipTabT {
   // outputs are scalar registers of unknown contents), the second one through a VGPR is redundant.  Who drops it is decided by
   // the census of the code objects: dexr_kernel's chain instantiations (plain / EXT) spill 30 / 33 SGPRs without it and 38 / 39
   // with it (34 / 42 before the batches), dexr_tip32_kernel's loop comes out instruction for instruction as it was with it.
-  template <bool ROT = true>
+  // BOX = false does the same for the box, pin_off<false> for the task frame's offset (batch 2): dexr_tip32_kernel, whose
+  // prologue then has no VGPR round trip (v_mov, s_nop, v_readfirstlane) for a value that arrived in a scalar register.
+  template <bool ROT = true, bool BOX = true>
   __device__ __forceinline__ void pin_joint0(const Stage& st) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -197,15 +201,17 @@ struct TipTabT {
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      lo[k] = tip_pin(st.lo[k]);
-      hi[k] = tip_pin(st.hi[k]);
+      lo[k] = BOX ? tip_pin(st.lo[k]) : st.lo[k];
+      hi[k] = BOX ? tip_pin(st.hi[k]) : st.hi[k];
     }
   }
-  __device__ __forceinline__ void pin_off(const Stage& st, int fo) {  // ... and batch 2
+  // ... and batch 2 (p0 is formed by a vector subtraction: it comes back through tip_pin's readfirstlane either way)
+  template <bool OFF = true>
+  __device__ __forceinline__ void pin_off(const Stage& st, int fo) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       p0[i] = tip_pin(st.X0[9 + i] - (fo >= 0 ? st.oo[i] : 0.f));
-      off[i] = tip_pin(st.ot[i]);
+      off[i] = OFF ? tip_pin(st.ot[i]) : st.ot[i];
     }
   }
 };

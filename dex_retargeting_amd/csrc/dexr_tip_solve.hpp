@@ -122,7 +122,6 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
   int h_t = kp.h_task[hrow], h_o = kp.h_origin[hrow];
   tt.fetch_off(tb, ft, fo, st);
   tt.hold_off(st, h_t, h_o);
-  api0 = tip_pin(api0);
 
   // Level 3, the lane's frame: start point / regularisation target from last_qpos, the term's target from the keypoints or the
   // ref_value row -- every load issued here, waited for once, behind the pins
@@ -144,18 +143,22 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
     }
   }
 
-  tt.place(st, fo, W + 64 * kp.lds_terms, lane);
+  // (joint 0, the box and the tip offset stay in the scalar registers hold() / hold_off() returned them in; so does api0)
+  tt.place<false>(st, fo, W + 64 * kp.lds_terms, lane);
 
-  // constants of the pass, pinned in SGPRs (the values read by every pass first)
-  const float k_delta = tip_pin(a_delta), k_lam0 = tip_pin(a_lam0), k_tol = tip_pin(a_tol), k_blind_tol = tip_pin(a_blind_tol);
-  const float k_step_cap = tip_pin(a_step_cap);
-  const float tip_beta = tip_pin(a_huber), tip_ibeta = tip_pin(1.f / a_huber);
-  const float tip_w = tip_pin(a_inv_norm), tip_nw = tip_pin(a_newton != 0 ? 1.f : 0.f);
-  const float k_lam_fastdec = tip_pin(a_lam_fastdec), k_lam_jump = tip_pin(a_lam_jump), k_lam_recover = tip_pin(a_lam_recover);
-  const float k_stall_ratio = tip_pin(a_stall_ratio);
-  const int k_stall_from = tip_pin(a_stall_from), k_max_blind = tip_pin(a_max_blind), k_max_iter = tip_pin(a_max_iter);
-  // ... and what the pass derives from them, formed once (the same single multiplications dexr_kernel does) and pinned as
-  // well: left to the compiler each becomes a VGPR that is live through the whole loop
+  // constants of the pass, pinned in SGPRs (the values read by every pass first).  The options are pinned since level 0: the
+  // empty asm there made each a scalar register of unknown contents, which the compiler can neither fold back into the
+  // kernel-argument load nor load again inside the pass -- a second pin through a VGPR (v_mov, s_nop, v_readfirstlane) adds nothing
+  const float k_delta = a_delta, k_lam0 = a_lam0, k_tol = a_tol, k_blind_tol = a_blind_tol;
+  const float k_step_cap = a_step_cap;
+  const float tip_beta = a_huber, tip_ibeta = tip_pin(1.f / a_huber);
+  const float tip_w = a_inv_norm, tip_nw = tip_pin(a_newton != 0 ? 1.f : 0.f);
+  const float k_lam_fastdec = a_lam_fastdec, k_lam_jump = a_lam_jump, k_lam_recover = a_lam_recover;
+  const float k_stall_ratio = a_stall_ratio;
+  const int k_stall_from = a_stall_from, k_max_blind = a_max_blind, k_max_iter = a_max_iter;
+  // ... and what the pass derives from them, formed once (the same single multiplications dexr_kernel does) by a vector
+  // operation and pinned through tip_pin's readfirstlane (behind a bare "+s" the compiler refuses the copy from the vector
+  // register): left to the compiler each becomes a VGPR that is live through the whole loop
   const float k_2delta = tip_pin(2.f * k_delta), k_10tol = tip_pin(10.f * k_tol);
   const float k_stall_max = tip_pin(a_stall_cap * k_tol);
   const float k_lam_ok = tip_pin(fmax(2.f * k_delta, 10.f * k_lam0)), k_lam_ok_half = tip_pin(0.5f * fmax(2.f * k_delta, 10.f * k_lam0));
@@ -224,23 +227,21 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
   while (__any(has)) {
     // (a) step from the kept model; joints held at a bound by the gradient sign are taken out of the system
     float g[4], H[10], d[4];
-    uint32_t freemask = 0;
+    // (which joints are free: four lane masks as the comparisons deliver them -- the pair conditions are scalar ANDs of them,
+    // not bits of an integer in a VGPR that are set and tested again)
+    bool fr[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float gk = gs[k];
       const bool act = (bool)(((int)(x[k] <= tt.lo[k]) & (int)(gk > 0)) | ((int)(x[k] >= tt.hi[k]) & (int)(gk < 0)));
-      if (!act) freemask |= 1u << k;
+      fr[k] = !act;
       g[k] = !act ? gk : 0.f;
     }
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
-      const bool fr = (freemask >> rr) & 1u;
 #pragma unroll
-      for (int cc = 0; cc < rr; ++cc) {
-        const bool fc = (freemask >> cc) & 1u;
-        H[hidx(rr, cc)] = (fr && fc) ? Hs[hidx(rr, cc)] : 0.f;
-      }
-      H[hidx(rr, rr)] = fr ? Hs[hidx(rr, rr)] + k_2delta + lam : 1.f;
+      for (int cc = 0; cc < rr; ++cc) H[hidx(rr, cc)] = (fr[rr] && fr[cc]) ? Hs[hidx(rr, cc)] : 0.f;
+      H[hidx(rr, rr)] = fr[rr] ? Hs[hidx(rr, rr)] + k_2delta + lam : 1.f;
     }
     float gm[4];
 #pragma unroll
