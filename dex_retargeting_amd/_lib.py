@@ -61,6 +61,8 @@ JAC_WORLD_ALIGNED, JAC_LOCAL = 0, 1  # DEXR_JAC_*
 WRENCH_EXPORTS = ["dexr_link_wrenches_dev", "dexr_link_velocities_vjp_dev", "dexr_link_wrenches", "dexr_link_velocities_vjp"]
 # include/dexr_ik.h (one damped least-squares IK step on a pose table): a list of its own
 IK_EXPORTS = ["dexr_link_ik_step_dev", "dexr_link_ik_step"]
+# include/dexr_ik_solve.h (the step iterated inside one kernel, to pose targets and with joint limits): a list of its own
+IK_SOLVE_EXPORTS = ["dexr_link_ik_solve_dev", "dexr_link_ik_solve"]
 UNIQUE_ID_BYTES = 128
 
 
@@ -144,6 +146,10 @@ def load() -> C.CDLL:
     lib.dexr_link_velocities_vjp.argtypes = [vp, i64, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p]
     lib.dexr_link_ik_step_dev.argtypes = [vp, i64, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_float, vp, vp]
     lib.dexr_link_ik_step.argtypes = [vp, i64, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, f64p]
+    lib.dexr_link_ik_solve_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp,
+                                           vp, vp]
+    lib.dexr_link_ik_solve.argtypes = [vp, i64, f64p, f64p, f64p, f64p, f64p, f64p, f64p, f64p, C.c_double, C.c_double, C.c_double,
+                                       C.c_int32, f64p, i32p, f64p]
     _lib = lib
     return lib
 
@@ -451,6 +457,17 @@ class PoseModel:
                                            err_ang_ptr or None, w_lin_ptr or None, w_ang_ptr or None, float(damping),
                                            dx_ptr or None, stream or None))
 
+    def ik_solve_dev(self, B: int, x0_ptr: int, fixed_ptr: int, tgt_pos_ptr: int, tgt_rot_ptr: int, w_lin_ptr: int, w_ang_ptr: int,
+                     lo_ptr: int, hi_ptr: int, damping: float, max_iters: int, x_ptr: int, iters_ptr: int = 0, err_ptr: int = 0,
+                     tol: float = 0.0, max_step: float = 0.0, stream: int = 0):
+        """x0 (B, n_in), tgt_pos (B, n_link, 3) and / or tgt_rot (B, n_link, 3, 3) world targets (0: absent), w_lin, w_ang
+        (B, n_link) or 0, lo, hi (n_in) or both 0 -> x (B, n_in), iters (B) int32 or 0, err (B) or 0: up to max_iters damped
+        least-squares steps inside one launch, every entry written; x may alias x0 (dexr_link_ik_solve_dev)."""
+        check(load().dexr_link_ik_solve_dev(self._h, B, x0_ptr or None, fixed_ptr or None, tgt_pos_ptr or None, tgt_rot_ptr or None,
+                                            w_lin_ptr or None, w_ang_ptr or None, lo_ptr or None, hi_ptr or None, float(damping),
+                                            float(max_step), float(tol), int(max_iters), x_ptr or None, iters_ptr or None,
+                                            err_ptr or None, stream or None))
+
     # host-pointer entry points: float64 in, float64 arithmetic, float64 out ----------------------------
     def _host_inputs(self, x, fixed):
         x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float64)))
@@ -542,6 +559,37 @@ class PoseModel:
                                        _ptr(err_lin, C.c_double), _ptr(err_ang, C.c_double), _ptr(w_lin, C.c_double),
                                        _ptr(w_ang, C.c_double), float(damping), _ptr(dx, C.c_double)))
         return dx
+
+    def ik_solve(self, x0, fixed=None, tgt_pos=None, tgt_rot=None, w_lin=None, w_ang=None, lo=None, hi=None, damping=None,
+                 max_iters=None, tol: float = 0.0, max_step: float = 0.0):
+        """-> (x (B, n_in) float64, iters (B) int32, err (B) float64) (dexr_link_ik_solve); at least one of tgt_pos
+        (B, n_link, 3), tgt_rot (B, n_link, 3, 3) is required, w_lin, w_ang (B, n_link) or None weigh them, lo, hi (n_in) are
+        given together or not at all, damping > 0 and max_iters in 1..256 are required."""
+        if damping is None:
+            raise ValueError("damping is required")
+        if max_iters is None:
+            raise ValueError("max_iters is required")
+        x0, fixed, B = self._host_inputs(x0, fixed)
+        tgt_pos = self._host_link_rows(tgt_pos, B, "tgt_pos")
+        if tgt_rot is not None:
+            tgt_rot = np.ascontiguousarray(tgt_rot, dtype=np.float64)
+            if tgt_rot.shape != (B, self.n_link, 3, 3):
+                raise ValueError(f"tgt_rot must have shape ({B}, {self.n_link}, 3, 3), got {tgt_rot.shape}")
+        w_lin, w_ang = self._host_link_weights(w_lin, B, "w_lin"), self._host_link_weights(w_ang, B, "w_ang")
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        if lo is not None:
+            lo, hi = (np.ascontiguousarray(a, dtype=np.float64) for a in (lo, hi))
+            if lo.shape != (self.n_in,) or hi.shape != (self.n_in,):
+                raise ValueError(f"lo and hi must have shape ({self.n_in},), got {lo.shape} and {hi.shape}")
+        x = np.zeros((B, self.n_in), dtype=np.float64)
+        iters = np.zeros(B, dtype=np.int32)
+        err = np.zeros(B, dtype=np.float64)
+        check(load().dexr_link_ik_solve(self._h, B, _ptr(x0, C.c_double), _ptr(fixed, C.c_double), _ptr(tgt_pos, C.c_double),
+                                        _ptr(tgt_rot, C.c_double), _ptr(w_lin, C.c_double), _ptr(w_ang, C.c_double),
+                                        _ptr(lo, C.c_double), _ptr(hi, C.c_double), float(damping), float(max_step), float(tol),
+                                        int(max_iters), _ptr(x, C.c_double), _ptr(iters, C.c_int32), _ptr(err, C.c_double)))
+        return x, iters, err
 
     def wrenches(self, x, fixed=None, force=None, torque=None, frame: int = 0):
         """-> tau (B, n_in) float64 (dexr_link_wrenches); at least one of force, torque (B, n_link, 3) is required."""

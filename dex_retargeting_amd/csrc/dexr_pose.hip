@@ -57,6 +57,13 @@
 //                                   links below both; then a Cholesky factorisation and two triangular solves in LDS, one barrier
 //                                   per column, and the scatter to dx with zeros in the columns no joint reads.
 // Every sum has a fixed order that does not depend on the frames per block: a frame's row is the same bits at every B.
+//
+// IK SOLVE TO LINK POSE TARGETS (include/dexr_ik_solve.h): that step iterated inside one kernel (pose_ik_solve_kernel<T>), the same
+// block and the same two phases with a loop around them.  A frame's current x lives in LDS and the walk reads it there; phase A
+// also forms the errors towards the world targets, their sum E_k and the frame's stop decision; phase B sums g first, freezes the
+// columns on a bound that g pushes outward (a 64-bit mask per frame in LDS, one more barrier), then builds H, solves, limits the
+// step, moves and clamps.  A stopped frame keeps walking through the barriers without working or writing; the block leaves the
+// loop on the AND of its frames' stop flags or at max_iters.  Phase B's sums and the factorisation are helpers both kernels call.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -68,6 +75,7 @@
 #include "dexr.h"
 #include "dexr_math.hpp"
 #include "dexr_ik.h"
+#include "dexr_ik_solve.h"
 #include "dexr_jacobian.h"
 #include "dexr_pose.h"
 #include "dexr_wrench.h"
@@ -802,6 +810,104 @@ __device__ __forceinline__ void ik_column(const T* a, bool rev, const T* p, T c[
   }
 }
 
+// entry (i, j), i >= j, of the packed lower triangle of H before the damping, from what phase A parked for the frame (pk): summed
+// over the joints of the two columns and the links below both.  d.x: i | j << 6; d.y: the entries of column i, of column j (both
+// empty where no link is below both)
+template <typename T>
+__device__ __forceinline__ T ik_h_entry(const uint2 d, const JacEnt* __restrict__ ents, const T* pk, int lbase) {
+  const int i0 = d.y & 255, i1 = (d.y >> 8) & 255, j0 = (d.y >> 16) & 255, j1 = d.y >> 24;
+  T s = T(0);
+  for (int ii = i0; ii < i1; ++ii) {
+    const JacEnt A = ents[ii];
+    const T* a = pk + 6 * A.xi;
+    const bool arev = A.type == DEXR_POSE_REVOLUTE;
+    for (int jj = j0; jj < j1; ++jj) {
+      const JacEnt Bn = ents[jj];
+      const int lo = A.link_begin > Bn.link_begin ? A.link_begin : Bn.link_begin;
+      const int hi = A.sub_end < Bn.sub_end ? A.sub_end : Bn.sub_end;
+      if (lo >= hi) continue;
+      const T* c = pk + 6 * Bn.xi;
+      const bool brev = Bn.type == DEXR_POSE_REVOLUTE;
+      const T mm = mult_of(A, T(0)) * mult_of(Bn, T(0));
+      const T aa = (arev && brev) ? dot_fma(a, c) : T(0);
+      T sl = T(0);
+      for (int l = lo; l < hi; ++l) {
+        const T* q = pk + lbase + IK_LINK * l;
+        T u[3], v[3];
+        ik_column(a, arev, q, u);
+        ik_column(c, brev, q, v);
+        sl = fma(q[9], dot_fma(u, v), fma(q[10], aa, sl));
+      }
+      s = fma(mm, sl, s);
+    }
+  }
+  return s;
+}
+
+// entry of g of the active column whose entries are r (first | end << 8)
+template <typename T>
+__device__ __forceinline__ T ik_g_entry(uint32_t r, const JacEnt* __restrict__ ents, const T* pk, int lbase) {
+  T s = T(0);
+  for (int ii = r & 255; ii < (int)(r >> 8); ++ii) {
+    const JacEnt A = ents[ii];
+    const T* a = pk + 6 * A.xi;
+    const bool arev = A.type == DEXR_POSE_REVOLUTE;
+    T sl = T(0);
+    for (int l = A.link_begin; l < A.sub_end; ++l) {
+      const T* q = pk + lbase + IK_LINK * l;
+      T u[3];
+      ik_column(a, arev, q, u);
+      sl += dot_fma(u, q + 3);
+      if (arev) sl += dot_fma(a, q + 6);
+    }
+    s = fma(mult_of(A, T(0)), sl, s);
+  }
+  return s;
+}
+
+// H (packed lower triangle) -> its Cholesky factor below the diagonal and dg, then L y = g and L^T dx = y: dx takes the place of
+// g.  One barrier per column and sweep, 3 n_act in all, reached by every thread of the block whatever `work` is: a frame that
+// has nothing to solve passes work = false and only keeps the barriers
+template <typename T>
+__device__ __forceinline__ void ik_factor_solve(T* H, T* g, T* y, T* dg, int n_act, int t, bool work) {
+  // Cholesky, one column per step: every thread of the frame forms the pivot itself (row k is complete), then its rows
+  for (int k = 0; k < n_act; ++k) {
+    if (work) {
+      const T* rk = H + k * (k + 1) / 2;
+      T skk = rk[k];
+      for (int p = 0; p < k; ++p) skk = fma(-rk[p], rk[p], skk);
+      const T d = sqrt(skk);
+      if (t == 0) dg[k] = d;
+      for (int i = k + 1 + t; i < n_act; i += IK_FANOUT) {
+        T* ri = H + i * (i + 1) / 2;
+        T s = ri[k];
+        for (int p = 0; p < k; ++p) s = fma(-ri[p], rk[p], s);
+        ri[k] = s / d;
+      }
+    }
+    __syncthreads();
+  }
+  // L y = g, by columns
+  for (int k = 0; k < n_act; ++k) {
+    if (work) {
+      const T yk = g[k] / dg[k];
+      if (t == 0) y[k] = yk;
+      for (int i = k + 1 + t; i < n_act; i += IK_FANOUT) g[i] = fma(-H[i * (i + 1) / 2 + k], yk, g[i]);
+    }
+    __syncthreads();
+  }
+  // L^T dx = y, by rows of L from the last; dx takes the place of g
+  for (int k = n_act - 1; k >= 0; --k) {
+    if (work) {
+      const T zk = y[k] / dg[k];
+      if (t == 0) g[k] = zk;
+      const T* rk = H + k * (k + 1) / 2;
+      for (int p = t; p < k; p += IK_FANOUT) y[p] = fma(-rk[p], zk, y[p]);
+    }
+    __syncthreads();
+  }
+}
+
 // Per frame one region of LDS, [frame][stride] with an odd stride: a, o per joint driven by x | IK_LINK values per sorted link |
 // H, the packed lower triangle over the active columns (row i starts at i (i + 1) / 2), overwritten by its Cholesky factor below
 // the diagonal | g (later dx) | y | the factor's diagonal.  Every entry of H and g is summed by one thread in table order, and
@@ -887,91 +993,235 @@ __global__ void __launch_bounds__(IK_FANOUT * IK_FRAMES) pose_ik_kernel(const Jo
   T* y = pk + ybase;
   T* dg = pk + dbase;
   for (int e = t; e < n_tri; e += IK_FANOUT) {  // H[i, j], i >= j: the joints of the two columns, the links below both
-    const uint2 d = tri[e];  // x: i | j << 6; y: the entries of column i, of column j (both empty where no link is below both)
-    const int i = d.x & 63, j = d.x >> 6;
-    const int i0 = d.y & 255, i1 = (d.y >> 8) & 255, j0 = (d.y >> 16) & 255, j1 = d.y >> 24;
-    T s = T(0);
-    for (int ii = i0; ii < i1; ++ii) {
-      const JacEnt A = ents[ii];
-      const T* a = pk + 6 * A.xi;
-      const bool arev = A.type == DEXR_POSE_REVOLUTE;
-      for (int jj = j0; jj < j1; ++jj) {
-        const JacEnt Bn = ents[jj];
-        const int lo = A.link_begin > Bn.link_begin ? A.link_begin : Bn.link_begin;
-        const int hi = A.sub_end < Bn.sub_end ? A.sub_end : Bn.sub_end;
-        if (lo >= hi) continue;
-        const T* c = pk + 6 * Bn.xi;
-        const bool brev = Bn.type == DEXR_POSE_REVOLUTE;
-        const T mm = mult_of(A, T(0)) * mult_of(Bn, T(0));
-        const T aa = (arev && brev) ? dot_fma(a, c) : T(0);
-        T sl = T(0);
-        for (int l = lo; l < hi; ++l) {
-          const T* q = pk + lbase + IK_LINK * l;
-          T u[3], v[3];
-          ik_column(a, arev, q, u);
-          ik_column(c, brev, q, v);
-          sl = fma(q[9], dot_fma(u, v), fma(q[10], aa, sl));
-        }
-        s = fma(mm, sl, s);
-      }
-    }
-    H[e] = i == j ? s + lambda : s;
+    const uint2 d = tri[e];
+    const T s = ik_h_entry(d, ents, pk, lbase);
+    H[e] = (d.x & 63) == (d.x >> 6) ? s + lambda : s;
   }
-  for (int i = t; i < n_act; i += IK_FANOUT) {  // g[i]
-    const uint32_t r = act_rng[i];
-    T s = T(0);
-    for (int ii = r & 255; ii < (int)(r >> 8); ++ii) {
-      const JacEnt A = ents[ii];
-      const T* a = pk + 6 * A.xi;
-      const bool arev = A.type == DEXR_POSE_REVOLUTE;
-      T sl = T(0);
-      for (int l = A.link_begin; l < A.sub_end; ++l) {
-        const T* q = pk + lbase + IK_LINK * l;
-        T u[3];
-        ik_column(a, arev, q, u);
-        sl += dot_fma(u, q + 3);
-        if (arev) sl += dot_fma(a, q + 6);
-      }
-      s = fma(mult_of(A, T(0)), sl, s);
-    }
-    g[i] = s;
-  }
+  for (int i = t; i < n_act; i += IK_FANOUT) g[i] = ik_g_entry(act_rng[i], ents, pk, lbase);
   __syncthreads();
-  // Cholesky, one column per step: every thread of the frame forms the pivot itself (row k is complete), then its rows
-  for (int k = 0; k < n_act; ++k) {
-    const T* rk = H + k * (k + 1) / 2;
-    T skk = rk[k];
-    for (int p = 0; p < k; ++p) skk = fma(-rk[p], rk[p], skk);
-    const T d = sqrt(skk);
-    if (t == 0) dg[k] = d;
-    for (int i = k + 1 + t; i < n_act; i += IK_FANOUT) {
-      T* ri = H + i * (i + 1) / 2;
-      T s = ri[k];
-      for (int p = 0; p < k; ++p) s = fma(-ri[p], rk[p], s);
-      ri[k] = s / d;
-    }
-    __syncthreads();
-  }
-  // L y = g, by columns
-  for (int k = 0; k < n_act; ++k) {
-    const T yk = g[k] / dg[k];
-    if (t == 0) y[k] = yk;
-    for (int i = k + 1 + t; i < n_act; i += IK_FANOUT) g[i] = fma(-H[i * (i + 1) / 2 + k], yk, g[i]);
-    __syncthreads();
-  }
-  // L^T dx = y, by rows of L from the last; dx takes the place of g
-  for (int k = n_act - 1; k >= 0; --k) {
-    const T zk = y[k] / dg[k];
-    if (t == 0) g[k] = zk;
-    const T* rk = H + k * (k + 1) / 2;
-    for (int p = t; p < k; p += IK_FANOUT) y[p] = fma(-rk[p], zk, y[p]);
-    __syncthreads();
-  }
+  ik_factor_solve(H, g, y, dg, n_act, t, true);
   if (first + fr < P.B) {
     T* o = dx + (first + fr) * P.n_in;
     for (int c = t; c < P.n_in; c += IK_FANOUT) {
       const int a = col_act[c];
       o[c] = a >= 0 ? g[a] : T(0);
+    }
+  }
+}
+
+// ---- IK solve to link pose targets (include/dexr_ik_solve.h): the step kernel's two phases inside an iteration loop ------------------
+__device__ __forceinline__ float atan2_t(float y, float x) { return atan2f(y, x); }
+__device__ __forceinline__ double atan2_t(double y, double x) { return atan2(y, x); }
+
+// phase A's share of one link at world pose (R, p): its errors towards the target row, parked as the step kernel parks them (d:
+// p_l, the weighted errors as a force and a moment in world axes, the two weights); returns w_lin |e_lin|^2 + w_ang |e_ang|^2
+template <typename T>
+__device__ __forceinline__ T ik_link_target(const T R[9], const T p[3], int64_t row, const T* __restrict__ tp, const T* __restrict__ tr,
+                                            const T* __restrict__ wl, const T* __restrict__ wa, T* d) {
+  T f[3] = {T(0), T(0), T(0)}, m[3] = {T(0), T(0), T(0)}, wf = T(0), wm = T(0), E = T(0);
+  if (tp) {
+    wf = wl ? wl[row] : T(1);
+    T e[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      e[i] = tp[row * 3 + i] - p[i];
+      f[i] = e[i] * wf;
+    }
+    E = wf * dot_fma(e, e);
+  }
+  if (tr) {
+    wm = wa ? wa[row] : T(1);
+    const T* G = tr + row * 9;
+    T M[9];  // M = G R^T: the rotation that takes the link to its target, in world axes
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) M[3 * i + j] = fma(G[3 * i + 2], R[3 * j + 2], fma(G[3 * i + 1], R[3 * j + 1], G[3 * i] * R[3 * j]));
+    const T v[3] = {T(0.5) * (M[7] - M[5]), T(0.5) * (M[2] - M[6]), T(0.5) * (M[3] - M[1])};
+    const T c = T(0.5) * (M[0] + M[4] + M[8] - T(1)), s = sqrt(dot_fma(v, v));
+    const T k = s > T(1e-6) ? atan2_t(s, c) / s : T(1);
+    T e[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      e[i] = v[i] * k;
+      m[i] = e[i] * wm;
+    }
+    E = fma(wm, dot_fma(e, e), E);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    d[i] = p[i];
+    d[3 + i] = f[i];
+    d[6 + i] = m[i];
+  }
+  d[9] = wf;
+  d[10] = wm;
+  return E;
+}
+
+// LDS of a block: the sixteen partial frozen masks of every frame (64 bits each: thread t holds the bits of the active columns
+// t, t + 16, ...; their OR is the frame's mask) | a stop flag and an iteration count per frame | the fork slots | per frame the
+// step kernel's region with the frame's current x (all n_in columns) and E behind it.  The walk reads x from LDS through
+// joint_move unchanged: row stride `stride`, row index = lane.
+//
+// THE LOOP CANNOT HANG: it runs k = 0 .. max_iters at most; every barrier sits outside every condition that differs between the
+// threads of a block (4 + 3 n_act per iteration); a frame that has stopped (or an idle lane of a ragged last block: stopped from
+// the start) does no work and writes nothing but walks through the same barriers; the one early exit is taken on the AND of all
+// stop flags of the block, which every thread reads from LDS after the same barrier, and at k == max_iters every flag is set.
+template <typename T>
+__global__ void __launch_bounds__(IK_FANOUT * IK_FRAMES) pose_ik_solve_kernel(const JointD<T>* __restrict__ joints, const LinkD<T>* __restrict__ links,
+                                                                             PoseArgs<T> P, const JacEnt* __restrict__ ents,
+                                                                             const uint32_t* __restrict__ act_rng,
+                                                                             const int32_t* __restrict__ act_col, const uint2* __restrict__ tri,
+                                                                             int n_jx, int n_act, int stride, const T* x0,
+                                                                             const T* __restrict__ fixed, const T* __restrict__ tp,
+                                                                             const T* __restrict__ tr, const T* __restrict__ wl,
+                                                                             const T* __restrict__ wa, const T* __restrict__ lo,
+                                                                             const T* __restrict__ hi, T lambda, T max_step, T tol2,
+                                                                             int max_iters, T* x_out, int32_t* __restrict__ iters_out,
+                                                                             T* __restrict__ err_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pose_lds[];
+  const int nl = blockDim.x / IK_FANOUT, tid = threadIdx.x;  // nl: frames of this block
+  unsigned long long* part = reinterpret_cast<unsigned long long*>(pose_lds);  // [nl][IK_FANOUT]
+  int32_t* stopf = reinterpret_cast<int32_t*>(part + nl * IK_FANOUT);           // [nl]
+  int32_t* itv = stopf + nl;                                                    // [nl]
+  T* slots = reinterpret_cast<T*>(itv + nl);
+  T* park = slots + (size_t)P.n_slot * 12 * nl;
+  const int lbase = 6 * n_jx, n_tri = n_act * (n_act + 1) / 2;
+  const int hbase = lbase + IK_LINK * P.n_link, gbase = hbase + n_tri, ybase = gbase + n_act, dbase = ybase + n_act;
+  const int xbase = dbase + n_act, ebase = xbase + P.n_in;
+  const int64_t first = (int64_t)blockIdx.x * nl;
+  const int fr = tid / IK_FANOUT, t = tid % IK_FANOUT;
+  const bool inb = first + fr < P.B;
+  T* pk = park + (size_t)fr * stride;
+  T* H = pk + hbase;
+  T* g = pk + gbase;
+  T* y = pk + ybase;
+  T* dg = pk + dbase;
+  T* xs = pk + xbase;
+  for (int c = t; c < P.n_in; c += IK_FANOUT) xs[c] = inb ? x0[(first + fr) * P.n_in + c] : T(0);
+  bool stopped = first + tid >= P.B;  // (read by the walking lanes alone) idle lanes of a ragged last block never start
+  if (tid < nl) {
+    stopf[tid] = stopped ? 1 : 0;
+    itv[tid] = 0;
+    park[(size_t)tid * stride + ebase] = T(0);
+  }
+  __syncthreads();
+  PoseArgs<T> PL = P;  // the walk's view of x: the frames' rows in LDS
+  PL.n_in = stride;
+  const T* xl = park + xbase;
+  const T* fixl = fixed + first * P.n_fixed;
+  for (int k = 0; k <= max_iters; ++k) {
+    if (tid < nl && !stopped) {  // phase A: lane = frame; FK at x_k, the errors, E_k and the stop test
+      const int lane = tid;
+      T* pa = park + (size_t)lane * stride;
+      const int64_t b = first + lane;
+      T E = T(0);
+      for (int l = 0; l < P.n_base; ++l) {  // links on the fixed base: below no joint, but their error counts
+        const LinkD<T>& L = links[l];
+        E += ik_link_target(L.R, L.p, b * P.n_link + L.out, tp, tr, wl, wa, pa + lbase + IK_LINK * l);
+      }
+      Xf<T> tf;
+#pragma unroll
+      for (int i = 0; i < 9; ++i) tf.R[i] = (i % 4 == 0) ? T(1) : T(0);
+      tf.p[0] = tf.p[1] = tf.p[2] = T(0);
+      int xi = 0;
+      for (int j = 0; j < P.n_joint; ++j) {
+        const JointD<T>& J = joints[j];
+        T a[3];
+        joint_step(J, PL, xl, fixl, (int64_t)lane, slots, nl, lane, tf, a);
+        if (J.src_kind == DEXR_POSE_SRC_X) {
+          T* d = pa + 6 * xi;
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {
+            d[i] = a[i];
+            d[3 + i] = tf.p[i];
+          }
+          ++xi;
+        }
+        for (int l = J.link_begin; l < J.link_end; ++l) {
+          const LinkD<T>& L = links[l];
+          T R[9], p[3];
+          link_pose(L, tf, R, p);
+          E += ik_link_target(R, p, b * P.n_link + L.out, tp, tr, wl, wa, pa + lbase + IK_LINK * l);
+        }
+      }
+      itv[lane] = k;
+      pa[ebase] = E;
+      if (E <= tol2 || k == max_iters) {  // (a NaN compares false: a spoiled frame runs to max_iters)
+        stopped = true;
+        stopf[lane] = 1;
+      }
+    }
+    __syncthreads();
+    bool all = true;  // the block's vote, the same in every thread
+    for (int f = 0; f < nl; ++f) all = all && stopf[f] != 0;
+    if (all) break;
+    const bool work = stopf[fr] == 0;
+    // phase B: g first, with the freeze test of its columns
+    unsigned long long mine = 0;
+    if (work) {
+      for (int i = t; i < n_act; i += IK_FANOUT) {
+        T s = ik_g_entry(act_rng[i], ents, pk, lbase);
+        if (lo) {
+          const int c = act_col[i];
+          const T xc = xs[c];
+          if ((xc <= lo[c] && s < T(0)) || (xc >= hi[c] && s > T(0))) {
+            mine |= 1ull << i;
+            s = T(0);
+          }
+        }
+        g[i] = s;
+      }
+    }
+    part[fr * IK_FANOUT + t] = mine;
+    __syncthreads();
+    unsigned long long frozen = 0;
+    for (int u = 0; u < IK_FANOUT; ++u) frozen |= part[fr * IK_FANOUT + u];
+    if (work) {
+      for (int e = t; e < n_tri; e += IK_FANOUT) {  // a frozen column's row and column of H are the identity's
+        const uint2 d = tri[e];
+        const int i = d.x & 63, j = d.x >> 6;
+        T h;
+        if (((frozen >> i) | (frozen >> j)) & 1ull) {
+          h = i == j ? T(1) : T(0);
+        } else {
+          h = ik_h_entry(d, ents, pk, lbase);
+          if (i == j) h += lambda;
+        }
+        H[e] = h;
+      }
+    }
+    __syncthreads();
+    ik_factor_solve(H, g, y, dg, n_act, t, work);
+    if (work) {  // limit the step, move, clamp: by comparisons, a NaN stays a NaN
+      T scale = T(1);
+      if (max_step > T(0)) {
+        T m = T(0);
+        for (int i = 0; i < n_act; ++i) {
+          const T a = fabs(g[i]);
+          m = a > m ? a : m;
+        }
+        if (m > max_step) scale = max_step / m;
+      }
+      for (int i = t; i < n_act; i += IK_FANOUT) {
+        const int c = act_col[i];
+        T v = xs[c] + g[i] * scale;
+        if (lo) {
+          const T l = lo[c], h = hi[c];
+          v = v < l ? l : (v > h ? h : v);
+        }
+        xs[c] = v;
+      }
+    }
+    __syncthreads();
+  }
+  if (inb) {
+    T* o = x_out + (first + fr) * P.n_in;
+    for (int c = t; c < P.n_in; c += IK_FANOUT) o[c] = xs[c];
+    if (t == 0) {
+      if (iters_out) iters_out[first + fr] = itv[fr];
+      if (err_out) err_out[first + fr] = sqrt(pk[ebase]);
     }
   }
 }
@@ -999,6 +1249,7 @@ struct dexr_pose_model {
   int n_act = 0;
   uint32_t* ik_act_rng = nullptr;  // (n_act): the entries of active column i in jac_ents, first | end << 8
   int32_t* ik_col_act = nullptr;   // (n_in): active index of column c, -1: no joint reads it
+  int32_t* ik_act_col = nullptr;   // (n_act): the column of active index i (the solve kernel's way back)
   uint2* ik_tri = nullptr;         // (n_act (n_act + 1) / 2), packed lower-triangle entry (i, j), i >= j: x = i | j << 6,
                                    // y = the entry ranges of the two columns, first_i | end_i << 8 | first_j << 16 | end_j << 24,
                                    // all 0 where no link is below a joint of each (the entry of H is a structural zero)
@@ -1196,9 +1447,11 @@ hipError_t upload_jacobian_index(const dexr_pose_header& h, const std::vector<de
   e = hipMalloc((void**)&m->ik_act_rng, (act_rng.size() + 1) * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc((void**)&m->ik_col_act, col_act.size() * sizeof(int32_t));
   if (e == hipSuccess) e = hipMalloc((void**)&m->ik_tri, (tri.size() + 1) * sizeof(uint2));
+  if (e == hipSuccess) e = hipMalloc((void**)&m->ik_act_col, (act_col.size() + 1) * sizeof(int32_t));
   if (e == hipSuccess && !act_rng.empty()) e = hipMemcpy(m->ik_act_rng, act_rng.data(), act_rng.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->ik_col_act, col_act.data(), col_act.size() * sizeof(int32_t), hipMemcpyHostToDevice);
   if (e == hipSuccess && !tri.empty()) e = hipMemcpy(m->ik_tri, tri.data(), tri.size() * sizeof(uint2), hipMemcpyHostToDevice);
+  if (e == hipSuccess && !act_col.empty()) e = hipMemcpy(m->ik_act_col, act_col.data(), act_col.size() * sizeof(int32_t), hipMemcpyHostToDevice);
   return e;
 }
 
@@ -1317,6 +1570,50 @@ int launch_ik(const dexr_pose_model* m, int64_t B, const T* x, const T* fixed, i
                      fixed, el, ea, wl, wa, lambda, dx);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "link IK step kernel launch failed: %s", hipGetErrorString(e));
+  return DEXR_OK;
+}
+
+// checks shared by the two entry points of dexr_ik_solve.h: < 0 error, 1 nothing to do, 0 go on
+int check_ik_solve_call(const dexr_pose_model* m, int64_t B, const void* x0, const void* fixed, const void* tp, const void* tr, const void* wl,
+                        const void* wa, const void* lo, const void* hi, double damping, double max_step, double tol, int32_t max_iters,
+                        const void* x_out) {
+  const double big = 1.7976931348623157e308;
+  if (!m) return dexr_set_error(DEXR_ERR_INVALID, "null pose model");
+  if (B < 0) return dexr_set_error(DEXR_ERR_INVALID, "negative batch size");
+  if (!(damping > 0.0) || damping > big) return dexr_set_error(DEXR_ERR_INVALID, "damping must be finite and > 0, got %g", damping);
+  if (!(max_step >= 0.0) || max_step > big) return dexr_set_error(DEXR_ERR_INVALID, "max_step must be finite and >= 0 (0: no limit), got %g", max_step);
+  if (!(tol >= 0.0) || tol > big) return dexr_set_error(DEXR_ERR_INVALID, "tol must be finite and >= 0, got %g", tol);
+  if (max_iters < 1 || max_iters > 256) return dexr_set_error(DEXR_ERR_INVALID, "max_iters must be in 1..256, got %d", max_iters);
+  if ((lo == nullptr) != (hi == nullptr)) return dexr_set_error(DEXR_ERR_INVALID, "lo and hi must both be given or both be NULL");
+  if (B == 0) return 1;
+  if (!tp && !tr) return dexr_set_error(DEXR_ERR_INVALID, "tgt_pos and tgt_rot are both NULL");
+  if (wl && !tp) return dexr_set_error(DEXR_ERR_INVALID, "w_lin given without tgt_pos");
+  if (wa && !tr) return dexr_set_error(DEXR_ERR_INVALID, "w_ang given without tgt_rot");
+  if (!x_out) return dexr_set_error(DEXR_ERR_INVALID, "x_out is NULL");
+  if (!x0 && m->h.n_in > 0) return dexr_set_error(DEXR_ERR_INVALID, "x0 is NULL");
+  return check_call(m, B, x0, fixed);
+}
+
+template <typename T>
+int launch_ik_solve(const dexr_pose_model* m, int64_t B, const T* x0, const T* fixed, const T* tp, const T* tr, const T* wl, const T* wa,
+                    const T* lo, const T* hi, T lambda, T max_step, T tol, int max_iters, T* x_out, int32_t* iters, T* err, hipStream_t st) {
+  // the step kernel's region with the frame's x (n_in values) and E behind it; odd.  Per frame in front of it: sixteen 64-bit
+  // partial masks, a stop flag and an iteration count
+  const int n_act = m->n_act;
+  const int stride = (6 * m->n_jx + IK_LINK * m->h.n_link + n_act * (n_act + 1) / 2 + 3 * n_act + m->h.n_in + 1) | 1;
+  const size_t per_frame = ((size_t)m->h.n_slot * 12 + (size_t)stride) * sizeof(T) + IK_FANOUT * sizeof(unsigned long long) + 2 * sizeof(int32_t);
+  int nl = IK_FRAMES;
+  while (nl > 1 && per_frame * nl > 64 * 1024) nl /= 2;  // (float64, 64 active columns and 64 links: 2 frames)
+  if (per_frame * nl > 64 * 1024)
+    return dexr_set_error(DEXR_ERR_UNSUPPORTED, "the table needs %zu B of LDS per frame: one frame does not fit a block", per_frame);
+  const int64_t blocks = (B + nl - 1) / nl;
+  if (blocks > 0x7fffffffLL) return dexr_set_error(DEXR_ERR_INVALID, "batch too large for one launch");
+  hipLaunchKernelGGL(pose_ik_solve_kernel<T>, dim3((unsigned)blocks), dim3(nl * IK_FANOUT), per_frame * nl, st, (const JointD<T>*)tables_of<T>(m).joints,
+                     (const LinkD<T>*)tables_of<T>(m).links, args_of<T>(m, B), (const JacEnt*)m->jac_ents, (const uint32_t*)m->ik_act_rng,
+                     (const int32_t*)m->ik_act_col, (const uint2*)m->ik_tri, m->n_jx, n_act, stride, x0, fixed, tp, tr, wl, wa, lo, hi, lambda,
+                     max_step, tol * tol, max_iters, x_out, iters, err);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "link IK solve kernel launch failed: %s", hipGetErrorString(e));
   return DEXR_OK;
 }
 
@@ -1477,6 +1774,7 @@ void dexr_pose_model_destroy(dexr_pose_model* m) {
   if (m->ik_act_rng) (void)hipFree(m->ik_act_rng);
   if (m->ik_col_act) (void)hipFree(m->ik_col_act);
   if (m->ik_tri) (void)hipFree(m->ik_tri);
+  if (m->ik_act_col) (void)hipFree(m->ik_act_col);
   delete m;
 }
 
@@ -1663,6 +1961,47 @@ int dexr_link_ik_step(const dexr_pose_model* m, int64_t B, const double* x, cons
   if (rc) return rc;
   POSE_HIP(hipDeviceSynchronize());
   if (nx) POSE_HIP(hipMemcpy(dx_out, dout.p, nx, hipMemcpyDeviceToHost));
+  return DEXR_OK;
+}
+
+// ---- include/dexr_ik_solve.h -----------------------------------------------------------------------------------------------
+int dexr_link_ik_solve_dev(const dexr_pose_model* m, int64_t B, const float* x0, const float* fixed, const float* tgt_pos,
+                           const float* tgt_rot, const float* w_lin, const float* w_ang, const float* lo, const float* hi, float damping,
+                           float max_step, float tol, int32_t max_iters, float* x_out, int32_t* iters_out, float* err_out, void* stream) {
+  const int c = check_ik_solve_call(m, B, x0, fixed, tgt_pos, tgt_rot, w_lin, w_ang, lo, hi, (double)damping, (double)max_step, (double)tol,
+                                    max_iters, x_out);
+  if (c) return c < 0 ? c : DEXR_OK;
+  return launch_ik_solve<float>(m, B, x0, fixed, tgt_pos, tgt_rot, w_lin, w_ang, lo, hi, damping, max_step, tol, max_iters, x_out, iters_out,
+                                err_out, (hipStream_t)stream);
+}
+
+int dexr_link_ik_solve(const dexr_pose_model* m, int64_t B, const double* x0, const double* fixed, const double* tgt_pos,
+                       const double* tgt_rot, const double* w_lin, const double* w_ang, const double* lo, const double* hi, double damping,
+                       double max_step, double tol, int32_t max_iters, double* x_out, int32_t* iters_out, double* err_out) {
+  const int c = check_ik_solve_call(m, B, x0, fixed, tgt_pos, tgt_rot, w_lin, w_ang, lo, hi, damping, max_step, tol, max_iters, x_out);
+  if (c) return c < 0 ? c : DEXR_OK;
+  const size_t nx = (size_t)B * m->h.n_in * sizeof(double), nf = (size_t)B * m->h.n_fixed * sizeof(double);
+  const size_t nw = (size_t)B * m->h.n_link * sizeof(double), nb = (size_t)m->h.n_in * sizeof(double);
+  DevBuf dx, dfix, dp, dr, dwl, dwa, dlo, dhi, dout, dit, derr;
+  POSE_HIP(dx.put(x0, nx));
+  POSE_HIP(dfix.put(fixed, nf));
+  if (tgt_pos) POSE_HIP(dp.put(tgt_pos, 3 * nw));
+  if (tgt_rot) POSE_HIP(dr.put(tgt_rot, 9 * nw));
+  if (w_lin) POSE_HIP(dwl.put(w_lin, nw));
+  if (w_ang) POSE_HIP(dwa.put(w_ang, nw));
+  if (lo) POSE_HIP(dlo.put(lo, nb));
+  if (hi) POSE_HIP(dhi.put(hi, nb));
+  POSE_HIP(dout.put(nullptr, nx));
+  POSE_HIP(dit.put(nullptr, (size_t)B * sizeof(int32_t)));
+  POSE_HIP(derr.put(nullptr, (size_t)B * sizeof(double)));
+  const int rc = launch_ik_solve<double>(m, B, (const double*)dx.p, (const double*)dfix.p, (const double*)dp.p, (const double*)dr.p,
+                                         (const double*)dwl.p, (const double*)dwa.p, (const double*)dlo.p, (const double*)dhi.p, damping,
+                                         max_step, tol, max_iters, (double*)dout.p, (int32_t*)dit.p, (double*)derr.p, nullptr);
+  if (rc) return rc;
+  POSE_HIP(hipDeviceSynchronize());
+  if (nx) POSE_HIP(hipMemcpy(x_out, dout.p, nx, hipMemcpyDeviceToHost));
+  if (iters_out) POSE_HIP(hipMemcpy(iters_out, dit.p, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (err_out) POSE_HIP(hipMemcpy(err_out, derr.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost));
   return DEXR_OK;
 }
 

@@ -24,6 +24,10 @@ Jang_l^T torque_l`` -- joint torques of contact forces, a differential-IK step o
 
 built, factorised (Cholesky) and solved inside one kernel: neither J nor the normal matrix reaches memory.
 
+``link_ik_solve(optimizer, q0, link_names, target_pos, target_rot, ..., damping=lam, max_iters=n, limits=lim)`` iterates that
+step inside ONE kernel towards world pose targets, with joint limits (bound variables the step pushes outward are frozen) and
+a per-frame stop: -> (q, iters, err) (include/dexr_ik_solve.h).
+
 The outputs carry NO autograd graph: the functions of this module build no derivative of theirs (a VJP of the IK step is not
 built either).  Where a loss needs
 gradients, differentiate through ``autograd.link_poses`` (poses) or ``autograd.link_velocities`` (velocities, in q and qdot:
@@ -206,6 +210,83 @@ def _ik_step(model_of, x, fixed_qpos, link_names, frame, pos_err, rot_err, pos_w
     return dq
 
 
+def _ik_solve_rules(q0, link_names, target_pos, target_rot, pos_weight, rot_weight, damping, max_iters, tol, max_step, limits, n_in):
+    """the rules of an IK solve beyond those of _check (the targets' types and shapes, the scalars, the limits) -> (rows,
+    weights) for _check.  Nothing here looks at a device; the device rule of the targets and the limits comes after _check."""
+    import math
+
+    import torch
+
+    if target_pos is None and target_rot is None:
+        raise ValueError("target_pos and target_rot are both None: at least one of them is required")
+    if pos_weight is not None and target_pos is None:
+        raise ValueError("pos_weight given without target_pos")
+    if rot_weight is not None and target_rot is None:
+        raise ValueError("rot_weight given without target_rot")
+    if damping is _REQUIRED:
+        raise ValueError("damping is required: a positive finite Python float (there is no default)")
+    if isinstance(damping, bool) or not isinstance(damping, (int, float)) or not math.isfinite(damping) or damping <= 0:
+        raise ValueError(f"damping must be a positive finite Python float, got {damping!r}")
+    if max_iters is _REQUIRED:
+        raise ValueError("max_iters is required: a Python int in 1..256 (there is no default)")
+    if isinstance(max_iters, bool) or not isinstance(max_iters, int) or not 1 <= max_iters <= 256:
+        raise ValueError(f"max_iters must be a Python int in 1..256, got {max_iters!r}")
+    for name, v in (("tol", tol), ("max_step", max_step)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{name} must be a finite Python float >= 0, got {v!r}")
+    if not isinstance(link_names, str) and len(link_names) > 64:
+        raise ValueError(f"an IK solve takes at most 64 links (one pose table), got {len(link_names)}: the normal matrix "
+                         "cannot be split across tables")
+    if target_rot is not None:
+        if not isinstance(target_rot, torch.Tensor):
+            raise ValueError("target_rot must be a torch tensor")
+        if target_rot.dtype != torch.float32:
+            raise ValueError(f"target_rot must be float32, got {target_rot.dtype}")
+        if isinstance(q0, torch.Tensor) and q0.ndim == 2 and not isinstance(link_names, str) and \
+                tuple(target_rot.shape) != (q0.shape[0], len(link_names), 3, 3):
+            raise ValueError(f"target_rot must have shape ({q0.shape[0]}, {len(link_names)}, 3, 3), got {tuple(target_rot.shape)}")
+    if limits is not None:
+        if not isinstance(limits, torch.Tensor):
+            raise ValueError("limits must be a torch tensor")
+        if limits.dtype != torch.float32:
+            raise ValueError(f"limits must be float32, got {limits.dtype}")
+        if tuple(limits.shape) != (n_in, 2):
+            raise ValueError(f"limits must have shape ({n_in}, 2), lower and upper bound per variable, got {tuple(limits.shape)}")
+    rows = [("target_pos", target_pos)] if target_pos is not None else []
+    weights = [(n, t) for n, t in (("pos_weight", pos_weight), ("rot_weight", rot_weight)) if t is not None]
+    return rows, weights
+
+
+def _ik_solve(model_of, n_in, n_fixed, kin, x0, what, fixed_qpos, link_names, target_pos, target_rot, pos_weight, rot_weight, damping,
+              max_iters, tol, max_step, limits):
+    """every rule, then one table and one launch."""
+    import torch
+
+    rows, weights = _ik_solve_rules(x0, link_names, target_pos, target_rot, pos_weight, rot_weight, damping, max_iters, tol, max_step,
+                                    limits, n_in)
+    _check(n_in, n_fixed, x0, False, fixed_qpos, link_names, "world", kin, what=what, rows=rows, weights=weights)
+    for name, t in (("target_rot", target_rot), ("limits", limits)):
+        if t is not None and t.device != x0.device:
+            raise ValueError(f"{name} is on {t.device}, {what} on {x0.device}: all tensors must be on one CUDA device")
+    B = x0.shape[0]
+    xc = x0.detach().contiguous()
+    fixed = None if fixed_qpos is None or fixed_qpos.shape[1] == 0 else fixed_qpos.detach().contiguous()
+    tp, tr, wl, wa = (None if a is None else a.detach().contiguous() for a in (target_pos, target_rot, pos_weight, rot_weight))
+    lo, hi = (None, None) if limits is None else (limits.detach()[:, 0].contiguous(), limits.detach()[:, 1].contiguous())
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    with torch.cuda.device(x0.device):
+        stream = torch.cuda.current_stream(x0.device).cuda_stream
+        model = model_of(list(link_names))
+        q = torch.empty((B, model.n_in), dtype=torch.float32, device=x0.device)
+        iters = torch.empty((B,), dtype=torch.int32, device=x0.device)
+        err = torch.empty((B,), dtype=torch.float32, device=x0.device)
+        if B > 0:
+            model.ik_solve_dev(B, xc.data_ptr(), ptr(fixed), ptr(tp), ptr(tr), ptr(wl), ptr(wa), ptr(lo), ptr(hi), float(damping),
+                               int(max_iters), q.data_ptr(), iters.data_ptr(), err.data_ptr(), tol=float(tol), max_step=float(max_step),
+                               stream=stream)
+    return q, iters, err
+
+
 def link_jacobians(optimizer, q, link_names, fixed_qpos=None, frame="world", angular=True):
     """Jacobians of `link_names` with respect to the optimiser's variables: q (B, n_opt) float32 CUDA -- what `retarget`
     returns --, fixed_qpos (B, n_fixed) or None -> (jlin (B, L, 3, n_opt), jang of the same shape or None), float32.  Mimic
@@ -254,6 +335,32 @@ def link_ik_step(optimizer, q, link_names, pos_err=None, rot_err=None, pos_weigh
     return _ik_step(optimizer.pose_model, q, fixed_qpos, link_names, f, pos_err, rot_err, pos_weight, rot_weight, damping)
 
 
+def link_ik_solve(optimizer, q0, link_names, target_pos=None, target_rot=None, pos_weight=None, rot_weight=None,
+                  damping=_REQUIRED, max_iters=_REQUIRED, tol=0.0, max_step=0.0, limits=None, fixed_qpos=None):
+    """Inverse kinematics of the optimiser's variables to world pose targets, solved inside ONE launch: from q0 (B, n_opt)
+    float32 CUDA, up to `max_iters` (1..256) damped least-squares steps of `link_ik_step` towards target_pos (B, L, 3), the
+    world positions of the link origins, and / or target_rot (B, L, 3, 3), their world rotations, weighted per frame and link
+    by pos_weight, rot_weight (B, L) float32 >= 0 (None: 1) -> (q (B, n_opt) float32, iters (B) int32, err (B) float32).
+    The rotation error of a link is the rotation vector log(target_rot R^T) in world axes (an error of angle pi reads as 0:
+    keep targets nearer than that).  A frame stops at the first iterate whose err = sqrt(sum_l w_pos |pos error|^2 + w_rot
+    |rot error|^2) is <= tol, or at max_iters; `iters` is the number of steps it took and `err` the error at the q returned.
+    limits (n_opt, 2) float32 or None are lower and upper bounds shared by the batch: a variable on a bound that the step
+    would push outward is frozen before the solve (its step is exactly 0), and every iterate is clamped.  max_step > 0 scales
+    a step so that its largest entry is max_step at most.  `damping` and `max_iters` are required (no defaults on purpose).
+    Mimic joints fold onto their source's column, fixed joints do not move, variables no joint reads come back unchanged.  At
+    most 64 links.  The outputs carry no autograd graph.  One step alone, with errors of your own: `link_ik_step`."""
+    return _ik_solve(optimizer.pose_model, optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, q0, "q", fixed_qpos,
+                     link_names, target_pos, target_rot, pos_weight, rot_weight, damping, max_iters, tol, max_step, limits)
+
+
+def robot_link_ik_solve(robot, qpos0, link_names, target_pos=None, target_rot=None, pos_weight=None, rot_weight=None,
+                        damping=_REQUIRED, max_iters=_REQUIRED, tol=0.0, max_step=0.0, limits=None):
+    """(qpos (B, robot.dof), iters (B), err (B)) for a full robot qpos in dof order; every joint is a column of its own, limits
+    (robot.dof, 2).  At most 64 links."""
+    return _ik_solve(robot.pose_model, robot.dof, 0, robot.kin, qpos0, "qpos", None, link_names, target_pos, target_rot, pos_weight,
+                     rot_weight, damping, max_iters, tol, max_step, limits)
+
+
 def robot_link_jacobians(robot, qpos, link_names, frame="world", angular=True):
     """The same for a full robot qpos (B, robot.dof) in dof order: (jlin (B, L, 3, dof), jang or None).  Every joint is a
     column of its own here, mimic joints included (RobotWrapper does not know about them)."""
@@ -281,5 +388,5 @@ def robot_link_ik_step(robot, qpos, link_names, pos_err=None, rot_err=None, pos_
     return _ik_step(robot.pose_model, qpos, None, link_names, f, pos_err, rot_err, pos_weight, rot_weight, damping)
 
 
-__all__ = ["link_jacobians", "link_velocities", "link_wrenches", "link_ik_step", "robot_link_jacobians",
-           "robot_link_velocities", "robot_link_wrenches", "robot_link_ik_step"]
+__all__ = ["link_jacobians", "link_velocities", "link_wrenches", "link_ik_step", "link_ik_solve", "robot_link_jacobians",
+           "robot_link_velocities", "robot_link_wrenches", "robot_link_ik_step", "robot_link_ik_solve"]
