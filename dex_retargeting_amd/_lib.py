@@ -63,6 +63,11 @@ WRENCH_EXPORTS = ["dexr_link_wrenches_dev", "dexr_link_velocities_vjp_dev", "dex
 IK_EXPORTS = ["dexr_link_ik_step_dev", "dexr_link_ik_step"]
 # include/dexr_ik_solve.h (the step iterated inside one kernel, to pose targets and with joint limits): a list of its own
 IK_SOLVE_EXPORTS = ["dexr_link_ik_solve_dev", "dexr_link_ik_solve"]
+# include/dexr_spheres.h (sphere-pair self-collision on a pose table: distances, their VJP, the fused penalty): a list of its own
+SPHERE_EXPORTS = ["dexr_sphere_model_create", "dexr_sphere_model_destroy", "dexr_sphere_model_info", "dexr_sphere_distances_dev",
+                  "dexr_sphere_distances_vjp_dev", "dexr_sphere_penalty_dev", "dexr_sphere_distances", "dexr_sphere_distances_vjp",
+                  "dexr_sphere_penalty"]
+SPHERE_MAX, SPHERE_MAXPAIR = 128, 8192  # DEXR_SPHERE_*
 UNIQUE_ID_BYTES = 128
 
 
@@ -150,6 +155,16 @@ def load() -> C.CDLL:
                                            vp, vp]
     lib.dexr_link_ik_solve.argtypes = [vp, i64, f64p, f64p, f64p, f64p, f64p, f64p, f64p, f64p, C.c_double, C.c_double, C.c_double,
                                        C.c_int32, f64p, i32p, f64p]
+    lib.dexr_sphere_model_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, i32p, f64p, f64p, C.c_int32, i32p, C.POINTER(vp)]
+    lib.dexr_sphere_model_destroy.argtypes = [vp]
+    lib.dexr_sphere_model_destroy.restype = None
+    lib.dexr_sphere_model_info.argtypes = [vp, i32p, i32p, i32p, i32p]
+    lib.dexr_sphere_distances_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    lib.dexr_sphere_distances_vjp_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    lib.dexr_sphere_penalty_dev.argtypes = [vp, i64, vp, vp, C.c_float, vp, vp, vp, vp]
+    lib.dexr_sphere_distances.argtypes = [vp, i64, f64p, f64p, f64p, f64p]
+    lib.dexr_sphere_distances_vjp.argtypes = [vp, i64, f64p, f64p, f64p, f64p]
+    lib.dexr_sphere_penalty.argtypes = [vp, i64, f64p, f64p, C.c_double, f64p, f64p, f64p]
     _lib = lib
     return lib
 
@@ -615,6 +630,92 @@ class PoseModel:
                                               int(frame), _ptr(grad_lin, C.c_double), _ptr(grad_ang, C.c_double),
                                               _ptr(gx, C.c_double), _ptr(gxd, C.c_double)))
         return gx, gxd
+
+
+class SphereModel:
+    """Owns one dexr_sphere_model (include/dexr_spheres.h): the pose table of a list of links with spheres on them and a list
+    of sphere pairs, resident in HBM.  sphere_link (S) rows of the link list, center (S, 3) in the link's frame, radius (S),
+    pair (P, 2) sphere indices."""
+
+    def __init__(self, pose_blob: bytes, sphere_link, center, radius, pair):
+        lib = load()
+        self._h = C.c_void_p()
+        link = np.ascontiguousarray(sphere_link, dtype=np.int32).reshape(-1)
+        cen = np.ascontiguousarray(center, dtype=np.float64).reshape(-1, 3)
+        rad = np.ascontiguousarray(radius, dtype=np.float64).reshape(-1)
+        pr = np.ascontiguousarray(pair, dtype=np.int32).reshape(-1, 2)
+        if not (len(link) == len(cen) == len(rad)):
+            raise ValueError(f"sphere_link, center and radius must have one row per sphere, got {len(link)}, {len(cen)}, {len(rad)}")
+        buf = C.create_string_buffer(pose_blob, len(pose_blob))
+        check(lib.dexr_sphere_model_create(buf, len(pose_blob), len(link), _ptr(link, C.c_int32), _ptr(cen, C.c_double),
+                                           _ptr(rad, C.c_double), len(pr), _ptr(pr, C.c_int32), C.byref(self._h)))
+        v = [C.c_int32() for _ in range(4)]
+        check(lib.dexr_sphere_model_info(self._h, *[C.byref(a) for a in v]))
+        self.n_in, self.n_fixed, self.n_sphere, self.n_pair = (int(a.value) for a in v)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib is not None:
+            _lib.dexr_sphere_model_destroy(h)
+            self._h = None
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    # device-pointer entry points: float32, C-contiguous, enqueued on `stream` ------------------------
+    def distances_dev(self, B: int, x_ptr: int, fixed_ptr: int, dist_ptr: int, center_ptr: int = 0, stream: int = 0):
+        """x (B, n_in), fixed (B, n_fixed) or 0 -> dist (B, n_pair), center (B, n_sphere, 3) or 0 (dexr_sphere_distances_dev)."""
+        check(load().dexr_sphere_distances_dev(self._h, B, x_ptr or None, fixed_ptr or None, dist_ptr or None, center_ptr or None,
+                                               stream or None))
+
+    def distances_vjp_dev(self, B: int, x_ptr: int, fixed_ptr: int, grad_dist_ptr: int, grad_x_ptr: int, stream: int = 0):
+        """grad_dist (B, n_pair) -> grad_x (B, n_in), every entry written (dexr_sphere_distances_vjp_dev)."""
+        check(load().dexr_sphere_distances_vjp_dev(self._h, B, x_ptr or None, fixed_ptr or None, grad_dist_ptr or None,
+                                                   grad_x_ptr or None, stream or None))
+
+    def penalty_dev(self, B: int, x_ptr: int, fixed_ptr: int, margin: float, pair_weight_ptr: int, energy_ptr: int, grad_x_ptr: int,
+                    stream: int = 0):
+        """margin >= 0, pair_weight (n_pair) or 0 (weights of 1) -> energy (B) and / or grad_x (B, n_in), either may be 0, from
+        one launch (dexr_sphere_penalty_dev)."""
+        check(load().dexr_sphere_penalty_dev(self._h, B, x_ptr or None, fixed_ptr or None, float(margin), pair_weight_ptr or None,
+                                             energy_ptr or None, grad_x_ptr or None, stream or None))
+
+    # host-pointer entry points: float64 in, float64 arithmetic, float64 out ----------------------------
+    _host_inputs = PoseModel._host_inputs
+
+    def distances(self, x, fixed=None, centers: bool = False):
+        """-> dist (B, n_pair), centers (B, n_sphere, 3) or None; float64 (dexr_sphere_distances)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        dist = np.zeros((B, self.n_pair), dtype=np.float64)
+        cen = np.zeros((B, self.n_sphere, 3), dtype=np.float64) if centers else None
+        check(load().dexr_sphere_distances(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), _ptr(dist, C.c_double),
+                                           _ptr(cen, C.c_double)))
+        return dist, cen
+
+    def distances_vjp(self, x, grad_dist, fixed=None):
+        """-> grad_x (B, n_in) float64 (dexr_sphere_distances_vjp)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        grad_dist = np.ascontiguousarray(grad_dist, dtype=np.float64)
+        if grad_dist.shape != (B, self.n_pair):
+            raise ValueError(f"grad_dist must have shape ({B}, {self.n_pair}), got {grad_dist.shape}")
+        gx = np.zeros((B, self.n_in), dtype=np.float64)
+        check(load().dexr_sphere_distances_vjp(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), _ptr(grad_dist, C.c_double),
+                                               _ptr(gx, C.c_double)))
+        return gx
+
+    def penalty(self, x, margin, pair_weight=None, fixed=None, want_energy: bool = True, want_grad: bool = True):
+        """-> (energy (B), grad_x (B, n_in)) float64, None where not wanted (dexr_sphere_penalty)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        if pair_weight is not None:
+            pair_weight = np.ascontiguousarray(pair_weight, dtype=np.float64)
+            if pair_weight.shape != (self.n_pair,):
+                raise ValueError(f"pair_weight must have shape ({self.n_pair},), got {pair_weight.shape}")
+        e = np.zeros(B, dtype=np.float64) if want_energy else None
+        gx = np.zeros((B, self.n_in), dtype=np.float64) if want_grad else None
+        check(load().dexr_sphere_penalty(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), float(margin),
+                                         _ptr(pair_weight, C.c_double), _ptr(e, C.c_double), _ptr(gx, C.c_double)))
+        return e, gx
 
 
 def seq_compose_dev(B: int, T: int, dof_kind, dof_idx, dof_mult, dof_off, n_opt: int, n_fixed: int, qraw_ptr: int,

@@ -375,4 +375,125 @@ def robot_link_velocities(robot, qpos, qvel, link_names, frame="world", angular=
     return _link_velocities(robot.pose_model, qpos, qvel, None, link_names, f, angular)
 
 
-__all__ = ["retarget", "ref_value_from_keypoints", "link_poses", "robot_link_poses", "link_velocities", "robot_link_velocities"]
+# ---- self-collision of a sphere set: distances and the fused penalty, differentiable in q -------------------------------------
+def _make_sphere_functions():
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _SphereDistances(torch.autograd.Function):
+        """Saves x (and fixed) only: the VJP kernel recomputes the walk and the normals."""
+
+        @staticmethod
+        def forward(ctx, x, fixed_qpos, model):
+            B = x.shape[0]
+            xc = x.detach().contiguous()
+            fixed = None if fixed_qpos is None or fixed_qpos.shape[1] == 0 else fixed_qpos.detach().contiguous()
+            dist = torch.empty((B, model.n_pair), dtype=torch.float32, device=x.device)
+            if B > 0:
+                model.distances_dev(B, xc.data_ptr(), 0 if fixed is None else fixed.data_ptr(), dist.data_ptr(), 0,
+                                    stream=torch.cuda.current_stream(x.device).cuda_stream)
+            ctx.model = model
+            ctx.has_fixed = fixed is not None
+            ctx.save_for_backward(*([xc] + ([fixed] if fixed is not None else [])))
+            return dist
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_dist):
+            if not ctx.needs_input_grad[0]:
+                return None, None, None
+            saved = list(ctx.saved_tensors)
+            x = saved[0]
+            fixed = saved[1] if ctx.has_fixed else None
+            B = x.shape[0]
+            gd = grad_dist.detach().to(torch.float32).contiguous()
+            gx = torch.empty_like(x)  # (the kernel writes every entry)
+            if B > 0:
+                ctx.model.distances_vjp_dev(B, x.data_ptr(), 0 if fixed is None else fixed.data_ptr(), gd.data_ptr(), gx.data_ptr(),
+                                            stream=torch.cuda.current_stream(x.device).cuda_stream)
+            return gx, None, None
+
+    class _SpherePenalty(torch.autograd.Function):
+        """The forward launch gives E and dE/dx together where x needs a gradient; backward scales the saved gradient."""
+
+        @staticmethod
+        def forward(ctx, x, fixed_qpos, model, margin, pair_weight):
+            from . import collision
+
+            want = bool(ctx.needs_input_grad[0])
+            e, g = collision._penalty(model, x, fixed_qpos, margin, pair_weight, want_grad=want)
+            ctx.save_for_backward(*([g] if want else []))
+            return e
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_e):
+            if not ctx.needs_input_grad[0] or not ctx.saved_tensors:
+                return None, None, None, None, None
+            return grad_e.to(torch.float32)[:, None] * ctx.saved_tensors[0], None, None, None, None
+
+    return _SphereDistances, _SpherePenalty
+
+
+_SPHERE_FNS = None
+
+
+def _sphere_fns():
+    global _SPHERE_FNS
+    if _SPHERE_FNS is None:
+        _SPHERE_FNS = _make_sphere_functions()
+    return _SPHERE_FNS
+
+
+def sphere_distances(optimizer, q, sphere_set, fixed_qpos=None):
+    """`collision.sphere_distances` with an autograd graph: dist (B, P) float32 of the set's sphere pairs at q (B, n_opt), the
+    same bits; backward is the distance VJP kernel (dexr_sphere_distances_vjp_dev).  Gradients flow to q only; once
+    differentiable."""
+    import torch
+
+    from . import collision
+
+    pairs = collision._check(optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q, fixed_qpos,
+                             sphere_set, "q")
+    with torch.cuda.device(q.device):
+        return _sphere_fns()[0].apply(q, fixed_qpos, optimizer.sphere_model(sphere_set, pairs))
+
+
+def self_collision_penalty(optimizer, q, sphere_set, margin, pair_weight=None, fixed_qpos=None):
+    """`collision.self_collision_penalty` with an autograd graph: E (B,) float32 = sum_p w_p max(0, margin - d_p)^2.  Where q
+    needs a gradient the forward launch computes E and dE/dq together (one launch, the same bits as the no-graph call) and
+    backward is grad_E[:, None] * dE/dq.  Gradients flow to q only (not to pair_weight or fixed_qpos); once differentiable."""
+    import torch
+
+    from . import collision
+
+    pairs = collision._check(optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q, fixed_qpos,
+                             sphere_set, "q", margin, pair_weight, penalty=True)
+    with torch.cuda.device(q.device):
+        return _sphere_fns()[1].apply(q, fixed_qpos, optimizer.sphere_model(sphere_set, pairs), float(margin), pair_weight)
+
+
+def robot_sphere_distances(robot, qpos, sphere_set):
+    """The same for a full robot qpos (B, robot.dof) float32 in dof order."""
+    import torch
+
+    from . import collision
+
+    pairs = collision._check(robot.dof, 0, robot.kin, robot, qpos, None, sphere_set, "qpos")
+    with torch.cuda.device(qpos.device):
+        return _sphere_fns()[0].apply(qpos, None, robot.sphere_model(sphere_set, pairs))
+
+
+def robot_self_collision_penalty(robot, qpos, sphere_set, margin, pair_weight=None):
+    """The same for a full robot qpos (B, robot.dof) float32 in dof order."""
+    import torch
+
+    from . import collision
+
+    pairs = collision._check(robot.dof, 0, robot.kin, robot, qpos, None, sphere_set, "qpos", margin, pair_weight, penalty=True)
+    with torch.cuda.device(qpos.device):
+        return _sphere_fns()[1].apply(qpos, None, robot.sphere_model(sphere_set, pairs), float(margin), pair_weight)
+
+
+__all__ = ["retarget", "ref_value_from_keypoints", "link_poses", "robot_link_poses", "link_velocities", "robot_link_velocities",
+           "sphere_distances", "self_collision_penalty", "robot_sphere_distances", "robot_self_collision_penalty"]

@@ -1658,15 +1658,19 @@ int host_wrench(const dexr_pose_model* m, int64_t B, const double* x, const doub
   return DEXR_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dexr_pose_model_create(const void* blob, size_t nbytes, dexr_pose_model** out) {
-  if (!blob || !out) return dexr_set_error(DEXR_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (nbytes < sizeof(dexr_pose_header)) return dexr_set_error(DEXR_ERR_INVALID, "pose blob truncated: shorter than its header");
+// a pose blob, validated: what dexr_pose_model_create uploads (the sphere model of dexr_spheres.h checks its own arrays between
+// the two steps, so that every argument error comes before the first HIP call)
+struct PoseParsed {
   dexr_pose_header h;
+  std::vector<dexr_pose_joint> js;
+  std::vector<dexr_pose_link> ls;
+  int n_base = 0;
+  uint64_t used[4] = {0, 0, 0, 0};
+};
+
+int parse_pose_blob(const void* blob, size_t nbytes, PoseParsed& parsed) {
+  if (nbytes < sizeof(dexr_pose_header)) return dexr_set_error(DEXR_ERR_INVALID, "pose blob truncated: shorter than its header");
+  dexr_pose_header& h = parsed.h;
   memcpy(&h, blob, sizeof(h));
   if (h.magic != DEXR_POSE_MAGIC) return dexr_set_error(DEXR_ERR_INVALID, "bad magic 0x%08x in pose blob", h.magic);
   if (h.version != DEXR_POSE_VERSION) return dexr_set_error(DEXR_ERR_INVALID, "pose table version %u, library expects %u", h.version, DEXR_POSE_VERSION);
@@ -1678,15 +1682,18 @@ int dexr_pose_model_create(const void* blob, size_t nbytes, dexr_pose_model** ou
   const size_t want = sizeof(h) + (size_t)h.n_joint * sizeof(dexr_pose_joint) + (size_t)h.n_link * sizeof(dexr_pose_link);
   if (nbytes < want) return dexr_set_error(DEXR_ERR_INVALID, "pose blob truncated: %zu B, its header implies %zu B", nbytes, want);
   if (nbytes != want) return dexr_set_error(DEXR_ERR_INVALID, "pose blob size %zu B, its header implies %zu B", nbytes, want);
-  std::vector<dexr_pose_joint> js(h.n_joint);
-  std::vector<dexr_pose_link> ls(h.n_link);
+  std::vector<dexr_pose_joint>& js = parsed.js;
+  std::vector<dexr_pose_link>& ls = parsed.ls;
+  js.resize(h.n_joint);
+  ls.resize(h.n_link);
   const unsigned char* p = static_cast<const unsigned char*>(blob) + sizeof(h);
   if (h.n_joint) memcpy(js.data(), p, (size_t)h.n_joint * sizeof(dexr_pose_joint));
   memcpy(ls.data(), p + (size_t)h.n_joint * sizeof(dexr_pose_joint), (size_t)h.n_link * sizeof(dexr_pose_link));
 
   // links: sorted by parent joint (base first), `out` a permutation
   uint64_t out_seen = 0;
-  int n_base = 0;
+  int& n_base = parsed.n_base;
+  n_base = 0;
   for (int l = 0; l < h.n_link; ++l) {
     const dexr_pose_link& L = ls[l];
     if (L.parent < -1 || L.parent >= h.n_joint) return dexr_set_error(DEXR_ERR_INVALID, "pose link %d: parent joint %d out of range", l, L.parent);
@@ -1697,7 +1704,8 @@ int dexr_pose_model_create(const void* blob, size_t nbytes, dexr_pose_model** ou
   }
   // joints: parent before child, contiguous subtrees, slot discipline, link ranges that match the link records
   std::vector<int> slot_owner(DEXR_POSE_MAXSLOT, -1), sub_end(h.n_joint, 0);
-  uint64_t used[4] = {0, 0, 0, 0};
+  uint64_t* used = parsed.used;
+  used[0] = used[1] = used[2] = used[3] = 0;
   int next_link = n_base;
   for (int k = 0; k < h.n_joint; ++k) {
     const dexr_pose_joint& J = js[k];
@@ -1739,12 +1747,18 @@ int dexr_pose_model_create(const void* blob, size_t nbytes, dexr_pose_model** ou
       if (a != k) return dexr_set_error(DEXR_ERR_INVALID, "pose joint %d: joints are not in depth-first order", c);
     }
   }
+  return DEXR_OK;
+}
 
+int upload_pose_model(const PoseParsed& parsed, dexr_pose_model** out) {
+  const dexr_pose_header& h = parsed.h;
+  const std::vector<dexr_pose_joint>& js = parsed.js;
+  const std::vector<dexr_pose_link>& ls = parsed.ls;
   dexr_pose_model* m = new (std::nothrow) dexr_pose_model();
   if (!m) return dexr_set_error(DEXR_ERR_INVALID, "out of host memory");
   m->h = h;
-  m->n_base = n_base;
-  for (int w = 0; w < 4; ++w) m->unused[w] = ~used[w];
+  m->n_base = parsed.n_base;
+  for (int w = 0; w < 4; ++w) m->unused[w] = ~parsed.used[w];
   std::vector<JointD<float>> jf;
   std::vector<LinkD<float>> lf;
   std::vector<JointD<double>> jd;
@@ -1760,6 +1774,19 @@ int dexr_pose_model_create(const void* blob, size_t nbytes, dexr_pose_model** ou
   }
   *out = m;
   return DEXR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dexr_pose_model_create(const void* blob, size_t nbytes, dexr_pose_model** out) {
+  if (!blob || !out) return dexr_set_error(DEXR_ERR_INVALID, "null argument");
+  *out = nullptr;
+  PoseParsed parsed;
+  const int rc = parse_pose_blob(blob, nbytes, parsed);
+  if (rc) return rc;
+  return upload_pose_model(parsed, out);
 }
 
 void dexr_pose_model_destroy(dexr_pose_model* m) {
@@ -2006,3 +2033,6 @@ int dexr_link_ik_solve(const dexr_pose_model* m, int64_t B, const double* x0, co
 }
 
 }  // extern "C"
+
+// ---- include/dexr_spheres.h: sphere-pair self-collision, a fragment of this unit -----------------------------------------------
+#include "dexr_spheres.hpp"

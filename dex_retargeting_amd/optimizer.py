@@ -79,6 +79,7 @@ class Optimizer:
         self._compiled: Optional[mc.CompiledModel] = None
         self._vjp_model: Optional[_lib.Model] = None  # vjp_model(): the same problem on generic tables
         self._pose_models: dict = {}  # pose_model(): per link tuple
+        self._sphere_models: dict = {}  # sphere_model(): per collision.SphereSet
         # True: compile to the generic table format even when the model fits the fixed-size records (the general kernel
         # then serves it; used by the tests that cross-check that kernel on the shipped robots)
         self.use_generic_tables = False
@@ -111,6 +112,7 @@ class Optimizer:
         self._model = None
         self._vjp_model = None
         self._pose_models = {}
+        self._sphere_models = {}
 
     @property
     def fixed_joint_names(self):
@@ -190,6 +192,18 @@ class Optimizer:
         if key not in self._pose_models:
             self._pose_models[key] = _lib.PoseModel(compile_poses(self.robot.kin, list(key), self.pose_source_map()))
         return self._pose_models[key]
+
+    def sphere_model(self, sphere_set, pairs=None) -> _lib.SphereModel:
+        """Sphere model of a collision.SphereSet on pose_source_map() (include/dexr_spheres.h): gradients land on the
+        optimiser's variables.  `pairs`: the set's own, or collision.default_pairs of this robot.  Cached per sphere set;
+        dropped by set_kinematic_adaptor."""
+        from . import collision
+
+        if sphere_set not in self._sphere_models:
+            if pairs is None:
+                pairs = collision._resolved_pairs(self.robot, sphere_set)
+            self._sphere_models[sphere_set] = collision.build_sphere_model(self.robot.kin, sphere_set, pairs, self.pose_source_map())
+        return self._sphere_models[sphere_set]
 
     def _options(self) -> Optional[_lib.SolveOptions]:
         if all(v is None for v in self.solve_options.values()):

@@ -37,6 +37,7 @@ class RobotWrapper:
         self._qpos = np.zeros((1, self.kin.dof))
         self._fk_models = {}
         self._pose_models = {}
+        self._sphere_models = {}
 
     # ---- properties (robot_wrapper.py:28-52) ------------------------------------------------------
     @property
@@ -112,6 +113,16 @@ class RobotWrapper:
         if key not in self._pose_models:
             self._pose_models[key] = _lib.PoseModel(compile_poses(self.kin, list(key)))
         return self._pose_models[key]
+
+    def sphere_model(self, sphere_set, pairs=None) -> _lib.SphereModel:
+        """Sphere model of a collision.SphereSet over the full qpos in dof order (include/dexr_spheres.h), cached per set."""
+        from . import collision
+
+        if sphere_set not in self._sphere_models:
+            if pairs is None:
+                pairs = collision._resolved_pairs(self, sphere_set)
+            self._sphere_models[sphere_set] = collision.build_sphere_model(self.kin, sphere_set, pairs)
+        return self._sphere_models[sphere_set]
 
     def link_poses(self, qpos: npt.NDArray, link_indices: Sequence[int]) -> np.ndarray:
         """(B, nq) -> (B, L, 4, 4) float64 world poses of the given links (frame ids from get_link_index), positions and
