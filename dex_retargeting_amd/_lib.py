@@ -68,6 +68,10 @@ SPHERE_EXPORTS = ["dexr_sphere_model_create", "dexr_sphere_model_destroy", "dexr
                   "dexr_sphere_distances_vjp_dev", "dexr_sphere_penalty_dev", "dexr_sphere_distances", "dexr_sphere_distances_vjp",
                   "dexr_sphere_penalty"]
 SPHERE_MAX, SPHERE_MAXPAIR = 128, 8192  # DEXR_SPHERE_*
+# include/dexr_resolve.h (the collision-aware posture solve on a sphere model, iterated inside one kernel): a list of its own
+RESOLVE_EXPORTS = ["dexr_sphere_resolve_dev", "dexr_sphere_resolve"]
+RESOLVE_MAXACTIVE, RESOLVE_LAM_UP, RESOLVE_LAM_DOWN, RESOLVE_MAXREJECT = 256, 8, 4, 12  # DEXR_RESOLVE_*
+RESOLVE_CONVERGED, RESOLVE_STALLED, RESOLVE_TRUNCATED = 1, 2, 4  # status bits
 UNIQUE_ID_BYTES = 128
 
 
@@ -165,6 +169,10 @@ def load() -> C.CDLL:
     lib.dexr_sphere_distances.argtypes = [vp, i64, f64p, f64p, f64p, f64p]
     lib.dexr_sphere_distances_vjp.argtypes = [vp, i64, f64p, f64p, f64p, f64p]
     lib.dexr_sphere_penalty.argtypes = [vp, i64, f64p, f64p, C.c_double, f64p, f64p, f64p]
+    lib.dexr_sphere_resolve_dev.argtypes = [vp, i64, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, C.c_float,
+                                            C.c_float, C.c_float, C.c_int32, vp, vp, vp, vp, vp]
+    lib.dexr_sphere_resolve.argtypes = [vp, i64, f64p, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, C.c_double, f64p,
+                                        f64p, f64p, C.c_double, C.c_double, C.c_double, C.c_int32, f64p, i32p, f64p, i32p]
     _lib = lib
     return lib
 
@@ -716,6 +724,58 @@ class SphereModel:
         check(load().dexr_sphere_penalty(self._h, B, _ptr(x, C.c_double), _ptr(fixed, C.c_double), float(margin),
                                          _ptr(pair_weight, C.c_double), _ptr(e, C.c_double), _ptr(gx, C.c_double)))
         return e, gx
+
+    # the collision-aware posture solve (include/dexr_resolve.h) ------------------------------------------
+    def resolve_dev(self, B: int, x0_ptr: int, fixed_ptr: int, margin: float, damping: float, max_iters: int, x_ptr: int,
+                    iters_ptr: int = 0, energy_ptr: int = 0, status_ptr: int = 0, x_ref_ptr: int = 0, posture_weight_ptr: int = 0,
+                    n_target: int = 0, target_pos_ptr: int = 0, target_rot_ptr: int = 0, pos_weight_ptr: int = 0, rot_weight_ptr: int = 0,
+                    collision_weight: float = 1.0, pair_weight_ptr: int = 0, lo_ptr: int = 0, hi_ptr: int = 0, tol: float = 0.0,
+                    max_step: float = 0.0, stream: int = 0):
+        """x0 (B, n_in), x_ref (B, n_in) or 0 (x0), posture_weight (n_in) or 0, the first n_target links of the table as targets:
+        target_pos (B, n_target, 3) and / or target_rot (B, n_target, 3, 3), pos_weight, rot_weight (B, n_target) or 0,
+        pair_weight (n_pair) or 0, lo, hi (n_in) or both 0 -> x (B, n_in), iters (B) int32, energy (B, 3), status (B) int32, each
+        of the last three or 0: up to max_iters trial steps inside one launch; x may alias x0 (dexr_sphere_resolve_dev)."""
+        check(load().dexr_sphere_resolve_dev(self._h, B, x0_ptr or None, fixed_ptr or None, x_ref_ptr or None, posture_weight_ptr or None,
+                                             int(n_target), target_pos_ptr or None, target_rot_ptr or None, pos_weight_ptr or None,
+                                             rot_weight_ptr or None, float(margin), float(collision_weight), pair_weight_ptr or None,
+                                             lo_ptr or None, hi_ptr or None, float(damping), float(max_step), float(tol), int(max_iters),
+                                             x_ptr or None, iters_ptr or None, energy_ptr or None, status_ptr or None, stream or None))
+
+    def resolve(self, x0, margin=None, damping=None, max_iters=None, fixed=None, x_ref=None, posture_weight=None, target_pos=None,
+                target_rot=None, pos_weight=None, rot_weight=None, collision_weight: float = 1.0, pair_weight=None, lo=None, hi=None,
+                tol: float = 0.0, max_step: float = 0.0, n_target=None):
+        """-> (x (B, n_in) float64, iters (B) int32, energy (B, 3) float64, status (B) int32) (dexr_sphere_resolve).  The
+        targets are the first n_target links of the table; n_target is read from the shape of target_pos / target_rot
+        ((B, n_target, 3) / (B, n_target, 3, 3)) unless given.  margin, damping > 0 and max_iters in 1..256 are required."""
+        for name, v in (("margin", margin), ("damping", damping), ("max_iters", max_iters)):
+            if v is None:
+                raise ValueError(f"{name} is required")
+        x0, fixed, B = self._host_inputs(x0, fixed)
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi = (
+            f64(a) for a in (x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi))
+        if n_target is None:
+            n_target = 0 if target_pos is None and target_rot is None else (target_pos if target_pos is not None else target_rot).shape[1]
+        n_target = int(n_target)
+        shapes = (("x_ref", x_ref, (B, self.n_in)), ("posture_weight", posture_weight, (self.n_in,)), ("target_pos", target_pos, (B, n_target, 3)),
+                  ("target_rot", target_rot, (B, n_target, 3, 3)), ("pos_weight", pos_weight, (B, n_target)),
+                  ("rot_weight", rot_weight, (B, n_target)), ("pair_weight", pair_weight, (self.n_pair,)), ("lo", lo, (self.n_in,)),
+                  ("hi", hi, (self.n_in,)))
+        for name, a, want in shapes:
+            if a is not None and a.shape != want:
+                raise ValueError(f"{name} must have shape {want}, got {a.shape}")
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        x = np.zeros((B, self.n_in), dtype=np.float64)
+        iters = np.zeros(B, dtype=np.int32)
+        energy = np.zeros((B, 3), dtype=np.float64)
+        status = np.zeros(B, dtype=np.int32)
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        check(load().dexr_sphere_resolve(self._h, B, d(x0), d(fixed), d(x_ref), d(posture_weight), n_target, d(target_pos), d(target_rot),
+                                         d(pos_weight), d(rot_weight), float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi),
+                                         float(damping), float(max_step), float(tol), int(max_iters), d(x), _ptr(iters, C.c_int32),
+                                         d(energy), _ptr(status, C.c_int32)))
+        return x, iters, energy, status
 
 
 def seq_compose_dev(B: int, T: int, dof_kind, dof_idx, dof_mult, dof_off, n_opt: int, n_fixed: int, qraw_ptr: int,

@@ -122,12 +122,34 @@ def _resolved_pairs(robot, sphere_set):
     return pairs
 
 
-def build_sphere_model(kin, sphere_set: SphereSet, pairs, source_map=None) -> _lib.SphereModel:
+def sphere_model_key(sphere_set: SphereSet, pairs, target_links=()):
+    """the cache key of a sphere model: the set alone without target links, else (set, pairs, target links)."""
+    if not target_links:
+        return sphere_set
+    return sphere_set, None if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).tobytes(), tuple(target_links)
+
+
+def resolve_table(sphere_set: SphereSet, target_links=()):
+    """(table links, sphere rows) of a sphere model: the set's own table without target links; with them the target links in the
+    caller's order followed by the sphere links not among them, the sphere rows remapped."""
+    if not target_links:
+        return list(sphere_set.table_links), sphere_set.sphere_rows
+    targets = list(target_links)
+    row_of = {}
+    for i, n in enumerate(targets):
+        row_of.setdefault(n, i)
+    rest = [n for n in sphere_set.table_links if n not in row_of]
+    for k, n in enumerate(rest):
+        row_of[n] = len(targets) + k
+    return targets + rest, np.array([row_of[n] for n in sphere_set.links], dtype=np.int32)
+
+
+def build_sphere_model(kin, sphere_set: SphereSet, pairs, source_map=None, target_links=()) -> _lib.SphereModel:
     """the device model of a sphere set on a kinematic model (what Optimizer.sphere_model / RobotWrapper.sphere_model cache)."""
     from .pose_tables import compile_poses
 
-    return _lib.SphereModel(compile_poses(kin, list(sphere_set.table_links), source_map), sphere_set.sphere_rows, sphere_set.centers,
-                            sphere_set.radii, pairs)
+    table, rows = resolve_table(sphere_set, target_links)
+    return _lib.SphereModel(compile_poses(kin, table, source_map), rows, sphere_set.centers, sphere_set.radii, pairs)
 
 
 def _check(n_in, n_fixed, kin, robot, q, fixed_qpos, sphere_set, what, margin=None, pair_weight=None, penalty=False):
@@ -221,5 +243,138 @@ def robot_self_collision_penalty(robot, qpos, sphere_set: SphereSet, margin, pai
     return _penalty(robot.sphere_model(sphere_set, pairs), qpos, None, margin, pair_weight)
 
 
+_REQUIRED = object()
+
+
+def _resolve_rules(n_in, x0, sphere_set, damping, max_iters, posture_weight, q_ref, collision_weight, link_names, target_pos, target_rot,
+                   pos_weight, rot_weight, tol, max_step, limits):
+    """The argument rules of the resolve that `_check` does not know, none of which looks at a device: the scalars, then the types,
+    dtypes and shapes of the optional tensors.  Returns the optional tensors by name, for the device rule that comes last."""
+    import torch
+
+    if not isinstance(sphere_set, SphereSet):
+        raise ValueError("sphere_set must be a collision.SphereSet")
+    if damping is _REQUIRED:
+        raise ValueError("damping is required: a positive finite Python float (there is no default)")
+    if isinstance(damping, bool) or not isinstance(damping, (int, float)) or not math.isfinite(damping) or damping <= 0:
+        raise ValueError(f"damping must be a positive finite Python float, got {damping!r}")
+    if max_iters is _REQUIRED:
+        raise ValueError("max_iters is required: a Python int in 1..256 (there is no default)")
+    if isinstance(max_iters, bool) or not isinstance(max_iters, int) or not 1 <= max_iters <= 256:
+        raise ValueError(f"max_iters must be a Python int in 1..256, got {max_iters!r}")
+    for name, v in (("collision_weight", collision_weight), ("tol", tol), ("max_step", max_step)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{name} must be a finite Python float >= 0, got {v!r}")
+    if posture_weight is not None and not isinstance(posture_weight, torch.Tensor):
+        if isinstance(posture_weight, bool) or not isinstance(posture_weight, (int, float)) or not math.isfinite(posture_weight) or posture_weight < 0:
+            raise ValueError(f"posture_weight must be a finite Python float >= 0 or a ({n_in},) float32 tensor, got {posture_weight!r}")
+    if link_names is None:
+        if any(a is not None for a in (target_pos, target_rot, pos_weight, rot_weight)):
+            raise ValueError("target_pos, target_rot, pos_weight and rot_weight need link_names: the links they are targets of")
+        L = 0
+    else:
+        if isinstance(link_names, str) or len(link_names) == 0 or not all(isinstance(n, str) for n in link_names):
+            raise ValueError("link_names must be a non-empty sequence of link names")
+        if target_pos is None and target_rot is None:
+            raise ValueError("link_names given but target_pos and target_rot are both None: at least one of them is required")
+        if pos_weight is not None and target_pos is None:
+            raise ValueError("pos_weight given without target_pos")
+        if rot_weight is not None and target_rot is None:
+            raise ValueError("rot_weight given without target_rot")
+        L = len(link_names)
+        n_table = len(resolve_table(sphere_set, link_names)[0])
+        if n_table > 64:
+            raise ValueError(f"the target links and the sphere links make {n_table} links, a resolve takes at most 64 (one pose table)")
+    B = x0.shape[0] if isinstance(x0, torch.Tensor) and x0.ndim == 2 else None
+    named = [(n, t, s) for n, t, s in (("q_ref", q_ref, (B, n_in)), ("target_pos", target_pos, (B, L, 3)), ("target_rot", target_rot, (B, L, 3, 3)),
+                                       ("pos_weight", pos_weight, (B, L)), ("rot_weight", rot_weight, (B, L)), ("limits", limits, (n_in, 2)))
+             if t is not None]
+    if isinstance(posture_weight, torch.Tensor):
+        named.append(("posture_weight", posture_weight, (n_in,)))
+    for name, t, _ in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+    for name, t, _ in named:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    for name, t, shape in named:
+        if (B is not None or shape[0] is not None) and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    return [(n, t) for n, t, _ in named]
+
+
+def _resolve(model_of, n_in, n_fixed, kin, robot, x0, what, fixed_qpos, sphere_set, margin, damping, max_iters, posture_weight, q_ref,
+             collision_weight, pair_weight, link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits):
+    """every rule, then one model and one launch."""
+    import torch
+
+    named = _resolve_rules(n_in, x0, sphere_set, damping, max_iters, posture_weight, q_ref, collision_weight, link_names, target_pos,
+                           target_rot, pos_weight, rot_weight, tol, max_step, limits)
+    for n in link_names or ():
+        kin.body_frame_index(n)  # ValueError on an unknown link
+    pairs = _check(n_in, n_fixed, kin, robot, x0, fixed_qpos, sphere_set, what, margin, pair_weight, penalty=True)  # (ends with the device)
+    for name, t in named:
+        if t.device != x0.device:
+            raise ValueError(f"{name} is on {t.device}, {what} on {x0.device}: all tensors must be on one CUDA device")
+    B = x0.shape[0]
+    xc, fixed = _inputs(x0, fixed_qpos)
+    c = lambda a: None if a is None else a.detach().contiguous()  # noqa: E731
+    xr, tp, tr, wl, wa, pw = (c(a) for a in (q_ref, target_pos, target_rot, pos_weight, rot_weight, pair_weight))
+    lo, hi = (None, None) if limits is None else (limits.detach()[:, 0].contiguous(), limits.detach()[:, 1].contiguous())
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    with torch.cuda.device(x0.device):
+        if isinstance(posture_weight, torch.Tensor):
+            u = c(posture_weight)
+        else:
+            u = None if not posture_weight else torch.full((n_in,), float(posture_weight), dtype=torch.float32, device=x0.device)
+        model = model_of(sphere_set, pairs, tuple(link_names or ()))
+        q = torch.empty((B, model.n_in), dtype=torch.float32, device=x0.device)
+        iters = torch.empty((B,), dtype=torch.int32, device=x0.device)
+        energy = torch.empty((B, 3), dtype=torch.float32, device=x0.device)
+        status = torch.empty((B,), dtype=torch.int32, device=x0.device)
+        if B > 0:
+            model.resolve_dev(B, xc.data_ptr(), ptr(fixed), float(margin), float(damping), int(max_iters), q.data_ptr(), iters.data_ptr(),
+                              energy.data_ptr(), status.data_ptr(), x_ref_ptr=ptr(xr), posture_weight_ptr=ptr(u),
+                              n_target=len(link_names or ()), target_pos_ptr=ptr(tp), target_rot_ptr=ptr(tr), pos_weight_ptr=ptr(wl),
+                              rot_weight_ptr=ptr(wa), collision_weight=float(collision_weight), pair_weight_ptr=ptr(pw), lo_ptr=ptr(lo),
+                              hi_ptr=ptr(hi), tol=float(tol), max_step=float(max_step), stream=torch.cuda.current_stream(x0.device).cuda_stream)
+    return q, iters, energy, status
+
+
+def resolve_self_collision(optimizer, q0, sphere_set: SphereSet, margin, damping=_REQUIRED, max_iters=_REQUIRED, posture_weight=None,
+                           q_ref=None, collision_weight=1.0, pair_weight=None, link_names=None, target_pos=None, target_rot=None,
+                           pos_weight=None, rot_weight=None, tol=0.0, max_step=0.0, limits=None, fixed_qpos=None):
+    """Project postures out of self-penetration inside ONE launch: from q0 (B, n_opt) float32 CUDA, up to `max_iters` (1..256)
+    damped Gauss-Newton trial steps on
+
+        E = sum_l w_pos |target_pos_l - p_l|^2 + w_rot |log(target_rot_l R_l^T)|^2  +  sum_c u_c (q_c - q_ref_c)^2
+            + collision_weight * sum_p w_p max(0, margin - d_p)^2
+
+    with an accept / reject rule and a damping of its own per frame (a trial that raises E is dropped and the damping grows
+    eightfold; an accepted one divides it by four, never below `damping`), so that E never rises: the answer is the last
+    accepted point.  -> (q (B, n_opt) float32, iters (B) int32 the trial steps taken, energy (B, 3) float32 the three terms of
+    E at q, status (B) int32: bits _lib.RESOLVE_CONVERGED (an accepted step moved nothing by more than `tol`), RESOLVE_STALLED
+    (twelve rejections in a row), RESOLVE_TRUNCATED (a point had more than 256 active pairs; the curvature used the first 256)).
+    posture_weight u: a Python float or an (n_opt,) float32 tensor >= 0, None: 0; q_ref (B, n_opt) or None: q0.  link_names with
+    target_pos (B, L, 3) and / or target_rot (B, L, 3, 3), pos_weight, rot_weight (B, L) or None (1) are world targets as in
+    `jacobians.link_ik_solve`; the links need carry no sphere.  pair_weight (P,) as in `self_collision_penalty`.  limits
+    (n_opt, 2) float32 or None: a variable on a bound that the step would push outward is frozen, every trial is clamped.
+    max_step > 0 scales a step so that its largest entry is max_step at most.  `margin`, `damping` and `max_iters` are required.
+    Mimic joints fold onto their source's column, fixed joints do not move, variables no joint reads come back unchanged.  The
+    target links and the sphere links together are at most 64.  No autograd graph."""
+    return _resolve(optimizer.sphere_model, optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q0, "q",
+                    fixed_qpos, sphere_set, margin, damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight, link_names,
+                    target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits)
+
+
+def robot_resolve_self_collision(robot, qpos0, sphere_set: SphereSet, margin, damping=_REQUIRED, max_iters=_REQUIRED, posture_weight=None,
+                                 q_ref=None, collision_weight=1.0, pair_weight=None, link_names=None, target_pos=None, target_rot=None,
+                                 pos_weight=None, rot_weight=None, tol=0.0, max_step=0.0, limits=None):
+    """The same for a full robot qpos (B, robot.dof) in dof order; every joint is a column of its own, limits (robot.dof, 2)."""
+    return _resolve(robot.sphere_model, robot.dof, 0, robot.kin, robot, qpos0, "qpos", None, sphere_set, margin, damping, max_iters,
+                    posture_weight, q_ref, collision_weight, pair_weight, link_names, target_pos, target_rot, pos_weight, rot_weight, tol,
+                    max_step, limits)
+
+
 __all__ = ["SphereSet", "default_pairs", "sphere_distances", "self_collision_penalty", "robot_sphere_distances",
-           "robot_self_collision_penalty"]
+           "robot_self_collision_penalty", "resolve_self_collision", "robot_resolve_self_collision"]

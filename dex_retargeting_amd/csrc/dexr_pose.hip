@@ -2036,3 +2036,6 @@ int dexr_link_ik_solve(const dexr_pose_model* m, int64_t B, const double* x0, co
 
 // ---- include/dexr_spheres.h: sphere-pair self-collision, a fragment of this unit -----------------------------------------------
 #include "dexr_spheres.hpp"
+
+// ---- include/dexr_resolve.h: the collision-aware posture solve, the IK solve's resident loop with the sphere phases inside -----
+#include "dexr_resolve.hpp"

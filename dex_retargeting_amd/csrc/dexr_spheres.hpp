@@ -218,6 +218,7 @@ struct dexr_sphere_model {
   int32_t* sph_out = nullptr;
   int32_t* inc_ptr = nullptr;
   uint32_t* inc = nullptr;
+  uint32_t* pair_sph = nullptr;  // (n_pair): the two spheres of a pair by sorted index, first | second << 7 (dexr_resolve.hpp)
 };
 
 namespace {
@@ -376,8 +377,10 @@ int dexr_sphere_model_create(const void* pose_blob, size_t nbytes, int32_t n_sph
   for (int s = 0; s < n_sphere; ++s) inc_ptr[s + 1] += inc_ptr[s];
   std::vector<uint32_t> inc((size_t)2 * n_pair);
   std::vector<int32_t> fill(inc_ptr.begin(), inc_ptr.end() - 1);
+  std::vector<uint32_t> pair_sph(n_pair);
   for (int p = 0; p < n_pair; ++p) {
     const int a = pos_of[pair[2 * p]], b = pos_of[pair[2 * p + 1]];
+    pair_sph[p] = (uint32_t)a | ((uint32_t)b << 7);
     inc[fill[a]++] = (uint32_t)b | SPH_FIRST | ((uint32_t)p << 8);
     inc[fill[b]++] = (uint32_t)a | ((uint32_t)p << 8);
   }
@@ -397,6 +400,7 @@ int dexr_sphere_model_create(const void* pose_blob, size_t nbytes, int32_t n_sph
   if (e == hipSuccess) e = upload_vector(order, &m->sph_out);
   if (e == hipSuccess) e = upload_vector(inc_ptr, &m->inc_ptr);
   if (e == hipSuccess) e = upload_vector(inc, &m->inc);
+  if (e == hipSuccess) e = upload_vector(pair_sph, &m->pair_sph);
   if (e != hipSuccess) {
     dexr_sphere_model_destroy(m);
     return dexr_set_error(DEXR_ERR_HIP, "uploading sphere tables failed: %s", hipGetErrorString(e));
@@ -416,6 +420,7 @@ void dexr_sphere_model_destroy(dexr_sphere_model* m) {
   if (m->sph_out) (void)hipFree(m->sph_out);
   if (m->inc_ptr) (void)hipFree(m->inc_ptr);
   if (m->inc) (void)hipFree(m->inc);
+  if (m->pair_sph) (void)hipFree(m->pair_sph);
   delete m;
 }
 

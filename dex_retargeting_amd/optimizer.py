@@ -193,17 +193,19 @@ class Optimizer:
             self._pose_models[key] = _lib.PoseModel(compile_poses(self.robot.kin, list(key), self.pose_source_map()))
         return self._pose_models[key]
 
-    def sphere_model(self, sphere_set, pairs=None) -> _lib.SphereModel:
+    def sphere_model(self, sphere_set, pairs=None, target_links=()) -> _lib.SphereModel:
         """Sphere model of a collision.SphereSet on pose_source_map() (include/dexr_spheres.h): gradients land on the
         optimiser's variables.  `pairs`: the set's own, or collision.default_pairs of this robot.  Cached per sphere set;
-        dropped by set_kinematic_adaptor."""
+        dropped by set_kinematic_adaptor.  With `target_links` (collision.resolve_self_collision) the table is those links in
+        the caller's order followed by the sphere links not among them, cached per (sphere set, pairs, target links)."""
         from . import collision
 
-        if sphere_set not in self._sphere_models:
+        key = collision.sphere_model_key(sphere_set, pairs, target_links)
+        if key not in self._sphere_models:
             if pairs is None:
                 pairs = collision._resolved_pairs(self.robot, sphere_set)
-            self._sphere_models[sphere_set] = collision.build_sphere_model(self.robot.kin, sphere_set, pairs, self.pose_source_map())
-        return self._sphere_models[sphere_set]
+            self._sphere_models[key] = collision.build_sphere_model(self.robot.kin, sphere_set, pairs, self.pose_source_map(), target_links)
+        return self._sphere_models[key]
 
     def _options(self) -> Optional[_lib.SolveOptions]:
         if all(v is None for v in self.solve_options.values()):

@@ -114,15 +114,17 @@ class RobotWrapper:
             self._pose_models[key] = _lib.PoseModel(compile_poses(self.kin, list(key)))
         return self._pose_models[key]
 
-    def sphere_model(self, sphere_set, pairs=None) -> _lib.SphereModel:
-        """Sphere model of a collision.SphereSet over the full qpos in dof order (include/dexr_spheres.h), cached per set."""
+    def sphere_model(self, sphere_set, pairs=None, target_links=()) -> _lib.SphereModel:
+        """Sphere model of a collision.SphereSet over the full qpos in dof order (include/dexr_spheres.h), cached per set; with
+        `target_links` per (set, pairs, target links), the table being those links followed by the sphere links not among them."""
         from . import collision
 
-        if sphere_set not in self._sphere_models:
+        key = collision.sphere_model_key(sphere_set, pairs, target_links)
+        if key not in self._sphere_models:
             if pairs is None:
                 pairs = collision._resolved_pairs(self, sphere_set)
-            self._sphere_models[sphere_set] = collision.build_sphere_model(self.kin, sphere_set, pairs)
-        return self._sphere_models[sphere_set]
+            self._sphere_models[key] = collision.build_sphere_model(self.kin, sphere_set, pairs, target_links=target_links)
+        return self._sphere_models[key]
 
     def link_poses(self, qpos: npt.NDArray, link_indices: Sequence[int]) -> np.ndarray:
         """(B, nq) -> (B, L, 4, 4) float64 world poses of the given links (frame ids from get_link_index), positions and

@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""GPU box: time of the fused collision-aware posture solve (dexr_sphere_resolve_dev: the accept / reject iteration inside one
+kernel) next to the same iteration written in torch from the calls the library had before it.  Read-only use of the library.
+
+Workload: Shadow hand vector config, the optimiser's variables as columns, B = 65 536, float32, q uniform inside the limits; the
+48-sphere set of tools/collision_probe.py (radius 0.012, collision.default_pairs), margin 0.010, collision weight 1; position
+targets on the five fingertips (their positions at q), weight 1; posture weight 1e-4 towards q; damping 1e-4, max_step 0.2, the
+joint limits; 8 and 16 trial steps, tol = 0.
+  (a) one resolve_dev call
+  (b) the same iteration from torch, per trial step: collision.self_collision_penalty (E_col and its gradient),
+      autograd.link_poses + jacobians.link_jacobians of the tips (E_pose, J^T W e, J^T W J), the pair curvature from
+      jacobians.link_jacobians of every sphere link (centres, normals, point Jacobians, (B, P, n) rows of the active pairs),
+      torch.linalg.solve, the step limit, the clamp, and the accept / reject rule with torch.where -- in chunks of `--chunk`
+      frames so that the (B, P, n) rows fit; no freeze rule and no cap on the active pairs
+HIP events around `--reps` back-to-back runs after `--warmup`; the variants alternate inside a round so both see the same box;
+the MEDIAN over `--rounds` rounds is reported, the rounds beside it.
+
+THE TWO WAYS OF FORMING THE PAIR CURVATURE.  The library is built with the rank-16 update (sixteen rows grad d_p staged in LDS at
+a time); csrc/dexr_resolve.hpp keeps the other way -- every entry of H walks the active list -- behind
+-DDEXR_RESOLVE_CURVATURE_WALK=1.  Build that variant beside the library and time (a) with it:
+
+    DEXR_EXTRA_FLAGS=-DDEXR_RESOLVE_CURVATURE_WALK=1 DEXR_BUILD_DIR=variants/walk DEXR_LIB_OUT=variants/walk/libdexr.so \\
+        python -m dex_retargeting_amd._build
+    DEXR_LIB=variants/walk/libdexr.so python tools/resolve_probe.py --no-torch
+
+    python tools/resolve_probe.py [--reps 5] [--rounds 5] [--iters 8,16] [--batch 65536] [--no-torch]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+from dex_retargeting_amd import _lib  # noqa: E402
+from dex_retargeting_amd import autograd as ag  # noqa: E402
+from dex_retargeting_amd import collision  # noqa: E402
+from dex_retargeting_amd import jacobians as jac  # noqa: E402
+from dex_retargeting_amd.constants import DEFAULT_URDF_DIR  # noqa: E402
+from dex_retargeting_amd.retargeting_config import RetargetingConfig  # noqa: E402
+from oracle import cases  # noqa: E402
+
+sys.path.insert(0, os.path.join(REPO, "tools"))
+from collision_probe import MARGIN, sphere_set, timed  # noqa: E402
+
+REL, N_SPHERE = "teleop/shadow_hand_right.yml", 48
+TIPS = ["thtip", "fftip", "mftip", "rftip", "lftip"]
+U, DAMPING, MAX_STEP = 1e-4, 1e-4, 0.2
+
+
+def torch_route(torch, opt, sset, pairs, q0, tp, lim, iters, chunk):
+    """the iteration of include/dexr_resolve.h from torch, chunk by chunk -> (q, E)."""
+    links = list(sset.table_links)
+    rows = torch.tensor(sset.sphere_rows.astype(np.int64), device="cuda")
+    cen = torch.tensor(sset.centers.astype(np.float32), device="cuda")
+    pi, pj = (torch.tensor(pairs[:, k].astype(np.int64), device="cuda") for k in (0, 1))
+    rsum = torch.tensor((sset.radii[pairs[:, 0]] + sset.radii[pairs[:, 1]]).astype(np.float32), device="cuda")
+    n = q0.shape[1]
+    eye = torch.eye(n, device="cuda")
+    lo, hi = lim[:, 0], lim[:, 1]
+
+    def energy(x, x0, t):
+        Ec, gc = collision.self_collision_penalty(opt, x, sset, MARGIN)
+        e = t - ag.link_poses(opt, x, TIPS, None, rotations=False)[0]
+        return (e * e).sum((1, 2)) + U * ((x - x0) ** 2).sum(1) + Ec, e, gc
+
+    xs, Es = [], []
+    for s in range(0, q0.shape[0], chunk):
+        x0, t = q0[s:s + chunk].contiguous(), tp[s:s + chunk].contiguous()
+        x = x0.clone()
+        lam = torch.full((x.shape[0],), DAMPING, device="cuda")
+        E, e, gc = energy(x, x0, t)
+        for _ in range(iters):
+            jl = jac.link_jacobians(opt, x, TIPS, angular=False)[0]  # (b, 5, 3, n)
+            J = jl.reshape(x.shape[0], -1, n)
+            g = torch.einsum("brc,br->bc", J, e.reshape(x.shape[0], -1)) + U * (x0 - x) - 0.5 * gc
+            H = J.transpose(1, 2) @ J + U * eye
+            # the pair curvature: point Jacobians of the sphere centres, the rows grad d_p of the active pairs
+            sl, sa = jac.link_jacobians(opt, x, links)
+            pos, rot = ag.link_poses(opt, x, links, None, rotations=True)
+            arm = torch.einsum("bsij,sj->bsi", rot[:, rows], cen)
+            ctr = pos[:, rows] + arm
+            jpt = sl[:, rows] + torch.cross(sa[:, rows], arm[..., None].expand(-1, -1, -1, n), dim=2)
+            D = ctr[:, pi] - ctr[:, pj]
+            sp = D.norm(dim=-1)
+            act = ((MARGIN - (sp - rsum)) > 0).float()
+            dd = torch.einsum("bpr,bprc->bpc", D / sp[..., None], jpt[:, pi] - jpt[:, pj])
+            H = H + dd.transpose(1, 2) @ (dd * act[..., None])
+            dx = torch.linalg.solve(H + lam[:, None, None] * eye, g[..., None])[..., 0]
+            m = dx.abs().amax(1, keepdim=True)
+            dx = dx * torch.where(m > MAX_STEP, MAX_STEP / m, torch.ones_like(m))
+            xt = torch.minimum(torch.maximum(x + dx, lo), hi)
+            Et, et, gt = energy(xt, x0, t)
+            acc = Et <= E
+            x = torch.where(acc[:, None], xt, x)
+            E = torch.where(acc, Et, E)
+            e = torch.where(acc[:, None, None], et, e)
+            gc = torch.where(acc[:, None], gt, gc)
+            lam = torch.where(acc, (lam / _lib.RESOLVE_LAM_DOWN).clamp_min(DAMPING), lam * _lib.RESOLVE_LAM_UP)
+        xs.append(x)
+        Es.append(E)
+    return torch.cat(xs), torch.cat(Es)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=65536)
+    ap.add_argument("--iters", default="8,16")
+    ap.add_argument("--chunk", type=int, default=4096)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--no-torch", action="store_true", help="time the fused launch alone (a variant library through DEXR_LIB)")
+    args = ap.parse_args()
+    import torch
+
+    if not torch.cuda.is_available():
+        sys.exit("resolve_probe: no GPU (a timing needs one)")
+    RetargetingConfig.set_default_urdf_dir(str(DEFAULT_URDF_DIR))
+    opt = RetargetingConfig.load_from_file(os.path.join(cases.CONFIG_DIR, REL)).build().optimizer
+    prob = cases.problem_from_config(REL)
+    sset = sphere_set(opt, N_SPHERE)
+    pairs = collision.default_pairs(opt.robot, sset)
+    model = opt.sphere_model(sset, pairs, TIPS)
+    assert model.n_fixed == 0
+    B, n = args.batch, model.n_in
+    lim_np = prob.robot.joint_limits[prob.idx_pin2target].astype(np.float32)
+    lim = torch.tensor(lim_np, device="cuda")
+    q = torch.tensor(np.random.default_rng(2).uniform(lim_np[:, 0], lim_np[:, 1], (B, n)).astype(np.float32), device="cuda")
+    tp = ag.link_poses(opt, q, TIPS, None, rotations=False)[0].contiguous()
+    print(f"# resolve_probe: {torch.cuda.get_device_name(0)}, float32, library {_lib.LIB_PATH}; {REL}: B = {B}, n_in = {n}, {N_SPHERE} spheres, "
+          f"{len(pairs)} default pairs, {len(TIPS)} tip targets; HIP events around {args.reps} back-to-back runs after {args.warmup} warm-up runs; "
+          f"median of {args.rounds} alternating rounds")
+    for iters in (int(v) for v in args.iters.split(",")):
+        out = {}
+
+        def a():
+            out["a"] = collision.resolve_self_collision(opt, q, sset, MARGIN, DAMPING, iters, U, link_names=TIPS, target_pos=tp, max_step=MAX_STEP, limits=lim)
+
+        def b():
+            out["b"] = torch_route(torch, opt, sset, pairs, q, tp, lim, iters, args.chunk)
+
+        KA, KB = f"(a) resolve_dev: {iters} trial steps, one launch", f"(b) torch: {iters} trial steps from penalty, link_jacobians, linalg.solve"
+        runs = {KA: a} if args.no_torch else {KA: a, KB: b}
+        t = {k: [] for k in runs}
+        for _ in range(args.rounds):
+            for k, fn in runs.items():
+                t[k].append(timed(torch, fn, args.reps if k == KA else 1, args.warmup if k == KA else 0))
+        torch.cuda.synchronize()
+        x, it, en, st = out["a"]
+        E0 = collision.self_collision_penalty(opt, q, sset, MARGIN)[0]
+        print(f"\n# {iters} trial steps: collision energy (median, max) {float(E0.median()):.3e}, {float(E0.max()):.3e} -> {float(en[:, 2].median()):.3e}, "
+              f"{float(en[:, 2].max()):.3e}; pose energy max {float(en[:, 0].max()):.3e}; iters {torch.bincount(it).tolist()}; status "
+              f"{torch.bincount(st, minlength=8).tolist()}")
+        if not args.no_torch:
+            xb, Eb = out["b"]
+            print(f"# torch route: max |x(a) - x(b)| = {float((x - xb).abs().max()):.3e}, median {float((x - xb).abs().amax(1).median()):.3e}; total E "
+                  f"median (a) {float(en.sum(1).median()):.4e}, (b) {float(Eb.median()):.4e}")
+        print(f"{'variant':80s} {'us':>12s}   rounds (us)")
+        med = {k: statistics.median(v) for k, v in t.items()}
+        for k in runs:
+            print(f"{k:80s} {med[k]:12.1f}   {' '.join(f'{v:11.1f}' for v in t[k])}")
+        print(f"# (a) = {med[KA] * 1e3 / B:.1f} ns per frame, {med[KA] * 1e3 / B / iters:.1f} ns per frame and trial step" +
+              ("" if args.no_torch else f"; (b) / (a) = {med[KB] / med[KA]:.1f}"))
+
+
+if __name__ == "__main__":
+    main()
