@@ -217,6 +217,37 @@ struct TipTabT {
 };
 typedef TipTabT<float> TipTab;
 
+// The float32 table with the placements of joints 1..3 in REGISTERS for the length of one pass (dexr_tip32_kernel).
+// TipTabT reads each joint's placement from LDS inside the serial chain of the forward kinematics, a joint ahead of its use
+// at best: round trips that a lone wave covers only in part (measured: 0.2-0.4 us of a small launch; four waves per SIMD
+// cover them anyway).  prefetch() issues all of them at once, where the caller has other work to do -- the
+// values are loop invariants, but 36 registers held through the whole loop would not fit, so the loads are volatile: each
+// call issues them again, where it stands (neither hoisted out of the loop nor sunk to the uses), and the scheduling barrier
+// keeps the instructions that follow behind them.  arrived() is the wait, to be called in front of the evaluation;
+// tip_eval<float, TipTabRegs> then takes XA / XB from the registers.
+struct TipTabRegs : TipTabT<float> {
+  kv2 xr[18];  // xl[0..17], as of the last prefetch()
+  __device__ __forceinline__ kv2 XA(int k1, int j) const { return xr[6 * k1 + j]; }
+  __device__ __forceinline__ kv2 XB(int k1, int j) const { return xr[6 * k1 + 3 + j]; }
+  __device__ __forceinline__ void prefetch() {
+    typedef float q4 __attribute__((ext_vector_type(4)));
+    typedef q4 q4a __attribute__((aligned(8)));  // (two pairs: the LDS block is aligned as pairs are, ds_read2_b64)
+    // (the address space by hand: it is not inferred for a volatile access, which would become a flat load)
+    typedef const volatile q4a __attribute__((address_space(3))) * lds_q4;
+    const lds_q4 src = (lds_q4)xl;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      const q4 v = src[i];
+      xr[2 * i] = kv2{v.x, v.y};
+      xr[2 * i + 1] = kv2{v.z, v.w};
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // In front of the evaluation: ONE wait for the whole batch (lgkmcnt(0), the other counters left alone) instead of the
+  // countdown, a wait per pair of loads, that the compiler would spread over the first joints of the chain
+  __device__ __forceinline__ void arrived() const { __builtin_amdgcn_s_waitcnt(0xc07f); }
+};
+
 // sin / cos of two angles at once.  Reduction by pi (k = rint(a / pi), two-constant Cody-Waite: 3.140625 has 9 significant
 // bits, so k * 3.140625 is exact), minimax polynomials of degree 9 / 10 on [-pi/2, pi/2] (fitted in float64; errors
 // 2.5e-8 / 3.3e-9 before rounding, 1.2e-7 / 1.1e-7 in float32 arithmetic over |a| < 7: RealTraits<float>::sincos measures
@@ -251,9 +282,10 @@ static __device__ __forceinline__ void tip_sincos2(typename TipVec<double>::v2 a
 
 // One pass at x: returns the data term (reference "huber_distance", no regulariser), writes its gradient g and the lower
 // triangle of its Hessian H (hidx order: 00 | 10 11 | 20 21 22 | 30 31 32 33).  t0..t2: the lane's target (origin folded, see
-// TipTab); w: the 'mean' factor; nw: 1 with the second-order kinematic term (Newton), 0 without.
-template <typename R>
-static __device__ __forceinline__ R tip_eval(const TipTabT<R>& tt, const R (&x)[4], R t0, R t1, R t2,
+// TipTab); w: the 'mean' factor; nw: 1 with the second-order kinematic term (Newton), 0 without.  TT: where the placements of
+// joints 1..3 come from -- TipTabT<R> (LDS, at the point of use) or TipTabRegs (registers, prefetched by the caller).
+template <typename R, typename TT = TipTabT<R>>
+static __device__ __forceinline__ R tip_eval(const TT& tt, const R (&x)[4], R t0, R t1, R t2,
                                              R beta, R ibeta, R w, R nw,
                                              R (&g)[4], R (&H)[10]) {
   typedef typename TipVec<R>::v2 kv2;  // (shadows the float pair: every formula below is written on this type)

@@ -6,11 +6,13 @@
 // objective-value output as live branches and live scalar registers.  A plain tile launch of a tip model -- the headline: every
 // lane gets its one frame before the first pass and never another -- needs none of it.  This kernel is that launch written
 // straight:
-//   prologue  table pin, the lane's frame (same values, same LDS layout as dexr_kernel), clamp to the box, evaluation of the
-//             start point (dexr_kernel's pass 0), whose model is adopted.  Its loads go out in batches, one wait per level
+//   prologue  table pin, the lane's frame (same values, same LDS layout as dexr_kernel -- but the lane's target stays in three
+//             registers, its LDS column is not used), clamp to the box, evaluation of the start point (dexr_kernel's pass 0),
+//             whose model is adopted.  Its loads go out in batches, one wait per level
 //             of their dependency chain, and the frame's own loads are in flight while the constants are pinned -- at every
 //             launch size, each issued once (they replace the early touch of the frame's lines that small launches had);
-//   loop      (a) damped 4 x 4 step from the kept model, (b) tip_eval at the trial point unless every live lane takes its
+//   loop      the placements of joints 1..3 from LDS into registers, one batch whose latency (a) covers (TipTabRegs),
+//             (a) damped 4 x 4 step from the kept model, (b) tip_eval at the trial point unless every live lane takes its
 //             blind last step, (c) accept / reject / damping / termination, (d) finished lanes store and drop out;
 //             the wave leaves when no lane holds a frame.
 // Every floating-point operation the answer depends on is the one dexr_kernel does, on the same operands in the same order
@@ -69,7 +71,8 @@ static __device__ __forceinline__ bool tip32_chol(float (&H)[10], const float (&
 
 // One wave = 64 frames x one tip component (wave w: component w % n_comp of tile w / n_comp, as dexr_kernel in tile mode).
 // blockDim.x = 64 * waves_per_block; dynamic LDS = waves_per_block * 64 * 4 * (3 * lds_frames + 4 * lds_terms + 1) bytes, laid
-// out as dexr_kernel's: the lane's target at T[(0..2) * 64 + lane], the broadcast placements of joints 1..3 behind W.
+// out as dexr_kernel's: the lane's target would be at T[(0..2) * 64 + lane] (unused here), the broadcast placements of joints
+// 1..3 behind W.
 __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip32_kernel(const KernelParams kp, const dexr_comp_table* __restrict__ comps) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   using RT = RealTraits<float, true>;
@@ -111,7 +114,7 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
 
   // Level 1: the component's table -- joint 0, the box, the lane's LDS constant, and the four integers the addresses below hang on
   const dexr_comp_table& tb = comps[comp];
-  TipTabT<float> tt;
+  TipTabRegs tt;  // (placements of joints 1..3: prefetched into registers once per pass)
   TipTabT<float>::Stage st;
   int api0 = tb.api[0];  // a tip component's four joints are consecutive columns of last_qpos / qpos_out
   int row = tb.term_ref[0], ft = tb.term_task[0], fo = tb.term_origin[0];
@@ -127,6 +130,7 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
   // ref_value row -- every load issued here, waited for once, behind the pins
   float x[4] = {0.f, 0.f, 0.f, 0.f}, xl[4] = {0.f, 0.f, 0.f, 0.f};
   float fl[4], ra[3], rb[3];  // (set and read by lanes that hold a frame only)
+  float tg[3] = {0.f, 0.f, 0.f};  // the lane's target: three registers for the whole solve (T, its LDS column in dexr_kernel, stays unused)
   // the target is keypoint h_t minus keypoint h_o, or keypoint h_t alone, or the ready-made ref_value row: the wave-uniform
   // choice is made on the ADDRESSES (without an origin keypoint rb re-reads ra's line and is not used), so that each load is
   // issued exactly once and no loaded value has to be merged with another or moved between registers before the pins are through
@@ -167,7 +171,7 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
   const float k_inf = __builtin_inff();
   const float k_rho_fast = tip_pin(a_lam_fastdec > 0 ? 0.9f : k_inf), k_lam_rec_from = tip_pin(a_lam_recover > 0 ? 10.f * a_lam0 : k_inf);
 
-  // ---- the frame has arrived: the term's target into the lane's LDS column, the start point into the box
+  // ---- the frame has arrived: the term's target into the lane's registers, the start point into the box
   if (has) {
     float rv[3];
     if (sub) {
@@ -178,7 +182,7 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
       for (int i = 0; i < 3; ++i) rv[i] = ra[i];
     }
 #pragma unroll
-    for (int i = 0; i < 3; ++i) T[i * 64 + lane] = rv[i] * a_scaling;  // f32 multiply: optimizer.py:246
+    for (int i = 0; i < 3; ++i) tg[i] = rv[i] * a_scaling;  // f32 multiply: optimizer.py:246
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       xl[k] = fl[k];
@@ -193,7 +197,8 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
 
   // value / gradient / Hessian at xe, regulariser included
   auto eval = [&](const float (&xe)[4], float (&g)[4], float (&H)[10]) -> float {
-    float Ft = tip_eval<float>(tt, xe, T[lane], T[64 + lane], T[128 + lane], tip_beta, tip_ibeta, tip_w, tip_nw, g, H);
+    tt.arrived();
+    float Ft = tip_eval<float>(tt, xe, tg[0], tg[1], tg[2], tip_beta, tip_ibeta, tip_w, tip_nw, g, H);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float dx = xe[k] - xl[k];
@@ -221,10 +226,14 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
   };
 
   // ---- start point: adopt its model unconditionally
+  tt.prefetch();
   F = eval(x, gs, Hs);
   if (has && !((bool)((int)(F == F) & (int)(fabs(F) < 1e30f)))) retire(ST_FALLBACK);
 
   while (__any(has)) {
+    // the placements (b) needs, issued here: step (a) uses none of them and covers their way from LDS.  Not gated on (b)'s
+    // condition, which (a) produces: a pass that skips (b) -- a wave's last, if any -- has read them for nothing
+    tt.prefetch();
     // (a) step from the kept model; joints held at a bound by the gradient sign are taken out of the system
     float g[4], H[10], d[4];
     // (which joints are free: four lane masks as the comparisons deliver them -- the pair conditions are scalar ANDs of them,
