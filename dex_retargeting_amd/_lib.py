@@ -72,6 +72,13 @@ SPHERE_MAX, SPHERE_MAXPAIR = 128, 8192  # DEXR_SPHERE_*
 RESOLVE_EXPORTS = ["dexr_sphere_resolve_dev", "dexr_sphere_resolve"]
 RESOLVE_MAXACTIVE, RESOLVE_LAM_UP, RESOLVE_LAM_DOWN, RESOLVE_MAXREJECT = 256, 8, 4, 12  # DEXR_RESOLVE_*
 RESOLVE_CONVERGED, RESOLVE_STALLED, RESOLVE_TRUNCATED = 1, 2, 4  # status bits
+# include/dexr_obstacles.h (the spheres of a sphere model against posed primitives: distances, their VJP, the fused penalty): a
+# list of its own
+OBSTACLE_EXPORTS = ["dexr_obstacle_set_create", "dexr_obstacle_set_destroy", "dexr_obstacle_set_info", "dexr_obstacle_distances_dev",
+                    "dexr_obstacle_distances_vjp_dev", "dexr_obstacle_penalty_dev", "dexr_obstacle_distances",
+                    "dexr_obstacle_distances_vjp", "dexr_obstacle_penalty"]
+OBSTACLE_MAX, OBSTACLE_PARAMS = 64, 16  # DEXR_OBSTACLE_*
+OBSTACLE_SPHERE, OBSTACLE_CAPSULE, OBSTACLE_BOX, OBSTACLE_HALFSPACE = 0, 1, 2, 3  # primitive kinds
 UNIQUE_ID_BYTES = 128
 
 
@@ -173,6 +180,16 @@ def load() -> C.CDLL:
                                             C.c_float, C.c_float, C.c_int32, vp, vp, vp, vp, vp]
     lib.dexr_sphere_resolve.argtypes = [vp, i64, f64p, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, C.c_double, f64p,
                                         f64p, f64p, C.c_double, C.c_double, C.c_double, C.c_int32, f64p, i32p, f64p, i32p]
+    lib.dexr_obstacle_set_create.argtypes = [C.c_int32, i32p, f64p, C.POINTER(vp)]
+    lib.dexr_obstacle_set_destroy.argtypes = [vp]
+    lib.dexr_obstacle_set_destroy.restype = None
+    lib.dexr_obstacle_set_info.argtypes = [vp, i32p]
+    lib.dexr_obstacle_distances_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.dexr_obstacle_distances_vjp_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.dexr_obstacle_penalty_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]
+    lib.dexr_obstacle_distances.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, f64p, i32p]
+    lib.dexr_obstacle_distances_vjp.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, f64p, f64p]
+    lib.dexr_obstacle_penalty.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, C.c_double, f64p, f64p, f64p, f64p]
     _lib = lib
     return lib
 
@@ -776,6 +793,107 @@ class SphereModel:
                                          float(damping), float(max_step), float(tol), int(max_iters), d(x), _ptr(iters, C.c_int32),
                                          d(energy), _ptr(status, C.c_int32)))
         return x, iters, energy, status
+
+    # the model's spheres against an obstacle set (include/dexr_obstacles.h); the pair list plays no part --------------
+    def obstacle_distances_dev(self, obstacles: "ObstacleSet", B: int, x_ptr: int, fixed_ptr: int, dist_ptr: int, nearest_ptr: int = 0,
+                               obstacle_pos_ptr: int = 0, obstacle_rot_ptr: int = 0, stream: int = 0):
+        """x (B, n_in), fixed (B, n_fixed) or 0, obstacle_pos (B, 3) or 0, obstacle_rot (B, 3, 3) or 0 -> dist (B, n_sphere) and /
+        or nearest (B, n_sphere) int32, either may be 0 (dexr_obstacle_distances_dev)."""
+        check(load().dexr_obstacle_distances_dev(self._h, obstacles.handle, B, x_ptr or None, fixed_ptr or None, obstacle_pos_ptr or None,
+                                                 obstacle_rot_ptr or None, dist_ptr or None, nearest_ptr or None, stream or None))
+
+    def obstacle_distances_vjp_dev(self, obstacles: "ObstacleSet", B: int, x_ptr: int, fixed_ptr: int, grad_dist_ptr: int, grad_x_ptr: int,
+                                   obstacle_pos_ptr: int = 0, obstacle_rot_ptr: int = 0, stream: int = 0):
+        """grad_dist (B, n_sphere) -> grad_x (B, n_in), every entry written (dexr_obstacle_distances_vjp_dev)."""
+        check(load().dexr_obstacle_distances_vjp_dev(self._h, obstacles.handle, B, x_ptr or None, fixed_ptr or None, obstacle_pos_ptr or None,
+                                                     obstacle_rot_ptr or None, grad_dist_ptr or None, grad_x_ptr or None, stream or None))
+
+    def obstacle_penalty_dev(self, obstacles: "ObstacleSet", B: int, x_ptr: int, fixed_ptr: int, margin: float, prim_weight_ptr: int,
+                             energy_ptr: int, grad_x_ptr: int, wrench_ptr: int = 0, obstacle_pos_ptr: int = 0, obstacle_rot_ptr: int = 0,
+                             stream: int = 0):
+        """margin >= 0, prim_weight (n_prim) or 0 (weights of 1) -> energy (B), grad_x (B, n_in), wrench (B, 6), each may be 0 but
+        not all, from one launch (dexr_obstacle_penalty_dev)."""
+        check(load().dexr_obstacle_penalty_dev(self._h, obstacles.handle, B, x_ptr or None, fixed_ptr or None, obstacle_pos_ptr or None,
+                                               obstacle_rot_ptr or None, float(margin), prim_weight_ptr or None, energy_ptr or None,
+                                               grad_x_ptr or None, wrench_ptr or None, stream or None))
+
+    @staticmethod
+    def _host_pose(B, obstacle_pos, obstacle_rot):
+        out = []
+        for name, a, shape in (("obstacle_pos", obstacle_pos, (B, 3)), ("obstacle_rot", obstacle_rot, (B, 3, 3))):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != shape:
+                    raise ValueError(f"{name} must have shape {shape}, got {a.shape}")
+            out.append(a)
+        return out
+
+    def obstacle_distances(self, obstacles: "ObstacleSet", x, fixed=None, obstacle_pos=None, obstacle_rot=None, nearest: bool = True):
+        """-> dist (B, n_sphere) float64, nearest (B, n_sphere) int32 or None (dexr_obstacle_distances)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        pos, rot = self._host_pose(B, obstacle_pos, obstacle_rot)
+        dist = np.zeros((B, self.n_sphere), dtype=np.float64)
+        near = np.zeros((B, self.n_sphere), dtype=np.int32) if nearest else None
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        check(load().dexr_obstacle_distances(self._h, obstacles.handle, B, d(x), d(fixed), d(pos), d(rot), d(dist), _ptr(near, C.c_int32)))
+        return dist, near
+
+    def obstacle_distances_vjp(self, obstacles: "ObstacleSet", x, grad_dist, fixed=None, obstacle_pos=None, obstacle_rot=None):
+        """-> grad_x (B, n_in) float64 (dexr_obstacle_distances_vjp)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        pos, rot = self._host_pose(B, obstacle_pos, obstacle_rot)
+        grad_dist = np.ascontiguousarray(grad_dist, dtype=np.float64)
+        if grad_dist.shape != (B, self.n_sphere):
+            raise ValueError(f"grad_dist must have shape ({B}, {self.n_sphere}), got {grad_dist.shape}")
+        gx = np.zeros((B, self.n_in), dtype=np.float64)
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        check(load().dexr_obstacle_distances_vjp(self._h, obstacles.handle, B, d(x), d(fixed), d(pos), d(rot), d(grad_dist), d(gx)))
+        return gx
+
+    def obstacle_penalty(self, obstacles: "ObstacleSet", x, margin, prim_weight=None, fixed=None, obstacle_pos=None, obstacle_rot=None,
+                         want_energy: bool = True, want_grad: bool = True, want_wrench: bool = True):
+        """-> (energy (B), grad_x (B, n_in), wrench (B, 6)) float64, None where not wanted (dexr_obstacle_penalty)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        pos, rot = self._host_pose(B, obstacle_pos, obstacle_rot)
+        if prim_weight is not None:
+            prim_weight = np.ascontiguousarray(prim_weight, dtype=np.float64)
+            if prim_weight.shape != (obstacles.n_prim,):
+                raise ValueError(f"prim_weight must have shape ({obstacles.n_prim},), got {prim_weight.shape}")
+        e = np.zeros(B, dtype=np.float64) if want_energy else None
+        gx = np.zeros((B, self.n_in), dtype=np.float64) if want_grad else None
+        wr = np.zeros((B, 6), dtype=np.float64) if want_wrench else None
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        check(load().dexr_obstacle_penalty(self._h, obstacles.handle, B, d(x), d(fixed), d(pos), d(rot), float(margin), d(prim_weight), d(e),
+                                           d(gx), d(wr)))
+        return e, gx, wr
+
+
+class ObstacleSet:
+    """Owns one dexr_obstacle_set (include/dexr_obstacles.h): 1 .. OBSTACLE_MAX primitives of an obstacle frame, resident in HBM.
+    kind (M) int32 of OBSTACLE_SPHERE / CAPSULE / BOX / HALFSPACE, param (M, OBSTACLE_PARAMS) float64.  Any SphereModel's
+    obstacle_* methods take it."""
+
+    def __init__(self, kind, param):
+        lib = load()
+        self._h = C.c_void_p()
+        kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(-1)
+        param = np.ascontiguousarray(param, dtype=np.float64)
+        if param.shape != (len(kind), OBSTACLE_PARAMS):
+            raise ValueError(f"param must have shape ({len(kind)}, {OBSTACLE_PARAMS}), one row per primitive, got {param.shape}")
+        check(lib.dexr_obstacle_set_create(len(kind), _ptr(kind, C.c_int32), _ptr(param, C.c_double), C.byref(self._h)))
+        n = C.c_int32()
+        check(lib.dexr_obstacle_set_info(self._h, C.byref(n)))
+        self.n_prim = int(n.value)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib is not None:
+            _lib.dexr_obstacle_set_destroy(h)
+            self._h = None
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
 
 
 def seq_compose_dev(B: int, T: int, dof_kind, dof_idx, dof_mult, dof_off, n_opt: int, n_fixed: int, qraw_ptr: int,

@@ -495,5 +495,148 @@ def robot_self_collision_penalty(robot, qpos, sphere_set, margin, pair_weight=No
         return _sphere_fns()[1].apply(qpos, None, robot.sphere_model(sphere_set, pairs), float(margin), pair_weight)
 
 
+# ---- the spheres against an obstacle set: distances and the fused penalty, differentiable in q (and the obstacle's position) ------
+def _make_obstacle_functions():
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _ObstacleDistances(torch.autograd.Function):
+        """Saves x, fixed and the obstacle pose only: the VJP kernel recomputes the walk, the nearest primitive and its normal."""
+
+        @staticmethod
+        def forward(ctx, x, fixed_qpos, obstacle_pos, obstacle_rot, model, obstacles):
+            from . import collision
+
+            dist = collision._obstacle_distances(model, obstacles, x, fixed_qpos, obstacle_pos, obstacle_rot, False)
+            xc, fixed = collision._inputs(x, fixed_qpos)
+            pos, rot = collision._obstacle_pose(obstacle_pos, obstacle_rot)
+            ctx.model, ctx.obstacles = model, obstacles
+            ctx.have = [a is not None for a in (fixed, pos, rot)]
+            ctx.save_for_backward(*[a for a in (xc, fixed, pos, rot) if a is not None])
+            return dist
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_dist):
+            if not ctx.needs_input_grad[0]:
+                return (None,) * 6
+            saved = list(ctx.saved_tensors)
+            x = saved.pop(0)
+            fixed, pos, rot = (saved.pop(0) if h else None for h in ctx.have)
+            B = x.shape[0]
+            gd = grad_dist.detach().to(torch.float32).contiguous()
+            gx = torch.empty_like(x)  # (the kernel writes every entry)
+            ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+            if B > 0:
+                with torch.cuda.device(x.device):
+                    ctx.model.obstacle_distances_vjp_dev(ctx.obstacles.device_set(torch.cuda.current_device()), B, x.data_ptr(), ptr(fixed),
+                                                         gd.data_ptr(), gx.data_ptr(), ptr(pos), ptr(rot),
+                                                         stream=torch.cuda.current_stream(x.device).cuda_stream)
+            return (gx,) + (None,) * 5
+
+    class _ObstaclePenalty(torch.autograd.Function):
+        """The forward launch gives E, dE/dx and the wrench together where they are needed; backward scales what it saved."""
+
+        @staticmethod
+        def forward(ctx, x, fixed_qpos, obstacle_pos, obstacle_rot, model, obstacles, margin, prim_weight):
+            from . import collision
+
+            want_x = bool(ctx.needs_input_grad[0])
+            want_p = obstacle_pos is not None and bool(ctx.needs_input_grad[2])
+            e, g, wr = collision._obstacle_penalty(model, obstacles, x, fixed_qpos, margin, prim_weight, obstacle_pos, obstacle_rot,
+                                                   want_grad=want_x, want_wrench=want_p)
+            ctx.want = (want_x, want_p)
+            ctx.save_for_backward(*[a for a in (g, wr) if a is not None])
+            return e
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_e):
+            saved = list(ctx.saved_tensors)
+            ge = grad_e.to(torch.float32)[:, None]
+            gx = ge * saved.pop(0) if ctx.want[0] else None
+            gp = ge * saved.pop(0)[:, :3] if ctx.want[1] else None  # dE/d(obstacle translation): the force half of the wrench
+            return (gx, None, gp) + (None,) * 5
+
+    return _ObstacleDistances, _ObstaclePenalty
+
+
+_OBSTACLE_FNS = None
+
+
+def _obstacle_fns():
+    global _OBSTACLE_FNS
+    if _OBSTACLE_FNS is None:
+        _OBSTACLE_FNS = _make_obstacle_functions()
+    return _OBSTACLE_FNS
+
+
+def _no_rot_grad(obstacle_rot):
+    import torch
+
+    if isinstance(obstacle_rot, torch.Tensor) and obstacle_rot.requires_grad:
+        raise ValueError("obstacle_rot requires grad, but no gradient flows to a rotation matrix: detach it and call "
+                         "collision.obstacle_penalty with wrench=True, whose last three columns are the torque dE/d(small world rotation)")
+
+
+def obstacle_distances(optimizer, q, sphere_set, obstacles, obstacle_pos=None, obstacle_rot=None, fixed_qpos=None):
+    """`collision.obstacle_distances` with an autograd graph: dist (B, S) float32, the same bits; backward is the distance VJP
+    kernel (dexr_obstacle_distances_vjp_dev).  Gradients flow to q only; once differentiable."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(obstacle_rot)
+    pairs = collision._check_obstacles(optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q, fixed_qpos,
+                                       sphere_set, obstacles, obstacle_pos, obstacle_rot, "q")
+    with torch.cuda.device(q.device):
+        return _obstacle_fns()[0].apply(q, fixed_qpos, obstacle_pos, obstacle_rot, optimizer.sphere_model(sphere_set, pairs), obstacles)
+
+
+def obstacle_penalty(optimizer, q, sphere_set, obstacles, margin, obstacle_pos=None, obstacle_rot=None, prim_weight=None, fixed_qpos=None):
+    """`collision.obstacle_penalty` with an autograd graph: E (B,) float32.  Where q or obstacle_pos needs a gradient the forward
+    launch computes E, dE/dq and the wrench together (one launch, the same bits as the no-graph call); backward is
+    grad_E[:, None] * dE/dq for q and grad_E[:, None] * wrench[:, :3] for obstacle_pos.  No gradient flows to obstacle_rot
+    (one that requires grad is a ValueError: `collision.obstacle_penalty(..., wrench=True)` gives the torque), prim_weight or
+    fixed_qpos; once differentiable."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(obstacle_rot)
+    pairs = collision._check_obstacles(optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q, fixed_qpos,
+                                       sphere_set, obstacles, obstacle_pos, obstacle_rot, "q", margin, prim_weight, penalty=True)
+    with torch.cuda.device(q.device):
+        return _obstacle_fns()[1].apply(q, fixed_qpos, obstacle_pos, obstacle_rot, optimizer.sphere_model(sphere_set, pairs), obstacles,
+                                        float(margin), prim_weight)
+
+
+def robot_obstacle_distances(robot, qpos, sphere_set, obstacles, obstacle_pos=None, obstacle_rot=None):
+    """The same for a full robot qpos (B, robot.dof) float32 in dof order."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(obstacle_rot)
+    pairs = collision._check_obstacles(robot.dof, 0, robot.kin, robot, qpos, None, sphere_set, obstacles, obstacle_pos, obstacle_rot, "qpos")
+    with torch.cuda.device(qpos.device):
+        return _obstacle_fns()[0].apply(qpos, None, obstacle_pos, obstacle_rot, robot.sphere_model(sphere_set, pairs), obstacles)
+
+
+def robot_obstacle_penalty(robot, qpos, sphere_set, obstacles, margin, obstacle_pos=None, obstacle_rot=None, prim_weight=None):
+    """The same for a full robot qpos (B, robot.dof) float32 in dof order."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(obstacle_rot)
+    pairs = collision._check_obstacles(robot.dof, 0, robot.kin, robot, qpos, None, sphere_set, obstacles, obstacle_pos, obstacle_rot, "qpos",
+                                       margin, prim_weight, penalty=True)
+    with torch.cuda.device(qpos.device):
+        return _obstacle_fns()[1].apply(qpos, None, obstacle_pos, obstacle_rot, robot.sphere_model(sphere_set, pairs), obstacles,
+                                        float(margin), prim_weight)
+
+
 __all__ = ["retarget", "ref_value_from_keypoints", "link_poses", "robot_link_poses", "link_velocities", "robot_link_velocities",
-           "sphere_distances", "self_collision_penalty", "robot_sphere_distances", "robot_self_collision_penalty"]
+           "sphere_distances", "self_collision_penalty", "robot_sphere_distances", "robot_self_collision_penalty", "obstacle_distances",
+           "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty"]

@@ -14,8 +14,15 @@ neither distances nor forces nor normals reach memory.  Mimic joints fold onto t
 geometry and take no gradient, variables no joint reads get exact zeros.  The squared hinge makes E continuously
 differentiable.
 
-The outputs of this module carry NO autograd graph; ``autograd.sphere_distances`` and ``autograd.self_collision_penalty`` are
-the same kernels with one, so that a penetration loss composes with ``autograd.retarget`` and reaches the keypoints.
+An ``ObstacleSet`` is the other side of a collision with something that is not the robot (include/dexr_obstacles.h,
+csrc/dexr_obstacles.hpp): spheres, capsules, boxes and half-spaces in an obstacle frame that has a world pose per frame
+(``obstacle_pos``, ``obstacle_rot``: a held object) or none (a shared scene).  ``obstacle_distances`` gives the signed distance of
+every sphere of a ``SphereSet`` to the nearest primitive, ``obstacle_penalty`` the squared-hinge energy over every (sphere,
+primitive) entry, its gradient in q and, asked for, the wrench on the obstacle, again from ONE launch.
+
+The outputs of this module carry NO autograd graph; ``autograd.sphere_distances``, ``autograd.self_collision_penalty``,
+``autograd.obstacle_distances`` and ``autograd.obstacle_penalty`` are the same kernels with one, so that a penetration loss
+composes with ``autograd.retarget`` and reaches the keypoints.
 """
 from __future__ import annotations
 
@@ -376,5 +383,246 @@ def robot_resolve_self_collision(robot, qpos0, sphere_set: SphereSet, margin, da
                     max_step, limits)
 
 
+# ---- obstacles: the robot's spheres against posed primitives outside the robot (include/dexr_obstacles.h) -------------------------
+class ObstacleSet:
+    """1 .. 64 primitives in an obstacle frame: plain data, immutable, hashable by content.
+
+    kinds   (M,) of _lib.OBSTACLE_SPHERE / OBSTACLE_CAPSULE / OBSTACLE_BOX / OBSTACLE_HALFSPACE
+    params  (M, 16) float64, per kind (the rest zeros):
+              sphere      centre (3), radius >= 0
+              capsule     end a (3), end b (3), radius >= 0
+              box         centre (3), half extents (3) > 0, rotation (9, row-major, box axes -> obstacle frame, orthonormal to 1e-6)
+              half-space  normal (3, unit to 1e-6), offset: the solid is n . y <= offset
+
+    Built with `ObstacleSet.spheres / capsules / boxes / half_spaces`; `a + b` (or `ObstacleSet.concat`) puts sets together, the
+    primitives of `a` first.  The rules are those of dexr_obstacle_set_create; a broken one is a ValueError.  The device tables of
+    a set are made at its first use and kept with it (`device_set`)."""
+
+    def __init__(self, kinds, params):
+        k = np.array(kinds, dtype=np.int64).reshape(-1)
+        p = np.array(params, dtype=np.float64)
+        M = len(k)
+        if not 1 <= M <= _lib.OBSTACLE_MAX:
+            raise ValueError(f"an obstacle set holds 1..{_lib.OBSTACLE_MAX} primitives, got {M}")
+        if p.shape != (M, _lib.OBSTACLE_PARAMS):
+            raise ValueError(f"{M} kinds name {M} primitives: params must have shape ({M}, {_lib.OBSTACLE_PARAMS}), got {p.shape}")
+        if ((k < _lib.OBSTACLE_SPHERE) | (k > _lib.OBSTACLE_HALFSPACE)).any():
+            raise ValueError(f"kinds must be one of {_lib.OBSTACLE_SPHERE} (sphere), {_lib.OBSTACLE_CAPSULE} (capsule), "
+                             f"{_lib.OBSTACLE_BOX} (box), {_lib.OBSTACLE_HALFSPACE} (half-space)")
+        if not np.isfinite(p).all():
+            raise ValueError("obstacle parameters must be finite")
+        tol = 1e-6
+        for m in range(M):
+            v = p[m]
+            if k[m] in (_lib.OBSTACLE_SPHERE, _lib.OBSTACLE_CAPSULE):
+                r = v[3] if k[m] == _lib.OBSTACLE_SPHERE else v[6]
+                if r < 0:
+                    raise ValueError(f"primitive {m}: the radius must be >= 0, got {r}")
+            elif k[m] == _lib.OBSTACLE_BOX:
+                if not (v[3:6] > 0).all():
+                    raise ValueError(f"primitive {m}: the half extents must be > 0, got {v[3:6].tolist()}")
+                R = v[6:15].reshape(3, 3)
+                if np.abs(R.T @ R - np.eye(3)).max() > tol:
+                    raise ValueError(f"primitive {m}: the box rotation is not orthonormal to {tol}")
+            elif abs(np.linalg.norm(v[:3]) - 1.0) > tol:
+                raise ValueError(f"primitive {m}: the half-space normal is not unit to {tol}")
+        k = k.astype(np.int32)
+        for a in (k, p):
+            a.setflags(write=False)
+        self.kinds, self.params = k, p
+        self._key = (k.tobytes(), p.tobytes())
+        self._device_sets = {}
+
+    @staticmethod
+    def _rows(kind, blocks, n_name):
+        """(M, 16) from per-primitive blocks [(name, array, width)], M read from the first."""
+        first = np.array(blocks[0][1], dtype=np.float64)
+        M = first.shape[0] if first.ndim >= 1 else 0
+        p = np.zeros((M, _lib.OBSTACLE_PARAMS))
+        o = 0
+        for name, a, width in blocks:
+            a = np.array(a, dtype=np.float64)
+            want = (M,) if width == 1 else ((M, 3, 3) if width == 9 else (M, width))
+            if a.shape != want or M == 0:
+                raise ValueError(f"{name} must have shape {('M',) + want[1:]} with one row per {n_name}, got {a.shape}")
+            p[:, o:o + width] = a.reshape(M, width)
+            o += width
+        return ObstacleSet(np.full(M, kind), p)
+
+    @classmethod
+    def spheres(cls, centers, radii):
+        """centers (M, 3), radii (M,)."""
+        return cls._rows(_lib.OBSTACLE_SPHERE, [("centers", centers, 3), ("radii", radii, 1)], "sphere")
+
+    @classmethod
+    def capsules(cls, a, b, radii):
+        """the two ends a, b (M, 3) of each axis, radii (M,); a == b is a sphere."""
+        return cls._rows(_lib.OBSTACLE_CAPSULE, [("a", a, 3), ("b", b, 3), ("radii", radii, 1)], "capsule")
+
+    @classmethod
+    def boxes(cls, centers, half_extents, rotations=None):
+        """centers (M, 3), half_extents (M, 3) > 0, rotations (M, 3, 3) box axes -> obstacle frame, or None: axis-aligned."""
+        if rotations is None:
+            n = np.array(centers, dtype=np.float64)
+            rotations = np.broadcast_to(np.eye(3), (n.shape[0] if n.ndim >= 1 else 0, 3, 3))
+        return cls._rows(_lib.OBSTACLE_BOX, [("centers", centers, 3), ("half_extents", half_extents, 3), ("rotations", rotations, 9)], "box")
+
+    @classmethod
+    def half_spaces(cls, normals, offsets):
+        """unit normals (M, 3) pointing out of the solid, offsets (M,): the free side is n . y > offset."""
+        return cls._rows(_lib.OBSTACLE_HALFSPACE, [("normals", normals, 3), ("offsets", offsets, 1)], "half-space")
+
+    @classmethod
+    def concat(cls, *sets):
+        if not sets or not all(isinstance(s, ObstacleSet) for s in sets):
+            raise ValueError("concat takes one or more ObstacleSet")
+        return cls(np.concatenate([s.kinds for s in sets]), np.concatenate([s.params for s in sets]))
+
+    def __add__(self, other):
+        if not isinstance(other, ObstacleSet):
+            return NotImplemented
+        return ObstacleSet.concat(self, other)
+
+    @property
+    def n_prim(self) -> int:
+        return len(self.kinds)
+
+    def device_set(self, device_index: int = 0) -> _lib.ObstacleSet:
+        """the set's tables on a device (made with that device current), cached with the set."""
+        if device_index not in self._device_sets:
+            self._device_sets[device_index] = _lib.ObstacleSet(self.kinds, self.params)
+        return self._device_sets[device_index]
+
+    def __hash__(self):
+        return hash(self._key)
+
+    def __eq__(self, other):
+        return isinstance(other, ObstacleSet) and self._key == other._key
+
+    def __repr__(self):
+        names = ("spheres", "capsules", "boxes", "half-spaces")
+        return "ObstacleSet(" + ", ".join(f"{int((self.kinds == i).sum())} {n}" for i, n in enumerate(names) if (self.kinds == i).any()) + ")"
+
+
+def _check_obstacles(n_in, n_fixed, kin, robot, q, fixed_qpos, sphere_set, obstacles, obstacle_pos, obstacle_rot, what, margin=None,
+                     prim_weight=None, penalty=False):
+    """Every argument rule in the order of `_check` -- the sphere set, the links, the pairs, the obstacle set, the scalars, then
+    types, dtypes and shapes, and last the device -- before anything touches the GPU."""
+    import torch
+
+    if not isinstance(sphere_set, SphereSet):
+        raise ValueError("sphere_set must be a collision.SphereSet")
+    for n in sphere_set.table_links:
+        kin.body_frame_index(n)  # ValueError on an unknown link
+    pairs = _resolved_pairs(robot, sphere_set)
+    if not isinstance(obstacles, ObstacleSet):
+        raise ValueError("obstacles must be a collision.ObstacleSet")
+    if penalty and (isinstance(margin, bool) or not isinstance(margin, (int, float)) or not math.isfinite(margin) or margin < 0):
+        raise ValueError(f"margin must be a finite Python float >= 0, got {margin!r}")
+    B = q.shape[0] if isinstance(q, torch.Tensor) and q.ndim == 2 else None
+    named = [(n, t, s) for n, t, s in (("obstacle_pos", obstacle_pos, (B, 3)), ("obstacle_rot", obstacle_rot, (B, 3, 3))) if t is not None]
+    if penalty and prim_weight is not None:
+        named.append(("prim_weight", prim_weight, (obstacles.n_prim,)))
+    for name, t, _ in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+    for name, t, _ in named:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    for name, t, shape in named:
+        if (B is not None or shape[0] is not None) and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    _check_poses(n_in, n_fixed, q, fixed_qpos, sphere_set.table_links, what=what)  # (ends with the device)
+    for name, t, _ in named:
+        if t.device != q.device:
+            raise ValueError(f"{name} is on {t.device}, {what} on {q.device}: all tensors must be on one CUDA device")
+    return pairs
+
+
+def _obstacle_pose(obstacle_pos, obstacle_rot):
+    c = lambda a: None if a is None else a.detach().contiguous()  # noqa: E731
+    return c(obstacle_pos), c(obstacle_rot)
+
+
+def _obstacle_distances(model, obstacles, x, fixed_qpos, obstacle_pos, obstacle_rot, nearest):
+    import torch
+
+    B = x.shape[0]
+    xc, fixed = _inputs(x, fixed_qpos)
+    pos, rot = _obstacle_pose(obstacle_pos, obstacle_rot)
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    with torch.cuda.device(x.device):
+        dist = torch.empty((B, model.n_sphere), dtype=torch.float32, device=x.device)
+        near = torch.empty((B, model.n_sphere), dtype=torch.int32, device=x.device) if nearest else None
+        if B > 0:
+            model.obstacle_distances_dev(obstacles.device_set(torch.cuda.current_device()), B, xc.data_ptr(), ptr(fixed), dist.data_ptr(),
+                                         ptr(near), ptr(pos), ptr(rot), stream=torch.cuda.current_stream(x.device).cuda_stream)
+    return (dist, near) if nearest else dist
+
+
+def _obstacle_penalty(model, obstacles, x, fixed_qpos, margin, prim_weight, obstacle_pos, obstacle_rot, want_grad=True, want_wrench=False):
+    """one launch -> (E (B,), grad (B, n_in) or None, wrench (B, 6) or None)."""
+    import torch
+
+    B = x.shape[0]
+    xc, fixed = _inputs(x, fixed_qpos)
+    pos, rot = _obstacle_pose(obstacle_pos, obstacle_rot)
+    w = None if prim_weight is None else prim_weight.detach().contiguous()
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    with torch.cuda.device(x.device):
+        e = torch.empty((B,), dtype=torch.float32, device=x.device)
+        g = torch.empty((B, model.n_in), dtype=torch.float32, device=x.device) if want_grad else None
+        wr = torch.empty((B, 6), dtype=torch.float32, device=x.device) if want_wrench else None
+        if B > 0:
+            model.obstacle_penalty_dev(obstacles.device_set(torch.cuda.current_device()), B, xc.data_ptr(), ptr(fixed), float(margin), ptr(w),
+                                       e.data_ptr(), ptr(g), ptr(wr), ptr(pos), ptr(rot), stream=torch.cuda.current_stream(x.device).cuda_stream)
+    return e, g, wr
+
+
+def obstacle_distances(optimizer, q, sphere_set: SphereSet, obstacles: ObstacleSet, obstacle_pos=None, obstacle_rot=None, fixed_qpos=None,
+                       nearest: bool = False):
+    """Signed distance of every sphere of the set to the nearest primitive of `obstacles` at the optimiser's variables: q
+    (B, n_opt) float32 CUDA, obstacle_pos (B, 3) and obstacle_rot (B, 3, 3) float32 the world pose of the obstacle frame per
+    frame, or None (zero translation / identity: a shared scene) -> dist (B, S) float32 in the set's sphere order, negative
+    where a sphere penetrates; with `nearest=True` -> (dist, nearest (B, S) int32), the first primitive that attains the
+    minimum.  No autograd graph."""
+    pairs = _check_obstacles(optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q, fixed_qpos, sphere_set,
+                             obstacles, obstacle_pos, obstacle_rot, "q")
+    return _obstacle_distances(optimizer.sphere_model(sphere_set, pairs), obstacles, q, fixed_qpos, obstacle_pos, obstacle_rot, nearest)
+
+
+def obstacle_penalty(optimizer, q, sphere_set: SphereSet, obstacles: ObstacleSet, margin, obstacle_pos=None, obstacle_rot=None,
+                     prim_weight=None, fixed_qpos=None, wrench: bool = False):
+    """(E (B,), grad_q (B, n_opt)) float32 from ONE launch: E = sum_s sum_m w_m max(0, margin - d_sm)^2 over every sphere s of
+    the set and every primitive m, d_sm the signed distance of the sphere's surface to the primitive, and its gradient in q.
+    margin: a finite Python float >= 0 (metres); prim_weight (M,) float32 >= 0 or None (1), shared by the batch; obstacle_pos,
+    obstacle_rot as in `obstacle_distances`.  With `wrench=True` -> (E, grad_q, wrench (B, 6)): dE/d(obstacle translation) and
+    dE/d(a world-aligned small rotation of the obstacle about its origin).  No autograd graph: `autograd.obstacle_penalty` is
+    the same launch with one."""
+    pairs = _check_obstacles(optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q, fixed_qpos, sphere_set,
+                             obstacles, obstacle_pos, obstacle_rot, "q", margin, prim_weight, penalty=True)
+    e, g, wr = _obstacle_penalty(optimizer.sphere_model(sphere_set, pairs), obstacles, q, fixed_qpos, margin, prim_weight, obstacle_pos,
+                                 obstacle_rot, want_wrench=wrench)
+    return (e, g, wr) if wrench else (e, g)
+
+
+def robot_obstacle_distances(robot, qpos, sphere_set: SphereSet, obstacles: ObstacleSet, obstacle_pos=None, obstacle_rot=None,
+                             nearest: bool = False):
+    """The same for a full robot qpos (B, robot.dof) in dof order; every joint is a column of its own."""
+    pairs = _check_obstacles(robot.dof, 0, robot.kin, robot, qpos, None, sphere_set, obstacles, obstacle_pos, obstacle_rot, "qpos")
+    return _obstacle_distances(robot.sphere_model(sphere_set, pairs), obstacles, qpos, None, obstacle_pos, obstacle_rot, nearest)
+
+
+def robot_obstacle_penalty(robot, qpos, sphere_set: SphereSet, obstacles: ObstacleSet, margin, obstacle_pos=None, obstacle_rot=None,
+                           prim_weight=None, wrench: bool = False):
+    """(E (B,), grad_qpos (B, robot.dof)[, wrench (B, 6)]) for a full robot qpos in dof order."""
+    pairs = _check_obstacles(robot.dof, 0, robot.kin, robot, qpos, None, sphere_set, obstacles, obstacle_pos, obstacle_rot, "qpos", margin,
+                             prim_weight, penalty=True)
+    e, g, wr = _obstacle_penalty(robot.sphere_model(sphere_set, pairs), obstacles, qpos, None, margin, prim_weight, obstacle_pos, obstacle_rot,
+                                 want_wrench=wrench)
+    return (e, g, wr) if wrench else (e, g)
+
+
 __all__ = ["SphereSet", "default_pairs", "sphere_distances", "self_collision_penalty", "robot_sphere_distances",
-           "robot_self_collision_penalty", "resolve_self_collision", "robot_resolve_self_collision"]
+           "robot_self_collision_penalty", "resolve_self_collision", "robot_resolve_self_collision", "ObstacleSet", "obstacle_distances",
+           "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty"]

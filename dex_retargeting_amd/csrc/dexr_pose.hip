@@ -2039,3 +2039,6 @@ int dexr_link_ik_solve(const dexr_pose_model* m, int64_t B, const double* x0, co
 
 // ---- include/dexr_resolve.h: the collision-aware posture solve, the IK solve's resident loop with the sphere phases inside -----
 #include "dexr_resolve.hpp"
+
+// ---- include/dexr_obstacles.h: the robot's spheres against posed primitives, the sphere kernel with another phase B ------------
+#include "dexr_obstacles.hpp"
