@@ -79,6 +79,10 @@ OBSTACLE_EXPORTS = ["dexr_obstacle_set_create", "dexr_obstacle_set_destroy", "de
                     "dexr_obstacle_distances_vjp", "dexr_obstacle_penalty"]
 OBSTACLE_MAX, OBSTACLE_PARAMS = 64, 16  # DEXR_OBSTACLE_*
 OBSTACLE_SPHERE, OBSTACLE_CAPSULE, OBSTACLE_BOX, OBSTACLE_HALFSPACE = 0, 1, 2, 3  # primitive kinds
+# include/dexr_resolve_obstacles.h (the posture solve with the obstacle term, iterated inside one kernel): a list of its own
+RESOLVE_OBSTACLE_EXPORTS = ["dexr_sphere_resolve_obstacles_dev", "dexr_sphere_resolve_obstacles"]
+RESOLVE_MAXCONTACT = 256  # DEXR_RESOLVE_MAXCONTACT
+RESOLVE_CONTACTS_TRUNCATED = 8  # status bit
 UNIQUE_ID_BYTES = 128
 
 
@@ -180,6 +184,12 @@ def load() -> C.CDLL:
                                             C.c_float, C.c_float, C.c_int32, vp, vp, vp, vp, vp]
     lib.dexr_sphere_resolve.argtypes = [vp, i64, f64p, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, C.c_double, f64p,
                                         f64p, f64p, C.c_double, C.c_double, C.c_double, C.c_int32, f64p, i32p, f64p, i32p]
+    lib.dexr_sphere_resolve_obstacles_dev.argtypes = [vp, i64, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp,
+                                                      C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp, vp, C.c_float, C.c_float, vp, vp,
+                                                      vp, vp, vp, vp]
+    lib.dexr_sphere_resolve_obstacles.argtypes = [vp, i64, f64p, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, C.c_double,
+                                                  f64p, f64p, f64p, C.c_double, C.c_double, C.c_double, C.c_int32, vp, f64p, f64p, C.c_double,
+                                                  C.c_double, f64p, f64p, i32p, f64p, i32p]
     lib.dexr_obstacle_set_create.argtypes = [C.c_int32, i32p, f64p, C.POINTER(vp)]
     lib.dexr_obstacle_set_destroy.argtypes = [vp]
     lib.dexr_obstacle_set_destroy.restype = None
@@ -792,6 +802,66 @@ class SphereModel:
                                          d(pos_weight), d(rot_weight), float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi),
                                          float(damping), float(max_step), float(tol), int(max_iters), d(x), _ptr(iters, C.c_int32),
                                          d(energy), _ptr(status, C.c_int32)))
+        return x, iters, energy, status
+
+    # the posture solve with the obstacle term (include/dexr_resolve_obstacles.h) --------------------------------
+    def resolve_obstacles_dev(self, obstacles: "ObstacleSet", B: int, x0_ptr: int, fixed_ptr: int, margin: float, damping: float,
+                              max_iters: int, x_ptr: int, iters_ptr: int = 0, energy_ptr: int = 0, status_ptr: int = 0, x_ref_ptr: int = 0,
+                              posture_weight_ptr: int = 0, n_target: int = 0, target_pos_ptr: int = 0, target_rot_ptr: int = 0,
+                              pos_weight_ptr: int = 0, rot_weight_ptr: int = 0, collision_weight: float = 1.0, pair_weight_ptr: int = 0,
+                              lo_ptr: int = 0, hi_ptr: int = 0, tol: float = 0.0, max_step: float = 0.0, obstacle_pos_ptr: int = 0,
+                              obstacle_rot_ptr: int = 0, obstacle_margin=None, obstacle_weight: float = 1.0, prim_weight_ptr: int = 0,
+                              stream: int = 0):
+        """the arguments of resolve_dev, and obstacle_pos (B, 3) or 0, obstacle_rot (B, 3, 3) or 0, obstacle_margin (None: margin),
+        obstacle_weight, prim_weight (n_prim) or 0 -> x (B, n_in), iters (B) int32, energy (B, 4), status (B) int32, each of the last
+        three or 0 (dexr_sphere_resolve_obstacles_dev)."""
+        om = margin if obstacle_margin is None else obstacle_margin
+        check(load().dexr_sphere_resolve_obstacles_dev(
+            self._h, B, x0_ptr or None, fixed_ptr or None, x_ref_ptr or None, posture_weight_ptr or None, int(n_target), target_pos_ptr or None,
+            target_rot_ptr or None, pos_weight_ptr or None, rot_weight_ptr or None, float(margin), float(collision_weight), pair_weight_ptr or None,
+            lo_ptr or None, hi_ptr or None, float(damping), float(max_step), float(tol), int(max_iters), obstacles.handle, obstacle_pos_ptr or None,
+            obstacle_rot_ptr or None, float(om), float(obstacle_weight), prim_weight_ptr or None, x_ptr or None, iters_ptr or None,
+            energy_ptr or None, status_ptr or None, stream or None))
+
+    def resolve_obstacles(self, obstacles: "ObstacleSet", x0, margin=None, damping=None, max_iters=None, fixed=None, x_ref=None,
+                          posture_weight=None, target_pos=None, target_rot=None, pos_weight=None, rot_weight=None,
+                          collision_weight: float = 1.0, pair_weight=None, lo=None, hi=None, tol: float = 0.0, max_step: float = 0.0,
+                          n_target=None, obstacle_pos=None, obstacle_rot=None, obstacle_margin=None, obstacle_weight: float = 1.0,
+                          prim_weight=None):
+        """-> (x (B, n_in) float64, iters (B) int32, energy (B, 4) float64, status (B) int32) (dexr_sphere_resolve_obstacles): the
+        arguments of `resolve`, and the obstacle pose per frame or None, obstacle_margin (None: margin), obstacle_weight and
+        prim_weight (n_prim) or None."""
+        for name, v in (("margin", margin), ("damping", damping), ("max_iters", max_iters)):
+            if v is None:
+                raise ValueError(f"{name} is required")
+        x0, fixed, B = self._host_inputs(x0, fixed)
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi, prim_weight = (
+            f64(a) for a in (x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi, prim_weight))
+        pos, rot = self._host_pose(B, obstacle_pos, obstacle_rot)
+        if n_target is None:
+            n_target = 0 if target_pos is None and target_rot is None else (target_pos if target_pos is not None else target_rot).shape[1]
+        n_target = int(n_target)
+        shapes = (("x_ref", x_ref, (B, self.n_in)), ("posture_weight", posture_weight, (self.n_in,)), ("target_pos", target_pos, (B, n_target, 3)),
+                  ("target_rot", target_rot, (B, n_target, 3, 3)), ("pos_weight", pos_weight, (B, n_target)),
+                  ("rot_weight", rot_weight, (B, n_target)), ("pair_weight", pair_weight, (self.n_pair,)), ("lo", lo, (self.n_in,)),
+                  ("hi", hi, (self.n_in,)), ("prim_weight", prim_weight, (obstacles.n_prim,)))
+        for name, a, want in shapes:
+            if a is not None and a.shape != want:
+                raise ValueError(f"{name} must have shape {want}, got {a.shape}")
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        x = np.zeros((B, self.n_in), dtype=np.float64)
+        iters = np.zeros(B, dtype=np.int32)
+        energy = np.zeros((B, 4), dtype=np.float64)
+        status = np.zeros(B, dtype=np.int32)
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        om = margin if obstacle_margin is None else obstacle_margin
+        check(load().dexr_sphere_resolve_obstacles(
+            self._h, B, d(x0), d(fixed), d(x_ref), d(posture_weight), n_target, d(target_pos), d(target_rot), d(pos_weight), d(rot_weight),
+            float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi), float(damping), float(max_step), float(tol), int(max_iters),
+            obstacles.handle, d(pos), d(rot), float(om), float(obstacle_weight), d(prim_weight), d(x), _ptr(iters, C.c_int32), d(energy),
+            _ptr(status, C.c_int32)))
         return x, iters, energy, status
 
     # the model's spheres against an obstacle set (include/dexr_obstacles.h); the pair list plays no part --------------

@@ -2042,3 +2042,6 @@ int dexr_link_ik_solve(const dexr_pose_model* m, int64_t B, const double* x0, co
 
 // ---- include/dexr_obstacles.h: the robot's spheres against posed primitives, the sphere kernel with another phase B ------------
 #include "dexr_obstacles.hpp"
+
+// ---- include/dexr_resolve_obstacles.h: the posture solve with the obstacle term, both kernels' phases in one resident loop -----
+#include "dexr_resolve_obstacles.hpp"

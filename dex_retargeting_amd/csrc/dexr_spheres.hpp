@@ -219,6 +219,7 @@ struct dexr_sphere_model {
   int32_t* inc_ptr = nullptr;
   uint32_t* inc = nullptr;
   uint32_t* pair_sph = nullptr;  // (n_pair): the two spheres of a pair by sorted index, first | second << 7 (dexr_resolve.hpp)
+  int32_t* sph_in = nullptr;     // (n_sphere): the sorted index of the caller's sphere, the inverse of sph_out (dexr_resolve_obstacles.hpp)
 };
 
 namespace {
@@ -401,6 +402,7 @@ int dexr_sphere_model_create(const void* pose_blob, size_t nbytes, int32_t n_sph
   if (e == hipSuccess) e = upload_vector(inc_ptr, &m->inc_ptr);
   if (e == hipSuccess) e = upload_vector(inc, &m->inc);
   if (e == hipSuccess) e = upload_vector(pair_sph, &m->pair_sph);
+  if (e == hipSuccess) e = upload_vector(pos_of, &m->sph_in);
   if (e != hipSuccess) {
     dexr_sphere_model_destroy(m);
     return dexr_set_error(DEXR_ERR_HIP, "uploading sphere tables failed: %s", hipGetErrorString(e));
@@ -421,6 +423,7 @@ void dexr_sphere_model_destroy(dexr_sphere_model* m) {
   if (m->inc_ptr) (void)hipFree(m->inc_ptr);
   if (m->inc) (void)hipFree(m->inc);
   if (m->pair_sph) (void)hipFree(m->pair_sph);
+  if (m->sph_in) (void)hipFree(m->sph_in);
   delete m;
 }
 
