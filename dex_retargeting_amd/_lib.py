@@ -83,6 +83,12 @@ OBSTACLE_SPHERE, OBSTACLE_CAPSULE, OBSTACLE_BOX, OBSTACLE_HALFSPACE = 0, 1, 2, 3
 RESOLVE_OBSTACLE_EXPORTS = ["dexr_sphere_resolve_obstacles_dev", "dexr_sphere_resolve_obstacles"]
 RESOLVE_MAXCONTACT = 256  # DEXR_RESOLVE_MAXCONTACT
 RESOLVE_CONTACTS_TRUNCATED = 8  # status bit
+# include/dexr_sdf_grid.h (the spheres of a sphere model against one sampled signed-distance field: distances, their VJP, the fused
+# penalty): a list of its own
+SDF_GRID_EXPORTS = ["dexr_sdf_grid_create", "dexr_sdf_grid_destroy", "dexr_sdf_grid_info", "dexr_grid_distances_dev",
+                    "dexr_grid_distances_vjp_dev", "dexr_grid_penalty_dev", "dexr_grid_distances", "dexr_grid_distances_vjp",
+                    "dexr_grid_penalty"]
+SDF_GRID_MIN_DIM, SDF_GRID_MAX_DIM, SDF_GRID_MAX_SAMPLES = 2, 1024, 1 << 24  # DEXR_SDF_GRID_*
 UNIQUE_ID_BYTES = 128
 
 
@@ -200,6 +206,16 @@ def load() -> C.CDLL:
     lib.dexr_obstacle_distances.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, f64p, i32p]
     lib.dexr_obstacle_distances_vjp.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, f64p, f64p]
     lib.dexr_obstacle_penalty.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, C.c_double, f64p, f64p, f64p, f64p]
+    lib.dexr_sdf_grid_create.argtypes = [i32p, f64p, f64p, f32p, C.POINTER(vp)]
+    lib.dexr_sdf_grid_destroy.argtypes = [vp]
+    lib.dexr_sdf_grid_destroy.restype = None
+    lib.dexr_sdf_grid_info.argtypes = [vp, i32p, f64p, f64p]
+    lib.dexr_grid_distances_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.dexr_grid_distances_vjp_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.dexr_grid_penalty_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]
+    lib.dexr_grid_distances.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, f64p]
+    lib.dexr_grid_distances_vjp.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, f64p, f64p]
+    lib.dexr_grid_penalty.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, C.c_double, f64p, f64p, f64p]
     _lib = lib
     return lib
 
@@ -937,6 +953,61 @@ class SphereModel:
                                            d(gx), d(wr)))
         return e, gx, wr
 
+    # the model's spheres against a sampled signed-distance field (include/dexr_sdf_grid.h); the pair list plays no part ----
+    def grid_distances_dev(self, grid: "SdfGrid", B: int, x_ptr: int, fixed_ptr: int, dist_ptr: int, obstacle_pos_ptr: int = 0,
+                           obstacle_rot_ptr: int = 0, stream: int = 0):
+        """x (B, n_in), fixed (B, n_fixed) or 0, obstacle_pos (B, 3) or 0, obstacle_rot (B, 3, 3) or 0 -> dist (B, n_sphere)
+        (dexr_grid_distances_dev)."""
+        check(load().dexr_grid_distances_dev(self._h, grid.handle, B, x_ptr or None, fixed_ptr or None, obstacle_pos_ptr or None,
+                                             obstacle_rot_ptr or None, dist_ptr or None, stream or None))
+
+    def grid_distances_vjp_dev(self, grid: "SdfGrid", B: int, x_ptr: int, fixed_ptr: int, grad_dist_ptr: int, grad_x_ptr: int,
+                               obstacle_pos_ptr: int = 0, obstacle_rot_ptr: int = 0, stream: int = 0):
+        """grad_dist (B, n_sphere) -> grad_x (B, n_in), every entry written (dexr_grid_distances_vjp_dev)."""
+        check(load().dexr_grid_distances_vjp_dev(self._h, grid.handle, B, x_ptr or None, fixed_ptr or None, obstacle_pos_ptr or None,
+                                                 obstacle_rot_ptr or None, grad_dist_ptr or None, grad_x_ptr or None, stream or None))
+
+    def grid_penalty_dev(self, grid: "SdfGrid", B: int, x_ptr: int, fixed_ptr: int, margin: float, energy_ptr: int, grad_x_ptr: int,
+                         wrench_ptr: int = 0, obstacle_pos_ptr: int = 0, obstacle_rot_ptr: int = 0, stream: int = 0):
+        """margin >= 0 -> energy (B), grad_x (B, n_in), wrench (B, 6), each may be 0 but not all, from one launch
+        (dexr_grid_penalty_dev)."""
+        check(load().dexr_grid_penalty_dev(self._h, grid.handle, B, x_ptr or None, fixed_ptr or None, obstacle_pos_ptr or None,
+                                           obstacle_rot_ptr or None, float(margin), energy_ptr or None, grad_x_ptr or None,
+                                           wrench_ptr or None, stream or None))
+
+    def grid_distances(self, grid: "SdfGrid", x, fixed=None, obstacle_pos=None, obstacle_rot=None):
+        """-> dist (B, n_sphere) float64 (dexr_grid_distances)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        pos, rot = self._host_pose(B, obstacle_pos, obstacle_rot)
+        dist = np.zeros((B, self.n_sphere), dtype=np.float64)
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        check(load().dexr_grid_distances(self._h, grid.handle, B, d(x), d(fixed), d(pos), d(rot), d(dist)))
+        return dist
+
+    def grid_distances_vjp(self, grid: "SdfGrid", x, grad_dist, fixed=None, obstacle_pos=None, obstacle_rot=None):
+        """-> grad_x (B, n_in) float64 (dexr_grid_distances_vjp)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        pos, rot = self._host_pose(B, obstacle_pos, obstacle_rot)
+        grad_dist = np.ascontiguousarray(grad_dist, dtype=np.float64)
+        if grad_dist.shape != (B, self.n_sphere):
+            raise ValueError(f"grad_dist must have shape ({B}, {self.n_sphere}), got {grad_dist.shape}")
+        gx = np.zeros((B, self.n_in), dtype=np.float64)
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        check(load().dexr_grid_distances_vjp(self._h, grid.handle, B, d(x), d(fixed), d(pos), d(rot), d(grad_dist), d(gx)))
+        return gx
+
+    def grid_penalty(self, grid: "SdfGrid", x, margin, fixed=None, obstacle_pos=None, obstacle_rot=None, want_energy: bool = True,
+                     want_grad: bool = True, want_wrench: bool = True):
+        """-> (energy (B), grad_x (B, n_in), wrench (B, 6)) float64, None where not wanted (dexr_grid_penalty)."""
+        x, fixed, B = self._host_inputs(x, fixed)
+        pos, rot = self._host_pose(B, obstacle_pos, obstacle_rot)
+        e = np.zeros(B, dtype=np.float64) if want_energy else None
+        gx = np.zeros((B, self.n_in), dtype=np.float64) if want_grad else None
+        wr = np.zeros((B, 6), dtype=np.float64) if want_wrench else None
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        check(load().dexr_grid_penalty(self._h, grid.handle, B, d(x), d(fixed), d(pos), d(rot), float(margin), d(e), d(gx), d(wr)))
+        return e, gx, wr
+
 
 class ObstacleSet:
     """Owns one dexr_obstacle_set (include/dexr_obstacles.h): 1 .. OBSTACLE_MAX primitives of an obstacle frame, resident in HBM.
@@ -959,6 +1030,36 @@ class ObstacleSet:
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib is not None:
             _lib.dexr_obstacle_set_destroy(h)
+            self._h = None
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+
+class SdfGrid:
+    """Owns one dexr_sdf_grid (include/dexr_sdf_grid.h): float32 samples values (nx, ny, nz) of a signed-distance field in C order,
+    resident in HBM; sample (ix, iy, iz) sits at origin + (ix, iy, iz) * spacing of the obstacle frame.  Any SphereModel's grid_*
+    methods take it."""
+
+    def __init__(self, values, origin, spacing):
+        lib = load()
+        self._h = C.c_void_p()
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
+        spacing = np.ascontiguousarray(spacing, dtype=np.float64).reshape(-1)
+        if values.ndim != 3 or origin.shape != (3,) or spacing.shape != (3,):
+            raise ValueError(f"values must have shape (nx, ny, nz), origin and spacing (3,), got {values.shape}, {origin.shape}, {spacing.shape}")
+        n = np.array(values.shape, dtype=np.int32)
+        check(lib.dexr_sdf_grid_create(_ptr(n, C.c_int32), _ptr(origin, C.c_double), _ptr(spacing, C.c_double), _ptr(values, C.c_float),
+                                       C.byref(self._h)))
+        check(lib.dexr_sdf_grid_info(self._h, _ptr(n, C.c_int32), None, None))
+        self.shape = tuple(int(v) for v in n)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib is not None:
+            _lib.dexr_sdf_grid_destroy(h)
             self._h = None
 
     @property

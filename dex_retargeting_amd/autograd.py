@@ -637,6 +637,139 @@ def robot_obstacle_penalty(robot, qpos, sphere_set, obstacles, margin, obstacle_
                                         float(margin), prim_weight)
 
 
+# ---- the spheres against a sampled signed-distance field: the obstacle functions with a grid on the other side ---------------------
+def _make_grid_functions():
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _GridDistances(torch.autograd.Function):
+        """Saves x, fixed and the obstacle pose only: the VJP kernel recomputes the walk, the cell and its gradient."""
+
+        @staticmethod
+        def forward(ctx, x, fixed_qpos, obstacle_pos, obstacle_rot, model, grid):
+            from . import collision
+
+            dist = collision._grid_distances(model, grid, x, fixed_qpos, obstacle_pos, obstacle_rot)
+            xc, fixed = collision._inputs(x, fixed_qpos)
+            pos, rot = collision._obstacle_pose(obstacle_pos, obstacle_rot)
+            ctx.model, ctx.grid = model, grid
+            ctx.have = [a is not None for a in (fixed, pos, rot)]
+            ctx.save_for_backward(*[a for a in (xc, fixed, pos, rot) if a is not None])
+            return dist
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_dist):
+            if not ctx.needs_input_grad[0]:
+                return (None,) * 6
+            saved = list(ctx.saved_tensors)
+            x = saved.pop(0)
+            fixed, pos, rot = (saved.pop(0) if h else None for h in ctx.have)
+            B = x.shape[0]
+            gd = grad_dist.detach().to(torch.float32).contiguous()
+            gx = torch.empty_like(x)  # (the kernel writes every entry)
+            ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+            if B > 0:
+                with torch.cuda.device(x.device):
+                    ctx.model.grid_distances_vjp_dev(ctx.grid.device_grid(torch.cuda.current_device()), B, x.data_ptr(), ptr(fixed),
+                                                     gd.data_ptr(), gx.data_ptr(), ptr(pos), ptr(rot),
+                                                     stream=torch.cuda.current_stream(x.device).cuda_stream)
+            return (gx,) + (None,) * 5
+
+    class _GridPenalty(torch.autograd.Function):
+        """The forward launch gives E, dE/dx and the wrench together where they are needed; backward scales what it saved."""
+
+        @staticmethod
+        def forward(ctx, x, fixed_qpos, obstacle_pos, obstacle_rot, model, grid, margin):
+            from . import collision
+
+            want_x = bool(ctx.needs_input_grad[0])
+            want_p = obstacle_pos is not None and bool(ctx.needs_input_grad[2])
+            e, g, wr = collision._grid_penalty(model, grid, x, fixed_qpos, margin, obstacle_pos, obstacle_rot, want_grad=want_x,
+                                               want_wrench=want_p)
+            ctx.want = (want_x, want_p)
+            ctx.save_for_backward(*[a for a in (g, wr) if a is not None])
+            return e
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_e):
+            saved = list(ctx.saved_tensors)
+            ge = grad_e.to(torch.float32)[:, None]
+            gx = ge * saved.pop(0) if ctx.want[0] else None
+            gp = ge * saved.pop(0)[:, :3] if ctx.want[1] else None  # dE/d(obstacle translation): the force half of the wrench
+            return (gx, None, gp) + (None,) * 4
+
+    return _GridDistances, _GridPenalty
+
+
+_GRID_FNS = None
+
+
+def _grid_fns():
+    global _GRID_FNS
+    if _GRID_FNS is None:
+        _GRID_FNS = _make_grid_functions()
+    return _GRID_FNS
+
+
+def grid_distances(optimizer, q, sphere_set, grid, obstacle_pos=None, obstacle_rot=None, fixed_qpos=None):
+    """`collision.grid_distances` with an autograd graph: dist (B, S) float32, the same bits; backward is the distance VJP kernel
+    (dexr_grid_distances_vjp_dev).  Gradients flow to q only; once differentiable."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(obstacle_rot)
+    pairs = collision._check_obstacles(optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q, fixed_qpos,
+                                       sphere_set, grid, obstacle_pos, obstacle_rot, "q", grid=True)
+    with torch.cuda.device(q.device):
+        return _grid_fns()[0].apply(q, fixed_qpos, obstacle_pos, obstacle_rot, optimizer.sphere_model(sphere_set, pairs), grid)
+
+
+def grid_penalty(optimizer, q, sphere_set, grid, margin, obstacle_pos=None, obstacle_rot=None, fixed_qpos=None):
+    """`collision.grid_penalty` with an autograd graph: E (B,) float32.  Where q or obstacle_pos needs a gradient the forward launch
+    computes E, dE/dq and the wrench together (one launch, the same bits as the no-graph call); backward is grad_E[:, None] *
+    dE/dq for q and grad_E[:, None] * wrench[:, :3] for obstacle_pos.  No gradient flows to obstacle_rot (one that requires grad
+    is a ValueError: `collision.grid_penalty(..., wrench=True)` gives the torque), to fixed_qpos or to the samples; once
+    differentiable."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(obstacle_rot)
+    pairs = collision._check_obstacles(optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q, fixed_qpos,
+                                       sphere_set, grid, obstacle_pos, obstacle_rot, "q", margin, penalty=True, grid=True)
+    with torch.cuda.device(q.device):
+        return _grid_fns()[1].apply(q, fixed_qpos, obstacle_pos, obstacle_rot, optimizer.sphere_model(sphere_set, pairs), grid, float(margin))
+
+
+def robot_grid_distances(robot, qpos, sphere_set, grid, obstacle_pos=None, obstacle_rot=None):
+    """The same for a full robot qpos (B, robot.dof) float32 in dof order."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(obstacle_rot)
+    pairs = collision._check_obstacles(robot.dof, 0, robot.kin, robot, qpos, None, sphere_set, grid, obstacle_pos, obstacle_rot, "qpos", grid=True)
+    with torch.cuda.device(qpos.device):
+        return _grid_fns()[0].apply(qpos, None, obstacle_pos, obstacle_rot, robot.sphere_model(sphere_set, pairs), grid)
+
+
+def robot_grid_penalty(robot, qpos, sphere_set, grid, margin, obstacle_pos=None, obstacle_rot=None):
+    """The same for a full robot qpos (B, robot.dof) float32 in dof order."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(obstacle_rot)
+    pairs = collision._check_obstacles(robot.dof, 0, robot.kin, robot, qpos, None, sphere_set, grid, obstacle_pos, obstacle_rot, "qpos",
+                                       margin, penalty=True, grid=True)
+    with torch.cuda.device(qpos.device):
+        return _grid_fns()[1].apply(qpos, None, obstacle_pos, obstacle_rot, robot.sphere_model(sphere_set, pairs), grid, float(margin))
+
+
 __all__ = ["retarget", "ref_value_from_keypoints", "link_poses", "robot_link_poses", "link_velocities", "robot_link_velocities",
            "sphere_distances", "self_collision_penalty", "robot_sphere_distances", "robot_self_collision_penalty", "obstacle_distances",
-           "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty"]
+           "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty", "grid_distances", "grid_penalty", "robot_grid_distances",
+           "robot_grid_penalty"]

@@ -22,9 +22,15 @@ primitive) entry, its gradient in q and, asked for, the wrench on the obstacle, 
 is ``resolve_self_collision`` with that energy added (include/dexr_resolve_obstacles.h): one launch takes retargeted postures out of
 the robot's own links and out of the object.
 
+An ``SdfGrid`` is an obstacle that no handful of primitives describes -- a mesh, a scan, a depth fusion -- as float32 samples of
+its signed-distance field on a regular grid of the obstacle frame (include/dexr_sdf_grid.h, csrc/dexr_sdf_grid.hpp), posed like
+an ``ObstacleSet``.  ``grid_distances`` and ``grid_penalty`` are ``obstacle_distances`` and ``obstacle_penalty`` against it: one
+trilinear lookup per sphere however complex the shape is, the distance continued outside the grid's box by the distance to the
+box.  ``SdfGrid.from_obstacles`` samples an ``ObstacleSet``.
+
 The outputs of this module carry NO autograd graph; ``autograd.sphere_distances``, ``autograd.self_collision_penalty``,
-``autograd.obstacle_distances`` and ``autograd.obstacle_penalty`` are the same kernels with one, so that a penetration loss
-composes with ``autograd.retarget`` and reaches the keypoints.
+``autograd.obstacle_distances``, ``autograd.obstacle_penalty``, ``autograd.grid_distances`` and ``autograd.grid_penalty`` are the
+same kernels with one, so that a penetration loss composes with ``autograd.retarget`` and reaches the keypoints.
 """
 from __future__ import annotations
 
@@ -510,9 +516,9 @@ class ObstacleSet:
 
 
 def _check_obstacles(n_in, n_fixed, kin, robot, q, fixed_qpos, sphere_set, obstacles, obstacle_pos, obstacle_rot, what, margin=None,
-                     prim_weight=None, penalty=False):
-    """Every argument rule in the order of `_check` -- the sphere set, the links, the pairs, the obstacle set, the scalars, then
-    types, dtypes and shapes, and last the device -- before anything touches the GPU."""
+                     prim_weight=None, penalty=False, grid=False):
+    """Every argument rule in the order of `_check` -- the sphere set, the links, the pairs, the obstacle set (with `grid` an
+    SdfGrid), the scalars, then types, dtypes and shapes, and last the device -- before anything touches the GPU."""
     import torch
 
     if not isinstance(sphere_set, SphereSet):
@@ -520,7 +526,9 @@ def _check_obstacles(n_in, n_fixed, kin, robot, q, fixed_qpos, sphere_set, obsta
     for n in sphere_set.table_links:
         kin.body_frame_index(n)  # ValueError on an unknown link
     pairs = _resolved_pairs(robot, sphere_set)
-    if not isinstance(obstacles, ObstacleSet):
+    if grid and not isinstance(obstacles, SdfGrid):
+        raise ValueError("grid must be a collision.SdfGrid")
+    if not grid and not isinstance(obstacles, ObstacleSet):
         raise ValueError("obstacles must be a collision.ObstacleSet")
     if penalty and (isinstance(margin, bool) or not isinstance(margin, (int, float)) or not math.isfinite(margin) or margin < 0):
         raise ValueError(f"margin must be a finite Python float >= 0, got {margin!r}")
@@ -628,6 +636,184 @@ def robot_obstacle_penalty(robot, qpos, sphere_set: SphereSet, obstacles: Obstac
     return (e, g, wr) if wrench else (e, g)
 
 
+# ---- a sampled signed-distance field: the robot's spheres against a mesh, a scan, a depth fusion (include/dexr_sdf_grid.h) -------------
+def _primitive_sdf(kind, v, y):
+    """the signed distance of the points y (..., 3) to one primitive of an ObstacleSet, the formulas of include/dexr_obstacles.h"""
+    if kind == _lib.OBSTACLE_HALFSPACE:
+        return y @ v[:3] - v[3]
+    if kind == _lib.OBSTACLE_BOX:
+        q = np.abs((y - v[:3]) @ v[6:15].reshape(3, 3)) - v[3:6]
+        mx = q.max(-1)
+        return np.where(mx <= 0, mx, np.linalg.norm(np.maximum(q, 0.0), axis=-1))
+    if kind == _lib.OBSTACLE_CAPSULE:
+        a, ab, r = v[:3], v[3:6] - v[:3], v[6]
+        l2 = ab @ ab
+        t = np.clip((y - a) @ ab / l2, 0.0, 1.0) if l2 > 0 else np.zeros(y.shape[:-1])
+        return np.linalg.norm(y - (a + t[..., None] * ab), axis=-1) - r
+    return np.linalg.norm(y - v[:3], axis=-1) - v[3]
+
+
+class SdfGrid:
+    """A signed-distance field sampled on a regular grid of an obstacle frame: plain data, immutable, hashable by content.
+
+    values   (nx, ny, nz) float32 samples in C order (kept as float32: what the device holds), each dimension 2 .. 1024, at most
+             2^24 samples, all finite
+    origin   (3,) or a scalar: the position of sample (0, 0, 0) in the obstacle frame, finite
+    spacing  (3,) or a scalar: the distance between samples along each axis, finite and > 0 (it may differ per axis)
+
+    Sample (ix, iy, iz) sits at origin + (ix, iy, iz) * spacing.  Between samples the field is the trilinear interpolant, outside
+    the grid's box it is the interpolant at the nearest point of the box plus the distance to the box (include/dexr_sdf_grid.h).
+    The rules are those of dexr_sdf_grid_create; a broken one is a ValueError.  `SdfGrid.from_obstacles` samples an ObstacleSet.
+    The device copy of a grid is made at its first use and kept with it (`device_grid`)."""
+
+    def __init__(self, values, origin, spacing):
+        with np.errstate(over="ignore"):  # (a value beyond float32 becomes an infinity, which is refused below)
+            v = np.array(values, dtype=np.float32)
+        if v.ndim != 3:
+            raise ValueError(f"values must have shape (nx, ny, nz), got {v.shape}")
+        try:
+            o = np.array(np.broadcast_to(np.asarray(origin, dtype=np.float64), (3,)))
+            h = np.array(np.broadcast_to(np.asarray(spacing, dtype=np.float64), (3,)))
+        except ValueError:
+            raise ValueError("origin and spacing must each be a scalar or have shape (3,)") from None
+        lo, hi = _lib.SDF_GRID_MIN_DIM, _lib.SDF_GRID_MAX_DIM
+        if min(v.shape) < lo or max(v.shape) > hi:
+            raise ValueError(f"every dimension of a grid is {lo}..{hi} samples, got {v.shape}")
+        if v.size > _lib.SDF_GRID_MAX_SAMPLES:
+            raise ValueError(f"a grid holds at most {_lib.SDF_GRID_MAX_SAMPLES} samples, got {v.size}")
+        with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+            inv_ok = np.isfinite(1.0 / h).all()
+        if not (np.isfinite(h).all() and (h > 0).all() and inv_ok):
+            raise ValueError(f"spacing must be finite and > 0, got {h.tolist()}")
+        if not np.isfinite(o).all():
+            raise ValueError(f"origin must be finite, got {o.tolist()}")
+        if not np.isfinite(v).all():
+            raise ValueError("the samples must be finite")
+        v = np.ascontiguousarray(v)
+        for a in (v, o, h):
+            a.setflags(write=False)
+        self.values, self.origin, self.spacing = v, o, h
+        self._key = (v.shape, v.tobytes(), o.tobytes(), h.tobytes())
+        self._hash = hash(self._key)
+        self._device_grids = {}
+
+    @classmethod
+    def from_obstacles(cls, obstacle_set: ObstacleSet, origin, spacing, shape):
+        """the union of an ObstacleSet sampled in float64 -- the minimum over its primitives of the signed distances of
+        include/dexr_obstacles.h -- on `shape` = (nx, ny, nz) (or one int for all three) samples from `origin` at `spacing`, rounded
+        to float32: a grid of a known shape without a mesh library."""
+        if not isinstance(obstacle_set, ObstacleSet):
+            raise ValueError("obstacle_set must be a collision.ObstacleSet")
+        try:
+            n = tuple(int(k) for k in np.broadcast_to(np.asarray(shape), (3,)))
+            o = np.broadcast_to(np.asarray(origin, dtype=np.float64), (3,))
+            h = np.broadcast_to(np.asarray(spacing, dtype=np.float64), (3,))
+        except (ValueError, TypeError):
+            raise ValueError("shape, origin and spacing must each be a scalar or have shape (3,)") from None
+        if min(n) < _lib.SDF_GRID_MIN_DIM or max(n) > _lib.SDF_GRID_MAX_DIM or n[0] * n[1] * n[2] > _lib.SDF_GRID_MAX_SAMPLES:
+            raise ValueError(f"every dimension of a grid is {_lib.SDF_GRID_MIN_DIM}..{_lib.SDF_GRID_MAX_DIM} samples and there are at most "
+                             f"{_lib.SDF_GRID_MAX_SAMPLES}, got {n}")
+        ax = [o[a] + np.arange(n[a]) * h[a] for a in range(3)]
+        values = np.empty(n, dtype=np.float32)
+        for ix in range(n[0]):  # a slab at a time: the memory of one slab per primitive, whatever the grid
+            y = np.stack(np.broadcast_arrays(ax[0][ix], ax[1][:, None], ax[2][None, :]), -1)
+            d = np.full(n[1:], np.inf)
+            for kind, v in zip(obstacle_set.kinds, obstacle_set.params):
+                d = np.minimum(d, _primitive_sdf(kind, v, y))
+            values[ix] = d
+        return cls(values, o, h)
+
+    @property
+    def shape(self):
+        return self.values.shape
+
+    def device_grid(self, device_index: int = 0) -> _lib.SdfGrid:
+        """the grid's samples on a device (made with that device current), cached with the grid."""
+        if device_index not in self._device_grids:
+            self._device_grids[device_index] = _lib.SdfGrid(self.values, self.origin, self.spacing)
+        return self._device_grids[device_index]
+
+    def __hash__(self):
+        return self._hash
+
+    def __eq__(self, other):
+        return isinstance(other, SdfGrid) and self._key == other._key
+
+    def __repr__(self):
+        return f"SdfGrid({'x'.join(str(k) for k in self.shape)} samples, origin {self.origin.tolist()}, spacing {self.spacing.tolist()})"
+
+
+def _grid_distances(model, grid, x, fixed_qpos, obstacle_pos, obstacle_rot):
+    import torch
+
+    B = x.shape[0]
+    xc, fixed = _inputs(x, fixed_qpos)
+    pos, rot = _obstacle_pose(obstacle_pos, obstacle_rot)
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    with torch.cuda.device(x.device):
+        dist = torch.empty((B, model.n_sphere), dtype=torch.float32, device=x.device)
+        if B > 0:
+            model.grid_distances_dev(grid.device_grid(torch.cuda.current_device()), B, xc.data_ptr(), ptr(fixed), dist.data_ptr(), ptr(pos),
+                                     ptr(rot), stream=torch.cuda.current_stream(x.device).cuda_stream)
+    return dist
+
+
+def _grid_penalty(model, grid, x, fixed_qpos, margin, obstacle_pos, obstacle_rot, want_grad=True, want_wrench=False):
+    """one launch -> (E (B,), grad (B, n_in) or None, wrench (B, 6) or None)."""
+    import torch
+
+    B = x.shape[0]
+    xc, fixed = _inputs(x, fixed_qpos)
+    pos, rot = _obstacle_pose(obstacle_pos, obstacle_rot)
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    with torch.cuda.device(x.device):
+        e = torch.empty((B,), dtype=torch.float32, device=x.device)
+        g = torch.empty((B, model.n_in), dtype=torch.float32, device=x.device) if want_grad else None
+        wr = torch.empty((B, 6), dtype=torch.float32, device=x.device) if want_wrench else None
+        if B > 0:
+            model.grid_penalty_dev(grid.device_grid(torch.cuda.current_device()), B, xc.data_ptr(), ptr(fixed), float(margin), e.data_ptr(),
+                                   ptr(g), ptr(wr), ptr(pos), ptr(rot), stream=torch.cuda.current_stream(x.device).cuda_stream)
+    return e, g, wr
+
+
+def grid_distances(optimizer, q, sphere_set: SphereSet, grid: SdfGrid, obstacle_pos=None, obstacle_rot=None, fixed_qpos=None):
+    """Signed distance of every sphere of the set to the field of `grid` at the optimiser's variables: q (B, n_opt) float32 CUDA,
+    obstacle_pos (B, 3) and obstacle_rot (B, 3, 3) float32 the world pose of the grid's frame per frame, or None (zero translation
+    / identity: a shared scene) -> dist (B, S) float32 in the set's sphere order, negative where a sphere penetrates.  One
+    trilinear lookup per sphere, whatever the shape.  No autograd graph."""
+    pairs = _check_obstacles(optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q, fixed_qpos, sphere_set,
+                             grid, obstacle_pos, obstacle_rot, "q", grid=True)
+    return _grid_distances(optimizer.sphere_model(sphere_set, pairs), grid, q, fixed_qpos, obstacle_pos, obstacle_rot)
+
+
+def grid_penalty(optimizer, q, sphere_set: SphereSet, grid: SdfGrid, margin, obstacle_pos=None, obstacle_rot=None, fixed_qpos=None,
+                 wrench: bool = False):
+    """(E (B,), grad_q (B, n_opt)) float32 from ONE launch: E = sum_s max(0, margin - d_s)^2 over every sphere s of the set, d_s
+    the signed distance of the sphere's surface to the field, and its gradient in q.  margin: a finite Python float >= 0
+    (metres); obstacle_pos, obstacle_rot as in `grid_distances`.  With `wrench=True` -> (E, grad_q, wrench (B, 6)):
+    dE/d(obstacle translation) and dE/d(a world-aligned small rotation of the obstacle about its origin).  No autograd graph:
+    `autograd.grid_penalty` is the same launch with one."""
+    pairs = _check_obstacles(optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q, fixed_qpos, sphere_set,
+                             grid, obstacle_pos, obstacle_rot, "q", margin, penalty=True, grid=True)
+    e, g, wr = _grid_penalty(optimizer.sphere_model(sphere_set, pairs), grid, q, fixed_qpos, margin, obstacle_pos, obstacle_rot,
+                             want_wrench=wrench)
+    return (e, g, wr) if wrench else (e, g)
+
+
+def robot_grid_distances(robot, qpos, sphere_set: SphereSet, grid: SdfGrid, obstacle_pos=None, obstacle_rot=None):
+    """The same for a full robot qpos (B, robot.dof) in dof order; every joint is a column of its own."""
+    pairs = _check_obstacles(robot.dof, 0, robot.kin, robot, qpos, None, sphere_set, grid, obstacle_pos, obstacle_rot, "qpos", grid=True)
+    return _grid_distances(robot.sphere_model(sphere_set, pairs), grid, qpos, None, obstacle_pos, obstacle_rot)
+
+
+def robot_grid_penalty(robot, qpos, sphere_set: SphereSet, grid: SdfGrid, margin, obstacle_pos=None, obstacle_rot=None, wrench: bool = False):
+    """(E (B,), grad_qpos (B, robot.dof)[, wrench (B, 6)]) for a full robot qpos in dof order."""
+    pairs = _check_obstacles(robot.dof, 0, robot.kin, robot, qpos, None, sphere_set, grid, obstacle_pos, obstacle_rot, "qpos", margin,
+                             penalty=True, grid=True)
+    e, g, wr = _grid_penalty(robot.sphere_model(sphere_set, pairs), grid, qpos, None, margin, obstacle_pos, obstacle_rot, want_wrench=wrench)
+    return (e, g, wr) if wrench else (e, g)
+
+
 # ---- the posture solve with the obstacle term (include/dexr_resolve_obstacles.h) -----------------------------------------------------
 def _resolve_obstacles(model_of, n_in, n_fixed, kin, robot, x0, what, fixed_qpos, sphere_set, obstacles, margin, obstacle_margin, obstacle_pos,
                        obstacle_rot, obstacle_weight, prim_weight, damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight,
@@ -716,4 +902,5 @@ def robot_resolve_collisions(robot, qpos0, sphere_set: SphereSet, obstacles: Obs
 
 __all__ = ["SphereSet", "default_pairs", "sphere_distances", "self_collision_penalty", "robot_sphere_distances",
            "robot_self_collision_penalty", "resolve_self_collision", "robot_resolve_self_collision", "ObstacleSet", "obstacle_distances",
-           "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty", "resolve_collisions", "robot_resolve_collisions"]
+           "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty", "resolve_collisions", "robot_resolve_collisions", "SdfGrid",
+           "grid_distances", "grid_penalty", "robot_grid_distances", "robot_grid_penalty"]

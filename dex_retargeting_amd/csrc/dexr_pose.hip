@@ -2045,3 +2045,6 @@ int dexr_link_ik_solve(const dexr_pose_model* m, int64_t B, const double* x0, co
 
 // ---- include/dexr_resolve_obstacles.h: the posture solve with the obstacle term, both kernels' phases in one resident loop -----
 #include "dexr_resolve_obstacles.hpp"
+
+// ---- include/dexr_sdf_grid.h: the robot's spheres against a sampled signed-distance field, the obstacle kernel with another phase B
+#include "dexr_sdf_grid.hpp"
