@@ -89,6 +89,8 @@ SDF_GRID_EXPORTS = ["dexr_sdf_grid_create", "dexr_sdf_grid_destroy", "dexr_sdf_g
                     "dexr_grid_distances_vjp_dev", "dexr_grid_penalty_dev", "dexr_grid_distances", "dexr_grid_distances_vjp",
                     "dexr_grid_penalty"]
 SDF_GRID_MIN_DIM, SDF_GRID_MAX_DIM, SDF_GRID_MAX_SAMPLES = 2, 1024, 1 << 24  # DEXR_SDF_GRID_*
+# include/dexr_resolve_grid.h (the posture solve with the grid term, iterated inside one kernel): a list of its own
+RESOLVE_GRID_EXPORTS = ["dexr_sphere_resolve_grid_dev", "dexr_sphere_resolve_grid"]
 UNIQUE_ID_BYTES = 128
 
 
@@ -216,6 +218,11 @@ def load() -> C.CDLL:
     lib.dexr_grid_distances.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, f64p]
     lib.dexr_grid_distances_vjp.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, f64p, f64p]
     lib.dexr_grid_penalty.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, C.c_double, f64p, f64p, f64p]
+    lib.dexr_sphere_resolve_grid_dev.argtypes = [vp, i64, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, C.c_float,
+                                                 C.c_float, C.c_float, C.c_int32, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]
+    lib.dexr_sphere_resolve_grid.argtypes = [vp, i64, f64p, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, C.c_double, f64p,
+                                             f64p, f64p, C.c_double, C.c_double, C.c_double, C.c_int32, vp, f64p, f64p, C.c_double, C.c_double,
+                                             f64p, i32p, f64p, i32p]
     _lib = lib
     return lib
 
@@ -1007,6 +1014,62 @@ class SphereModel:
         d = lambda a: _ptr(a, C.c_double)  # noqa: E731
         check(load().dexr_grid_penalty(self._h, grid.handle, B, d(x), d(fixed), d(pos), d(rot), float(margin), d(e), d(gx), d(wr)))
         return e, gx, wr
+
+    # the posture solve with the grid term (include/dexr_resolve_grid.h) -----------------------------------------
+    def resolve_grid_dev(self, grid: "SdfGrid", B: int, x0_ptr: int, fixed_ptr: int, margin: float, damping: float, max_iters: int,
+                         x_ptr: int, iters_ptr: int = 0, energy_ptr: int = 0, status_ptr: int = 0, x_ref_ptr: int = 0,
+                         posture_weight_ptr: int = 0, n_target: int = 0, target_pos_ptr: int = 0, target_rot_ptr: int = 0,
+                         pos_weight_ptr: int = 0, rot_weight_ptr: int = 0, collision_weight: float = 1.0, pair_weight_ptr: int = 0,
+                         lo_ptr: int = 0, hi_ptr: int = 0, tol: float = 0.0, max_step: float = 0.0, obstacle_pos_ptr: int = 0,
+                         obstacle_rot_ptr: int = 0, obstacle_margin=None, obstacle_weight: float = 1.0, stream: int = 0):
+        """the arguments of resolve_dev, and obstacle_pos (B, 3) or 0, obstacle_rot (B, 3, 3) or 0, obstacle_margin (None: margin),
+        obstacle_weight -> x (B, n_in), iters (B) int32, energy (B, 4), status (B) int32, each of the last three or 0
+        (dexr_sphere_resolve_grid_dev)."""
+        om = margin if obstacle_margin is None else obstacle_margin
+        check(load().dexr_sphere_resolve_grid_dev(
+            self._h, B, x0_ptr or None, fixed_ptr or None, x_ref_ptr or None, posture_weight_ptr or None, int(n_target), target_pos_ptr or None,
+            target_rot_ptr or None, pos_weight_ptr or None, rot_weight_ptr or None, float(margin), float(collision_weight), pair_weight_ptr or None,
+            lo_ptr or None, hi_ptr or None, float(damping), float(max_step), float(tol), int(max_iters), grid.handle, obstacle_pos_ptr or None,
+            obstacle_rot_ptr or None, float(om), float(obstacle_weight), x_ptr or None, iters_ptr or None, energy_ptr or None,
+            status_ptr or None, stream or None))
+
+    def resolve_grid(self, grid: "SdfGrid", x0, margin=None, damping=None, max_iters=None, fixed=None, x_ref=None, posture_weight=None,
+                     target_pos=None, target_rot=None, pos_weight=None, rot_weight=None, collision_weight: float = 1.0, pair_weight=None,
+                     lo=None, hi=None, tol: float = 0.0, max_step: float = 0.0, n_target=None, obstacle_pos=None, obstacle_rot=None,
+                     obstacle_margin=None, obstacle_weight: float = 1.0):
+        """-> (x (B, n_in) float64, iters (B) int32, energy (B, 4) float64, status (B) int32) (dexr_sphere_resolve_grid): the
+        arguments of `resolve`, and the obstacle pose per frame or None, obstacle_margin (None: margin) and obstacle_weight."""
+        for name, v in (("margin", margin), ("damping", damping), ("max_iters", max_iters)):
+            if v is None:
+                raise ValueError(f"{name} is required")
+        x0, fixed, B = self._host_inputs(x0, fixed)
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi = (
+            f64(a) for a in (x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi))
+        pos, rot = self._host_pose(B, obstacle_pos, obstacle_rot)
+        if n_target is None:
+            n_target = 0 if target_pos is None and target_rot is None else (target_pos if target_pos is not None else target_rot).shape[1]
+        n_target = int(n_target)
+        shapes = (("x_ref", x_ref, (B, self.n_in)), ("posture_weight", posture_weight, (self.n_in,)), ("target_pos", target_pos, (B, n_target, 3)),
+                  ("target_rot", target_rot, (B, n_target, 3, 3)), ("pos_weight", pos_weight, (B, n_target)),
+                  ("rot_weight", rot_weight, (B, n_target)), ("pair_weight", pair_weight, (self.n_pair,)), ("lo", lo, (self.n_in,)),
+                  ("hi", hi, (self.n_in,)))
+        for name, a, want in shapes:
+            if a is not None and a.shape != want:
+                raise ValueError(f"{name} must have shape {want}, got {a.shape}")
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi must both be given or both be None")
+        x = np.zeros((B, self.n_in), dtype=np.float64)
+        iters = np.zeros(B, dtype=np.int32)
+        energy = np.zeros((B, 4), dtype=np.float64)
+        status = np.zeros(B, dtype=np.int32)
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        om = margin if obstacle_margin is None else obstacle_margin
+        check(load().dexr_sphere_resolve_grid(
+            self._h, B, d(x0), d(fixed), d(x_ref), d(posture_weight), n_target, d(target_pos), d(target_rot), d(pos_weight), d(rot_weight),
+            float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi), float(damping), float(max_step), float(tol), int(max_iters),
+            grid.handle, d(pos), d(rot), float(om), float(obstacle_weight), d(x), _ptr(iters, C.c_int32), d(energy), _ptr(status, C.c_int32)))
+        return x, iters, energy, status
 
 
 class ObstacleSet:

@@ -26,7 +26,8 @@ An ``SdfGrid`` is an obstacle that no handful of primitives describes -- a mesh,
 its signed-distance field on a regular grid of the obstacle frame (include/dexr_sdf_grid.h, csrc/dexr_sdf_grid.hpp), posed like
 an ``ObstacleSet``.  ``grid_distances`` and ``grid_penalty`` are ``obstacle_distances`` and ``obstacle_penalty`` against it: one
 trilinear lookup per sphere however complex the shape is, the distance continued outside the grid's box by the distance to the
-box.  ``SdfGrid.from_obstacles`` samples an ``ObstacleSet``.
+box.  ``SdfGrid.from_obstacles`` samples an ``ObstacleSet``.  ``resolve_grid_collisions`` is ``resolve_collisions`` against a grid
+(include/dexr_resolve_grid.h): a sphere has one contact at most, so nothing is capped.
 
 The outputs of this module carry NO autograd graph; ``autograd.sphere_distances``, ``autograd.self_collision_penalty``,
 ``autograd.obstacle_distances``, ``autograd.obstacle_penalty``, ``autograd.grid_distances`` and ``autograd.grid_penalty`` are the
@@ -900,7 +901,92 @@ def robot_resolve_collisions(robot, qpos0, sphere_set: SphereSet, obstacles: Obs
                               limits)
 
 
+# ---- the posture solve with the grid term (include/dexr_resolve_grid.h) -----------------------------------------------------------------
+def _resolve_grid(model_of, n_in, n_fixed, kin, robot, x0, what, fixed_qpos, sphere_set, grid, margin, obstacle_margin, obstacle_pos, obstacle_rot,
+                  obstacle_weight, damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight, link_names, target_pos, target_rot,
+                  pos_weight, rot_weight, tol, max_step, limits):
+    """every rule (those of `_resolve`, then the grid side's), then one model and one launch."""
+    import torch
+
+    named = _resolve_rules(n_in, x0, sphere_set, damping, max_iters, posture_weight, q_ref, collision_weight, link_names, target_pos,
+                           target_rot, pos_weight, rot_weight, tol, max_step, limits)
+    for n in link_names or ():
+        kin.body_frame_index(n)  # ValueError on an unknown link
+    if isinstance(obstacle_weight, bool) or not isinstance(obstacle_weight, (int, float)) or not math.isfinite(obstacle_weight) or obstacle_weight < 0:
+        raise ValueError(f"obstacle_weight must be a finite Python float >= 0, got {obstacle_weight!r}")
+    if obstacle_margin is not None and (isinstance(obstacle_margin, bool) or not isinstance(obstacle_margin, (int, float))
+                                        or not math.isfinite(obstacle_margin) or obstacle_margin < 0):
+        raise ValueError(f"obstacle_margin must be a finite Python float >= 0 or None (margin), got {obstacle_margin!r}")
+    pairs = _check(n_in, n_fixed, kin, robot, x0, fixed_qpos, sphere_set, what, margin, pair_weight, penalty=True, poses=False)
+    _check_obstacles(n_in, n_fixed, kin, robot, x0, fixed_qpos, sphere_set, grid, obstacle_pos, obstacle_rot, what, margin, penalty=True,
+                     grid=True)  # (ends with the device)
+    if pair_weight is not None:
+        named = named + [("pair_weight", pair_weight)]
+    for name, t in named:
+        if t.device != x0.device:
+            raise ValueError(f"{name} is on {t.device}, {what} on {x0.device}: all tensors must be on one CUDA device")
+    B = x0.shape[0]
+    xc, fixed = _inputs(x0, fixed_qpos)
+    c = lambda a: None if a is None else a.detach().contiguous()  # noqa: E731
+    xr, tp, tr, wl, wa, pw = (c(a) for a in (q_ref, target_pos, target_rot, pos_weight, rot_weight, pair_weight))
+    pos, rot = _obstacle_pose(obstacle_pos, obstacle_rot)
+    lo, hi = (None, None) if limits is None else (limits.detach()[:, 0].contiguous(), limits.detach()[:, 1].contiguous())
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    with torch.cuda.device(x0.device):
+        if isinstance(posture_weight, torch.Tensor):
+            u = c(posture_weight)
+        else:
+            u = None if not posture_weight else torch.full((n_in,), float(posture_weight), dtype=torch.float32, device=x0.device)
+        model = model_of(sphere_set, pairs, tuple(link_names or ()))
+        q = torch.empty((B, model.n_in), dtype=torch.float32, device=x0.device)
+        iters = torch.empty((B,), dtype=torch.int32, device=x0.device)
+        energy = torch.empty((B, 4), dtype=torch.float32, device=x0.device)
+        status = torch.empty((B,), dtype=torch.int32, device=x0.device)
+        if B > 0:
+            model.resolve_grid_dev(grid.device_grid(torch.cuda.current_device()), B, xc.data_ptr(), ptr(fixed), float(margin), float(damping),
+                                   int(max_iters), q.data_ptr(), iters.data_ptr(), energy.data_ptr(), status.data_ptr(), x_ref_ptr=ptr(xr),
+                                   posture_weight_ptr=ptr(u), n_target=len(link_names or ()), target_pos_ptr=ptr(tp), target_rot_ptr=ptr(tr),
+                                   pos_weight_ptr=ptr(wl), rot_weight_ptr=ptr(wa), collision_weight=float(collision_weight),
+                                   pair_weight_ptr=ptr(pw), lo_ptr=ptr(lo), hi_ptr=ptr(hi), tol=float(tol), max_step=float(max_step),
+                                   obstacle_pos_ptr=ptr(pos), obstacle_rot_ptr=ptr(rot),
+                                   obstacle_margin=float(margin if obstacle_margin is None else obstacle_margin),
+                                   obstacle_weight=float(obstacle_weight), stream=torch.cuda.current_stream(x0.device).cuda_stream)
+    return q, iters, energy, status
+
+
+def resolve_grid_collisions(optimizer, q0, sphere_set: SphereSet, grid: SdfGrid, margin, obstacle_margin=None, obstacle_pos=None,
+                            obstacle_rot=None, obstacle_weight=1.0, damping=_REQUIRED, max_iters=_REQUIRED, posture_weight=None, q_ref=None,
+                            collision_weight=1.0, pair_weight=None, link_names=None, target_pos=None, target_rot=None, pos_weight=None,
+                            rot_weight=None, tol=0.0, max_step=0.0, limits=None, fixed_qpos=None):
+    """`resolve_collisions` against an `SdfGrid` instead of primitives: project postures out of self-penetration AND out of the
+    field of `grid` -- a held object with a pose per frame, or a shared scene, given as a mesh, a scan or a depth fusion -- inside
+    ONE launch, on
+
+        E = E of resolve_self_collision + obstacle_weight * sum_s max(0, obstacle_margin - d_s)^2
+
+    with d_s of `grid_penalty`.  obstacle_margin: a finite Python float >= 0, None: `margin`; obstacle_pos (B, 3), obstacle_rot
+    (B, 3, 3) float32 or None as in `grid_distances`, fixed during the solve.  Every other argument, the accept / reject rule and
+    the damping are those of `resolve_self_collision`.  -> (q (B, n_opt) float32, iters (B) int32, energy (B, 4) float32: pose,
+    posture, self-collision and grid term at q, status (B) int32).  A sphere has at most one contact with a grid: every contact
+    enters the curvature and _lib.RESOLVE_CONTACTS_TRUNCATED is never set.  No autograd graph."""
+    return _resolve_grid(optimizer.sphere_model, optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q0, "q",
+                         fixed_qpos, sphere_set, grid, margin, obstacle_margin, obstacle_pos, obstacle_rot, obstacle_weight, damping, max_iters,
+                         posture_weight, q_ref, collision_weight, pair_weight, link_names, target_pos, target_rot, pos_weight, rot_weight, tol,
+                         max_step, limits)
+
+
+def robot_resolve_grid_collisions(robot, qpos0, sphere_set: SphereSet, grid: SdfGrid, margin, obstacle_margin=None, obstacle_pos=None,
+                                  obstacle_rot=None, obstacle_weight=1.0, damping=_REQUIRED, max_iters=_REQUIRED, posture_weight=None,
+                                  q_ref=None, collision_weight=1.0, pair_weight=None, link_names=None, target_pos=None, target_rot=None,
+                                  pos_weight=None, rot_weight=None, tol=0.0, max_step=0.0, limits=None):
+    """The same for a full robot qpos (B, robot.dof) in dof order; every joint is a column of its own, limits (robot.dof, 2)."""
+    return _resolve_grid(robot.sphere_model, robot.dof, 0, robot.kin, robot, qpos0, "qpos", None, sphere_set, grid, margin, obstacle_margin,
+                         obstacle_pos, obstacle_rot, obstacle_weight, damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight,
+                         link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits)
+
+
 __all__ = ["SphereSet", "default_pairs", "sphere_distances", "self_collision_penalty", "robot_sphere_distances",
            "robot_self_collision_penalty", "resolve_self_collision", "robot_resolve_self_collision", "ObstacleSet", "obstacle_distances",
            "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty", "resolve_collisions", "robot_resolve_collisions", "SdfGrid",
-           "grid_distances", "grid_penalty", "robot_grid_distances", "robot_grid_penalty"]
+           "grid_distances", "grid_penalty", "robot_grid_distances", "robot_grid_penalty", "resolve_grid_collisions",
+           "robot_resolve_grid_collisions"]

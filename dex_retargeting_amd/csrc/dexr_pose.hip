@@ -2048,3 +2048,6 @@ int dexr_link_ik_solve(const dexr_pose_model* m, int64_t B, const double* x0, co
 
 // ---- include/dexr_sdf_grid.h: the robot's spheres against a sampled signed-distance field, the obstacle kernel with another phase B
 #include "dexr_sdf_grid.hpp"
+
+// ---- include/dexr_resolve_grid.h: the posture solve against a signed-distance field, the cell lookup inside the resident loop --
+#include "dexr_resolve_grid.hpp"

@@ -1,5 +1,5 @@
 // dexr_sdf_grid.hpp -- the robot's spheres against one sampled signed-distance field (include/dexr_sdf_grid.h): a fragment of
-// dexr_pose.hip, which includes it once at its end, after dexr_resolve_obstacles.hpp.  It is pose_obstacle_kernel
+// dexr_pose.hip, which includes it once after dexr_resolve_obstacles.hpp.  It is pose_obstacle_kernel
 // (dexr_obstacles.hpp) with another phase B: the same three-phase block, per-frame LDS layout and frames per block.  What that
 // family has as functions is used as it is -- joint_step, link_pose, sphere_centre, resolve_force_entry, cross_fma, obstacle_point
 // and obstacle_to_world of dexr_resolve_obstacles.hpp, ObstacleArgs, check_call, check_margin, DevBuf / POSE_HIP.  Phases A and C
