@@ -91,6 +91,11 @@ SDF_GRID_EXPORTS = ["dexr_sdf_grid_create", "dexr_sdf_grid_destroy", "dexr_sdf_g
 SDF_GRID_MIN_DIM, SDF_GRID_MAX_DIM, SDF_GRID_MAX_SAMPLES = 2, 1024, 1 << 24  # DEXR_SDF_GRID_*
 # include/dexr_resolve_grid.h (the posture solve with the grid term, iterated inside one kernel): a list of its own
 RESOLVE_GRID_EXPORTS = ["dexr_sphere_resolve_grid_dev", "dexr_sphere_resolve_grid"]
+# include/dexr_mesh_sdf.h (signed distances of points and of grid samples to a triangle mesh, brute force): a list of its own
+MESH_SDF_EXPORTS = ["dexr_mesh_create", "dexr_mesh_destroy", "dexr_mesh_info", "dexr_mesh_distances_dev", "dexr_mesh_distances",
+                    "dexr_mesh_sample_grid_dev", "dexr_mesh_sample_grid"]
+MESH_MAX_VERTICES, MESH_MAX_TRIANGLES = 1 << 20, 1 << 20  # DEXR_MESH_MAX_*
+MESH_TILE, MESH_BLOCK_POINTS, MESH_PAIRS_PER_LAUNCH = 256, 512, 1 << 34  # DEXR_MESH_TILE, DEXR_MESH_BLOCK_POINTS, DEXR_MESH_PAIRS_PER_LAUNCH
 UNIQUE_ID_BYTES = 128
 
 
@@ -223,6 +228,14 @@ def load() -> C.CDLL:
     lib.dexr_sphere_resolve_grid.argtypes = [vp, i64, f64p, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, C.c_double, f64p,
                                              f64p, f64p, C.c_double, C.c_double, C.c_double, C.c_int32, vp, f64p, f64p, C.c_double, C.c_double,
                                              f64p, i32p, f64p, i32p]
+    lib.dexr_mesh_create.argtypes = [C.c_int32, f64p, C.c_int32, i32p, C.POINTER(vp)]
+    lib.dexr_mesh_destroy.argtypes = [vp]
+    lib.dexr_mesh_destroy.restype = None
+    lib.dexr_mesh_info.argtypes = [vp, i32p, i32p, f64p]
+    lib.dexr_mesh_distances_dev.argtypes = [vp, i64, vp, vp, vp, vp]
+    lib.dexr_mesh_distances.argtypes = [vp, i64, f64p, f64p, f64p]
+    lib.dexr_mesh_sample_grid_dev.argtypes = [vp, i32p, f64p, f64p, vp, vp]
+    lib.dexr_mesh_sample_grid.argtypes = [vp, i32p, f64p, f64p, f32p]
     _lib = lib
     return lib
 
@@ -1128,6 +1141,80 @@ class SdfGrid:
     @property
     def handle(self) -> C.c_void_p:
         return self._h
+
+
+def mesh_points_per_launch(n_triangle: int) -> int:
+    """points of one launch of the mesh kernels against a mesh of n_triangle triangles (include/dexr_mesh_sdf.h, BOUNDED LAUNCHES)"""
+    return max(1, (MESH_PAIRS_PER_LAUNCH // n_triangle) // MESH_BLOCK_POINTS) * MESH_BLOCK_POINTS
+
+
+class TriangleMesh:
+    """Owns one dexr_mesh (include/dexr_mesh_sdf.h): vertices (V, 3) float64 and faces (T, 3) int32, the per-triangle records
+    resident in HBM in float32 and float64.  Signed distances (the sign from the generalised winding number) of points or of the
+    samples of a regular grid, brute force: points x T pairs."""
+
+    def __init__(self, vertices, faces):
+        lib = load()
+        self._h = C.c_void_p()
+        vertices = np.ascontiguousarray(vertices, dtype=np.float64)
+        faces = np.ascontiguousarray(faces, dtype=np.int32)
+        if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+            raise ValueError(f"vertices must have shape (V, 3) and faces (T, 3), got {vertices.shape}, {faces.shape}")
+        check(lib.dexr_mesh_create(len(vertices), _ptr(vertices, C.c_double), len(faces), _ptr(faces, C.c_int32), C.byref(self._h)))
+        nv, nt = C.c_int32(), C.c_int32()
+        bounds = np.zeros(6, dtype=np.float64)
+        check(lib.dexr_mesh_info(self._h, C.byref(nv), C.byref(nt), _ptr(bounds, C.c_double)))
+        self.n_vertex, self.n_triangle, self.bounds = int(nv.value), int(nt.value), bounds.reshape(2, 3)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib is not None:
+            _lib.dexr_mesh_destroy(h)
+            self._h = None
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    @staticmethod
+    def _grid_args(n, origin, spacing):
+        n = np.ascontiguousarray(n, dtype=np.int32).reshape(-1)
+        origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
+        spacing = np.ascontiguousarray(spacing, dtype=np.float64).reshape(-1)
+        if n.shape != (3,) or origin.shape != (3,) or spacing.shape != (3,):
+            raise ValueError(f"n, origin and spacing must each have shape (3,), got {n.shape}, {origin.shape}, {spacing.shape}")
+        return n, origin, spacing
+
+    def distances_dev(self, P: int, points_ptr: int, dist_ptr: int, winding_ptr: int = 0, stream: int = 0):
+        """device pointers, float32: points (P, 3) -> dist (P), winding (P) or 0.  Never synchronises, never allocates."""
+        check(load().dexr_mesh_distances_dev(self._h, P, points_ptr or None, dist_ptr or None, winding_ptr or None, stream or None))
+
+    def distances(self, points, winding: bool = False):
+        """points (P, 3) float64 on the host -> dist (P) float64 [, winding (P) float64], float64 arithmetic on the device."""
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError(f"points must have shape (P, 3), got {points.shape}")
+        P = points.shape[0]
+        dist = np.zeros(P, dtype=np.float64)
+        wind = np.zeros(P, dtype=np.float64) if winding else None
+        check(load().dexr_mesh_distances(self._h, P, _ptr(points, C.c_double), _ptr(dist, C.c_double), _ptr(wind, C.c_double)))
+        return (dist, wind) if winding else dist
+
+    def sample_grid_dev(self, n, origin, spacing, values_ptr: int, stream: int = 0):
+        """values (n[0], n[1], n[2]) float32 on the device, float32 arithmetic.  Never synchronises, never allocates."""
+        n, origin, spacing = self._grid_args(n, origin, spacing)
+        check(load().dexr_mesh_sample_grid_dev(self._h, _ptr(n, C.c_int32), _ptr(origin, C.c_double), _ptr(spacing, C.c_double),
+                                               values_ptr or None, stream or None))
+
+    def sample_grid(self, n, origin, spacing):
+        """-> values (n[0], n[1], n[2]) float32 on the host: float64 arithmetic on the device, rounded to float32 at the store."""
+        n, origin, spacing = self._grid_args(n, origin, spacing)
+        lo, hi = SDF_GRID_MIN_DIM, SDF_GRID_MAX_DIM
+        ok = n.min() >= lo and n.max() <= hi and int(n[0]) * int(n[1]) * int(n[2]) <= SDF_GRID_MAX_SAMPLES
+        values = np.zeros(tuple(int(k) for k in n) if ok else (1,), dtype=np.float32)  # (a refused shape: the library says why)
+        check(load().dexr_mesh_sample_grid(self._h, _ptr(n, C.c_int32), _ptr(origin, C.c_double), _ptr(spacing, C.c_double),
+                                           _ptr(values, C.c_float)))
+        return values
 
 
 def seq_compose_dev(B: int, T: int, dof_kind, dof_idx, dof_mult, dof_off, n_opt: int, n_fixed: int, qraw_ptr: int,

@@ -654,6 +654,126 @@ def _primitive_sdf(kind, v, y):
     return np.linalg.norm(y - v[:3], axis=-1) - v[3]
 
 
+class TriangleMesh:
+    """A triangle mesh of an obstacle frame: plain data, immutable, hashable by content.
+
+    vertices  (V, 3) float64, finite, 1 .. 2^20 of them
+    faces     (T, 3) int32 vertex indices, 1 .. 2^20 of them; a triangle whose cross product (b - a) x (c - a) is exactly zero in
+              float64 is refused, or with `drop_degenerate=True` removed first
+
+    The rules are those of dexr_mesh_create (include/dexr_mesh_sdf.h); a broken one is a ValueError.  The sign of a distance comes
+    from the generalised winding number: it is right for a closed mesh whose normals (b - a) x (c - a) point outwards
+    (`is_closed` and `volume > 0`), and a majority vote on an open one.  `SdfGrid.from_mesh` samples the mesh into a grid,
+    `mesh_distances` gives the distances of arbitrary points.  The device tables of a mesh are made at its first use and kept with
+    it (`device_mesh`)."""
+
+    def __init__(self, vertices, faces, drop_degenerate: bool = False):
+        v = np.array(vertices, dtype=np.float64)
+        f = np.array(faces)
+        if v.ndim != 2 or v.shape[1] != 3:
+            raise ValueError(f"vertices must have shape (V, 3), got {v.shape}")
+        if f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+            raise ValueError(f"faces must be integers of shape (T, 3), got {f.dtype} {f.shape}")
+        f = f.astype(np.int64)
+        if not 1 <= len(v) <= _lib.MESH_MAX_VERTICES:
+            raise ValueError(f"a mesh holds 1..{_lib.MESH_MAX_VERTICES} vertices, got {len(v)}")
+        if len(f) and (f.min() < 0 or f.max() >= len(v)):
+            raise ValueError(f"a face index is outside 0..{len(v) - 1}")
+        if not np.isfinite(v).all():
+            raise ValueError("the vertices must be finite")
+        if len(f):
+            a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+            with np.errstate(over="ignore", invalid="ignore"):
+                flat = (np.cross(b - a, c - a) == 0.0).all(1)
+            if flat.any():
+                if not drop_degenerate:
+                    raise ValueError(f"triangle {int(np.flatnonzero(flat)[0])} has no area ({int(flat.sum())} such): drop_degenerate=True removes them")
+                f = f[~flat]
+        if not 1 <= len(f) <= _lib.MESH_MAX_TRIANGLES:
+            raise ValueError(f"a mesh holds 1..{_lib.MESH_MAX_TRIANGLES} triangles, got {len(f)}")
+        f = np.ascontiguousarray(f.astype(np.int32))
+        for a in (v, f):
+            a.setflags(write=False)
+        self.vertices, self.faces = v, f
+        self._key = (v.shape, f.shape, v.tobytes(), f.tobytes())
+        self._hash = hash(self._key)
+        self._device_meshes = {}
+
+    @property
+    def n_vertex(self) -> int:
+        return len(self.vertices)
+
+    @property
+    def n_triangle(self) -> int:
+        return len(self.faces)
+
+    @property
+    def bounds(self) -> np.ndarray:
+        """(2, 3): the smallest and the largest coordinate of all vertices per axis."""
+        return np.stack([self.vertices.min(0), self.vertices.max(0)])
+
+    @property
+    def is_closed(self) -> bool:
+        """every undirected edge belongs to exactly two triangles, which traverse it in opposite directions."""
+        f = self.faces.astype(np.int64)
+        e = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+        V = self.n_vertex
+        directed = e[:, 0] * V + e[:, 1]
+        if len(np.unique(directed)) != len(directed):  # a directed edge twice: two triangles run along it the same way
+            return False
+        lo, hi = e.min(1), e.max(1)
+        _, counts = np.unique(lo * V + hi, return_counts=True)
+        return bool((counts == 2).all())
+
+    @property
+    def volume(self) -> float:
+        """the signed sum of a . (b x c) / 6: the enclosed volume of a closed mesh with outward normals, negative inside out."""
+        a, b, c = (self.vertices[self.faces[:, k]] for k in range(3))
+        return float(np.einsum("ij,ij->i", a, np.cross(b, c)).sum() / 6.0)
+
+    def device_mesh(self, device_index: int = 0) -> _lib.TriangleMesh:
+        """the mesh's records on a device (made with that device current), cached with the mesh."""
+        if device_index not in self._device_meshes:
+            self._device_meshes[device_index] = _lib.TriangleMesh(self.vertices, self.faces)
+        return self._device_meshes[device_index]
+
+    def __hash__(self):
+        return self._hash
+
+    def __eq__(self, other):
+        return isinstance(other, TriangleMesh) and self._key == other._key
+
+    def __repr__(self):
+        return f"TriangleMesh({self.n_vertex} vertices, {self.n_triangle} triangles)"
+
+
+def mesh_distances(mesh: TriangleMesh, points, winding: bool = False):
+    """Signed distances of points to a mesh: points (..., 3) float32 CUDA -> dist of shape points.shape[:-1], float32, negative
+    inside; with `winding=True` -> (dist, w), w the generalised winding number behind the sign (include/dexr_mesh_sdf.h).  Brute
+    force on the current stream, points x triangles pairs.  No autograd graph."""
+    import torch
+
+    if not isinstance(mesh, TriangleMesh):
+        raise ValueError("mesh must be a collision.TriangleMesh")
+    if not isinstance(points, torch.Tensor):
+        raise ValueError("points must be a torch tensor")
+    if points.dtype != torch.float32:
+        raise ValueError(f"points must be float32, got {points.dtype}")
+    if points.ndim < 1 or points.shape[-1] != 3:
+        raise ValueError(f"points must have shape (..., 3), got {tuple(points.shape)}")
+    if not points.is_cuda:
+        raise ValueError("points must be a CUDA tensor")
+    pc = points.detach().contiguous()
+    P = pc.numel() // 3
+    with torch.cuda.device(points.device):
+        dist = torch.empty(points.shape[:-1], dtype=torch.float32, device=points.device)
+        w = torch.empty(points.shape[:-1], dtype=torch.float32, device=points.device) if winding else None
+        if P > 0:
+            mesh.device_mesh(torch.cuda.current_device()).distances_dev(P, pc.data_ptr(), dist.data_ptr(), 0 if w is None else w.data_ptr(),
+                                                                        stream=torch.cuda.current_stream(points.device).cuda_stream)
+    return (dist, w) if winding else dist
+
+
 class SdfGrid:
     """A signed-distance field sampled on a regular grid of an obstacle frame: plain data, immutable, hashable by content.
 
@@ -722,6 +842,72 @@ class SdfGrid:
             for kind, v in zip(obstacle_set.kinds, obstacle_set.params):
                 d = np.minimum(d, _primitive_sdf(kind, v, y))
             values[ix] = d
+        return cls(values, o, h)
+
+    @classmethod
+    def from_mesh(cls, mesh: TriangleMesh, origin=None, spacing=_REQUIRED, shape=None, padding=0.0, precision="float64",
+                  allow_open: bool = False):
+        """the signed distance to a TriangleMesh (include/dexr_mesh_sdf.h) sampled on the device, brute force: every sample against
+        every triangle.  `spacing` is required (a scalar or (3,)).  With `origin` and `shape` both None the box is fitted to the mesh:
+        origin = lo - padding and shape = ceil((hi - lo + 2 padding) / spacing) + 1 per axis, lo and hi the mesh's bounds; otherwise
+        both are given, as in `from_obstacles`.  precision "float64": float64 arithmetic rounded to float32 at the store, the contract
+        of `from_obstacles`; "float32": float32 arithmetic through a torch buffer on the current CUDA device.  The sign is right
+        only for a closed mesh with outward normals: a mesh with `is_closed == False` or `volume <= 0` is a ValueError unless
+        `allow_open=True` (an inside-out mesh would give a field that is positive everywhere)."""
+        if not isinstance(mesh, TriangleMesh):
+            raise ValueError("mesh must be a collision.TriangleMesh")
+        if spacing is _REQUIRED:
+            raise ValueError("spacing is required")
+        if precision not in ("float64", "float32"):
+            raise ValueError(f"precision must be 'float64' or 'float32', got {precision!r}")
+        if (origin is None) != (shape is None):
+            raise ValueError("origin and shape must both be given or both be None (None: the box is fitted to the mesh)")
+        try:
+            h = np.array(np.broadcast_to(np.asarray(spacing, dtype=np.float64), (3,)))
+            pad = float(padding)
+        except (ValueError, TypeError):
+            raise ValueError("spacing must be a scalar or have shape (3,), padding a number") from None
+        with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+            inv_ok = np.isfinite(1.0 / h).all()
+        if not (np.isfinite(h).all() and (h > 0).all() and inv_ok):
+            raise ValueError(f"spacing must be finite and > 0, got {h.tolist()}")
+        if not (math.isfinite(pad) and pad >= 0):
+            raise ValueError(f"padding must be finite and >= 0, got {padding}")
+        if origin is None:
+            lo, hi = mesh.bounds
+            o = lo - pad
+            cells = np.ceil((hi - lo + 2 * pad) / h)
+            if not (np.isfinite(cells).all() and (cells < 2 ** 31).all()):
+                raise ValueError(f"the fitted box needs {cells.tolist()} cells per axis")
+            n = tuple(int(k) + 1 for k in cells)
+        else:
+            try:
+                n = tuple(int(k) for k in np.broadcast_to(np.asarray(shape), (3,)))
+                o = np.array(np.broadcast_to(np.asarray(origin, dtype=np.float64), (3,)))
+            except (ValueError, TypeError):
+                raise ValueError("shape and origin must each be a scalar or have shape (3,)") from None
+        if min(n) < _lib.SDF_GRID_MIN_DIM or max(n) > _lib.SDF_GRID_MAX_DIM or n[0] * n[1] * n[2] > _lib.SDF_GRID_MAX_SAMPLES:
+            raise ValueError(f"every dimension of a grid is {_lib.SDF_GRID_MIN_DIM}..{_lib.SDF_GRID_MAX_DIM} samples and there are at most "
+                             f"{_lib.SDF_GRID_MAX_SAMPLES}, got {n}")
+        if not np.isfinite(o).all():
+            raise ValueError(f"origin must be finite, got {o.tolist()}")
+        if not allow_open:
+            if not mesh.is_closed:
+                raise ValueError("the mesh is not closed (an edge that does not belong to exactly two triangles of opposite direction): its "
+                                 "winding number is fractional and the sign only a majority vote; allow_open=True accepts that")
+            if not mesh.volume > 0:
+                raise ValueError(f"the mesh has volume {mesh.volume:g} <= 0: its triangles are oriented inside out and every sample would be "
+                                 "positive; flip the faces, or allow_open=True accepts that")
+        if precision == "float64":
+            values = mesh.device_mesh().sample_grid(n, o, h)
+        else:
+            import torch
+
+            with torch.cuda.device(torch.cuda.current_device()):
+                buf = torch.empty(n, dtype=torch.float32, device="cuda")
+                mesh.device_mesh(torch.cuda.current_device()).sample_grid_dev(n, o, h, buf.data_ptr(),
+                                                                              stream=torch.cuda.current_stream().cuda_stream)
+                values = buf.cpu().numpy()
         return cls(values, o, h)
 
     @property
@@ -989,4 +1175,4 @@ __all__ = ["SphereSet", "default_pairs", "sphere_distances", "self_collision_pen
            "robot_self_collision_penalty", "resolve_self_collision", "robot_resolve_self_collision", "ObstacleSet", "obstacle_distances",
            "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty", "resolve_collisions", "robot_resolve_collisions", "SdfGrid",
            "grid_distances", "grid_penalty", "robot_grid_distances", "robot_grid_penalty", "resolve_grid_collisions",
-           "robot_resolve_grid_collisions"]
+           "robot_resolve_grid_collisions", "TriangleMesh", "mesh_distances"]
