@@ -810,6 +810,25 @@ class SphereModel:
         """-> (x (B, n_in) float64, iters (B) int32, energy (B, 3) float64, status (B) int32) (dexr_sphere_resolve).  The
         targets are the first n_target links of the table; n_target is read from the shape of target_pos / target_rot
         ((B, n_target, 3) / (B, n_target, 3, 3)) unless given.  margin, damping > 0 and max_iters in 1..256 are required."""
+        (x0, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi), n_target, B, out = \
+            self._resolve_host(x0, margin, damping, max_iters, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight,
+                               pair_weight, lo, hi, n_target, 3)
+        x, iters, energy, status = out
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        check(load().dexr_sphere_resolve(self._h, B, d(x0), d(fixed), d(x_ref), d(posture_weight), n_target, d(target_pos), d(target_rot),
+                                         d(pos_weight), d(rot_weight), float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi),
+                                         float(damping), float(max_step), float(tol), int(max_iters), d(x), _ptr(iters, C.c_int32),
+                                         d(energy), _ptr(status, C.c_int32)))
+        return out
+
+    def _resolve_host(self, x0, margin, damping, max_iters, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight,
+                      pair_weight, lo, hi, n_target, energy_cols, pose=None, extra=()):
+        """What the three host resolve methods share, in the order their rules fire: the required scalars, x0 and fixed, every array
+        as contiguous float64 (extra: (name, array, a callable that gives its shape, asked when the table is built) of the caller's own, last in the shape
+        table), the obstacle pose where
+        pose = (obstacle_pos, obstacle_rot) is given, n_target from the shape of the targets unless given, the shape table, the
+        lo / hi rule and the four outputs.  -> ((x0, fixed, the nine arrays in argument order[, pos, rot], the extra arrays),
+        n_target, B, (x, iters, energy (B, energy_cols), status))."""
         for name, v in (("margin", margin), ("damping", damping), ("max_iters", max_iters)):
             if v is None:
                 raise ValueError(f"{name} is required")
@@ -817,28 +836,25 @@ class SphereModel:
         f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
         x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi = (
             f64(a) for a in (x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi))
+        extra = [(name, f64(a), want) for name, a, want in extra]
+        posed = () if pose is None else self._host_pose(B, *pose)
         if n_target is None:
             n_target = 0 if target_pos is None and target_rot is None else (target_pos if target_pos is not None else target_rot).shape[1]
         n_target = int(n_target)
-        shapes = (("x_ref", x_ref, (B, self.n_in)), ("posture_weight", posture_weight, (self.n_in,)), ("target_pos", target_pos, (B, n_target, 3)),
+        shapes = [("x_ref", x_ref, (B, self.n_in)), ("posture_weight", posture_weight, (self.n_in,)), ("target_pos", target_pos, (B, n_target, 3)),
                   ("target_rot", target_rot, (B, n_target, 3, 3)), ("pos_weight", pos_weight, (B, n_target)),
                   ("rot_weight", rot_weight, (B, n_target)), ("pair_weight", pair_weight, (self.n_pair,)), ("lo", lo, (self.n_in,)),
-                  ("hi", hi, (self.n_in,)))
+                  ("hi", hi, (self.n_in,))] + [(name, a, want()) for name, a, want in extra]
         for name, a, want in shapes:
             if a is not None and a.shape != want:
                 raise ValueError(f"{name} must have shape {want}, got {a.shape}")
         if (lo is None) != (hi is None):
             raise ValueError("lo and hi must both be given or both be None")
-        x = np.zeros((B, self.n_in), dtype=np.float64)
-        iters = np.zeros(B, dtype=np.int32)
-        energy = np.zeros((B, 3), dtype=np.float64)
-        status = np.zeros(B, dtype=np.int32)
-        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
-        check(load().dexr_sphere_resolve(self._h, B, d(x0), d(fixed), d(x_ref), d(posture_weight), n_target, d(target_pos), d(target_rot),
-                                         d(pos_weight), d(rot_weight), float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi),
-                                         float(damping), float(max_step), float(tol), int(max_iters), d(x), _ptr(iters, C.c_int32),
-                                         d(energy), _ptr(status, C.c_int32)))
-        return x, iters, energy, status
+        out = (np.zeros((B, self.n_in), dtype=np.float64), np.zeros(B, dtype=np.int32), np.zeros((B, energy_cols), dtype=np.float64),
+               np.zeros(B, dtype=np.int32))
+        arrays = (x0, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi, *posed,
+                  *(a for _, a, _ in extra))
+        return arrays, n_target, B, out
 
     # the posture solve with the obstacle term (include/dexr_resolve_obstacles.h) --------------------------------
     def resolve_obstacles_dev(self, obstacles: "ObstacleSet", B: int, x0_ptr: int, fixed_ptr: int, margin: float, damping: float,
@@ -867,30 +883,11 @@ class SphereModel:
         """-> (x (B, n_in) float64, iters (B) int32, energy (B, 4) float64, status (B) int32) (dexr_sphere_resolve_obstacles): the
         arguments of `resolve`, and the obstacle pose per frame or None, obstacle_margin (None: margin), obstacle_weight and
         prim_weight (n_prim) or None."""
-        for name, v in (("margin", margin), ("damping", damping), ("max_iters", max_iters)):
-            if v is None:
-                raise ValueError(f"{name} is required")
-        x0, fixed, B = self._host_inputs(x0, fixed)
-        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
-        x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi, prim_weight = (
-            f64(a) for a in (x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi, prim_weight))
-        pos, rot = self._host_pose(B, obstacle_pos, obstacle_rot)
-        if n_target is None:
-            n_target = 0 if target_pos is None and target_rot is None else (target_pos if target_pos is not None else target_rot).shape[1]
-        n_target = int(n_target)
-        shapes = (("x_ref", x_ref, (B, self.n_in)), ("posture_weight", posture_weight, (self.n_in,)), ("target_pos", target_pos, (B, n_target, 3)),
-                  ("target_rot", target_rot, (B, n_target, 3, 3)), ("pos_weight", pos_weight, (B, n_target)),
-                  ("rot_weight", rot_weight, (B, n_target)), ("pair_weight", pair_weight, (self.n_pair,)), ("lo", lo, (self.n_in,)),
-                  ("hi", hi, (self.n_in,)), ("prim_weight", prim_weight, (obstacles.n_prim,)))
-        for name, a, want in shapes:
-            if a is not None and a.shape != want:
-                raise ValueError(f"{name} must have shape {want}, got {a.shape}")
-        if (lo is None) != (hi is None):
-            raise ValueError("lo and hi must both be given or both be None")
-        x = np.zeros((B, self.n_in), dtype=np.float64)
-        iters = np.zeros(B, dtype=np.int32)
-        energy = np.zeros((B, 4), dtype=np.float64)
-        status = np.zeros(B, dtype=np.int32)
+        (x0, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi, pos, rot,
+         prim_weight), n_target, B, out = self._resolve_host(
+            x0, margin, damping, max_iters, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi,
+            n_target, 4, pose=(obstacle_pos, obstacle_rot), extra=(("prim_weight", prim_weight, lambda: (obstacles.n_prim,)),))
+        x, iters, energy, status = out
         d = lambda a: _ptr(a, C.c_double)  # noqa: E731
         om = margin if obstacle_margin is None else obstacle_margin
         check(load().dexr_sphere_resolve_obstacles(
@@ -898,7 +895,7 @@ class SphereModel:
             float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi), float(damping), float(max_step), float(tol), int(max_iters),
             obstacles.handle, d(pos), d(rot), float(om), float(obstacle_weight), d(prim_weight), d(x), _ptr(iters, C.c_int32), d(energy),
             _ptr(status, C.c_int32)))
-        return x, iters, energy, status
+        return out
 
     # the model's spheres against an obstacle set (include/dexr_obstacles.h); the pair list plays no part --------------
     def obstacle_distances_dev(self, obstacles: "ObstacleSet", B: int, x_ptr: int, fixed_ptr: int, dist_ptr: int, nearest_ptr: int = 0,
@@ -1052,37 +1049,17 @@ class SphereModel:
                      obstacle_margin=None, obstacle_weight: float = 1.0):
         """-> (x (B, n_in) float64, iters (B) int32, energy (B, 4) float64, status (B) int32) (dexr_sphere_resolve_grid): the
         arguments of `resolve`, and the obstacle pose per frame or None, obstacle_margin (None: margin) and obstacle_weight."""
-        for name, v in (("margin", margin), ("damping", damping), ("max_iters", max_iters)):
-            if v is None:
-                raise ValueError(f"{name} is required")
-        x0, fixed, B = self._host_inputs(x0, fixed)
-        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
-        x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi = (
-            f64(a) for a in (x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi))
-        pos, rot = self._host_pose(B, obstacle_pos, obstacle_rot)
-        if n_target is None:
-            n_target = 0 if target_pos is None and target_rot is None else (target_pos if target_pos is not None else target_rot).shape[1]
-        n_target = int(n_target)
-        shapes = (("x_ref", x_ref, (B, self.n_in)), ("posture_weight", posture_weight, (self.n_in,)), ("target_pos", target_pos, (B, n_target, 3)),
-                  ("target_rot", target_rot, (B, n_target, 3, 3)), ("pos_weight", pos_weight, (B, n_target)),
-                  ("rot_weight", rot_weight, (B, n_target)), ("pair_weight", pair_weight, (self.n_pair,)), ("lo", lo, (self.n_in,)),
-                  ("hi", hi, (self.n_in,)))
-        for name, a, want in shapes:
-            if a is not None and a.shape != want:
-                raise ValueError(f"{name} must have shape {want}, got {a.shape}")
-        if (lo is None) != (hi is None):
-            raise ValueError("lo and hi must both be given or both be None")
-        x = np.zeros((B, self.n_in), dtype=np.float64)
-        iters = np.zeros(B, dtype=np.int32)
-        energy = np.zeros((B, 4), dtype=np.float64)
-        status = np.zeros(B, dtype=np.int32)
+        (x0, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi, pos, rot), n_target, B, out = \
+            self._resolve_host(x0, margin, damping, max_iters, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight,
+                               pair_weight, lo, hi, n_target, 4, pose=(obstacle_pos, obstacle_rot))
+        x, iters, energy, status = out
         d = lambda a: _ptr(a, C.c_double)  # noqa: E731
         om = margin if obstacle_margin is None else obstacle_margin
         check(load().dexr_sphere_resolve_grid(
             self._h, B, d(x0), d(fixed), d(x_ref), d(posture_weight), n_target, d(target_pos), d(target_rot), d(pos_weight), d(rot_weight),
             float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi), float(damping), float(max_step), float(tol), int(max_iters),
             grid.handle, d(pos), d(rot), float(om), float(obstacle_weight), d(x), _ptr(iters, C.c_int32), d(energy), _ptr(status, C.c_int32)))
-        return x, iters, energy, status
+        return out
 
 
 class ObstacleSet:

@@ -1001,11 +1001,12 @@ def robot_grid_penalty(robot, qpos, sphere_set: SphereSet, grid: SdfGrid, margin
     return (e, g, wr) if wrench else (e, g)
 
 
-# ---- the posture solve with the obstacle term (include/dexr_resolve_obstacles.h) -----------------------------------------------------
-def _resolve_obstacles(model_of, n_in, n_fixed, kin, robot, x0, what, fixed_qpos, sphere_set, obstacles, margin, obstacle_margin, obstacle_pos,
-                       obstacle_rot, obstacle_weight, prim_weight, damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight,
-                       link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits):
-    """every rule (those of `_resolve`, then the obstacle side's), then one model and one launch."""
+# ---- the posture solve with an obstacle term: primitives (include/dexr_resolve_obstacles.h) or a grid (include/dexr_resolve_grid.h) ------
+def _resolve_contacts(model_of, n_in, n_fixed, kin, robot, x0, what, fixed_qpos, sphere_set, obstacle, grid, margin, obstacle_margin, obstacle_pos,
+                      obstacle_rot, obstacle_weight, prim_weight, damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight,
+                      link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits):
+    """every rule (those of `_resolve`, then the obstacle side's), then one model and one launch.  obstacle: an ObstacleSet, or with
+    `grid` an SdfGrid (which has no prim_weight: None)."""
     import torch
 
     named = _resolve_rules(n_in, x0, sphere_set, damping, max_iters, posture_weight, q_ref, collision_weight, link_names, target_pos,
@@ -1018,8 +1019,8 @@ def _resolve_obstacles(model_of, n_in, n_fixed, kin, robot, x0, what, fixed_qpos
                                         or not math.isfinite(obstacle_margin) or obstacle_margin < 0):
         raise ValueError(f"obstacle_margin must be a finite Python float >= 0 or None (margin), got {obstacle_margin!r}")
     pairs = _check(n_in, n_fixed, kin, robot, x0, fixed_qpos, sphere_set, what, margin, pair_weight, penalty=True, poses=False)
-    _check_obstacles(n_in, n_fixed, kin, robot, x0, fixed_qpos, sphere_set, obstacles, obstacle_pos, obstacle_rot, what, margin, prim_weight,
-                     penalty=True)  # (ends with the device)
+    _check_obstacles(n_in, n_fixed, kin, robot, x0, fixed_qpos, sphere_set, obstacle, obstacle_pos, obstacle_rot, what, margin, prim_weight,
+                     penalty=True, grid=grid)  # (ends with the device)
     if pair_weight is not None:
         named = named + [("pair_weight", pair_weight)]
     for name, t in named:
@@ -1043,15 +1044,17 @@ def _resolve_obstacles(model_of, n_in, n_fixed, kin, robot, x0, what, fixed_qpos
         energy = torch.empty((B, 4), dtype=torch.float32, device=x0.device)
         status = torch.empty((B,), dtype=torch.int32, device=x0.device)
         if B > 0:
-            model.resolve_obstacles_dev(obstacles.device_set(torch.cuda.current_device()), B, xc.data_ptr(), ptr(fixed), float(margin),
-                                        float(damping), int(max_iters), q.data_ptr(), iters.data_ptr(), energy.data_ptr(), status.data_ptr(),
-                                        x_ref_ptr=ptr(xr), posture_weight_ptr=ptr(u), n_target=len(link_names or ()), target_pos_ptr=ptr(tp),
-                                        target_rot_ptr=ptr(tr), pos_weight_ptr=ptr(wl), rot_weight_ptr=ptr(wa),
-                                        collision_weight=float(collision_weight), pair_weight_ptr=ptr(pw), lo_ptr=ptr(lo), hi_ptr=ptr(hi),
-                                        tol=float(tol), max_step=float(max_step), obstacle_pos_ptr=ptr(pos), obstacle_rot_ptr=ptr(rot),
-                                        obstacle_margin=float(margin if obstacle_margin is None else obstacle_margin),
-                                        obstacle_weight=float(obstacle_weight), prim_weight_ptr=ptr(ow),
-                                        stream=torch.cuda.current_stream(x0.device).cuda_stream)
+            if grid:
+                launch, handle, own = model.resolve_grid_dev, obstacle.device_grid(torch.cuda.current_device()), {}
+            else:
+                launch, handle, own = model.resolve_obstacles_dev, obstacle.device_set(torch.cuda.current_device()), dict(prim_weight_ptr=ptr(ow))
+            launch(handle, B, xc.data_ptr(), ptr(fixed), float(margin), float(damping), int(max_iters), q.data_ptr(), iters.data_ptr(),
+                   energy.data_ptr(), status.data_ptr(), x_ref_ptr=ptr(xr), posture_weight_ptr=ptr(u), n_target=len(link_names or ()),
+                   target_pos_ptr=ptr(tp), target_rot_ptr=ptr(tr), pos_weight_ptr=ptr(wl), rot_weight_ptr=ptr(wa),
+                   collision_weight=float(collision_weight), pair_weight_ptr=ptr(pw), lo_ptr=ptr(lo), hi_ptr=ptr(hi), tol=float(tol),
+                   max_step=float(max_step), obstacle_pos_ptr=ptr(pos), obstacle_rot_ptr=ptr(rot),
+                   obstacle_margin=float(margin if obstacle_margin is None else obstacle_margin), obstacle_weight=float(obstacle_weight),
+                   stream=torch.cuda.current_stream(x0.device).cuda_stream, **own)
     return q, iters, energy, status
 
 
@@ -1070,10 +1073,10 @@ def resolve_collisions(optimizer, q0, sphere_set: SphereSet, obstacles: Obstacle
     iters (B) int32, energy (B, 4) float32: pose, posture, self-collision and obstacle term at q, status (B) int32, whose bit
     _lib.RESOLVE_CONTACTS_TRUNCATED says that a point had more than 256 active (sphere, primitive) contacts: the curvature used the
     first 256 in the set's sphere order, then the primitives' order).  No autograd graph."""
-    return _resolve_obstacles(optimizer.sphere_model, optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q0,
-                              "q", fixed_qpos, sphere_set, obstacles, margin, obstacle_margin, obstacle_pos, obstacle_rot, obstacle_weight,
-                              prim_weight, damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight, link_names, target_pos,
-                              target_rot, pos_weight, rot_weight, tol, max_step, limits)
+    return _resolve_contacts(optimizer.sphere_model, optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q0,
+                             "q", fixed_qpos, sphere_set, obstacles, False, margin, obstacle_margin, obstacle_pos, obstacle_rot, obstacle_weight,
+                             prim_weight, damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight, link_names, target_pos,
+                             target_rot, pos_weight, rot_weight, tol, max_step, limits)
 
 
 def robot_resolve_collisions(robot, qpos0, sphere_set: SphereSet, obstacles: ObstacleSet, margin, obstacle_margin=None, obstacle_pos=None,
@@ -1081,63 +1084,10 @@ def robot_resolve_collisions(robot, qpos0, sphere_set: SphereSet, obstacles: Obs
                              posture_weight=None, q_ref=None, collision_weight=1.0, pair_weight=None, link_names=None, target_pos=None,
                              target_rot=None, pos_weight=None, rot_weight=None, tol=0.0, max_step=0.0, limits=None):
     """The same for a full robot qpos (B, robot.dof) in dof order; every joint is a column of its own, limits (robot.dof, 2)."""
-    return _resolve_obstacles(robot.sphere_model, robot.dof, 0, robot.kin, robot, qpos0, "qpos", None, sphere_set, obstacles, margin,
-                              obstacle_margin, obstacle_pos, obstacle_rot, obstacle_weight, prim_weight, damping, max_iters, posture_weight,
-                              q_ref, collision_weight, pair_weight, link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step,
-                              limits)
-
-
-# ---- the posture solve with the grid term (include/dexr_resolve_grid.h) -----------------------------------------------------------------
-def _resolve_grid(model_of, n_in, n_fixed, kin, robot, x0, what, fixed_qpos, sphere_set, grid, margin, obstacle_margin, obstacle_pos, obstacle_rot,
-                  obstacle_weight, damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight, link_names, target_pos, target_rot,
-                  pos_weight, rot_weight, tol, max_step, limits):
-    """every rule (those of `_resolve`, then the grid side's), then one model and one launch."""
-    import torch
-
-    named = _resolve_rules(n_in, x0, sphere_set, damping, max_iters, posture_weight, q_ref, collision_weight, link_names, target_pos,
-                           target_rot, pos_weight, rot_weight, tol, max_step, limits)
-    for n in link_names or ():
-        kin.body_frame_index(n)  # ValueError on an unknown link
-    if isinstance(obstacle_weight, bool) or not isinstance(obstacle_weight, (int, float)) or not math.isfinite(obstacle_weight) or obstacle_weight < 0:
-        raise ValueError(f"obstacle_weight must be a finite Python float >= 0, got {obstacle_weight!r}")
-    if obstacle_margin is not None and (isinstance(obstacle_margin, bool) or not isinstance(obstacle_margin, (int, float))
-                                        or not math.isfinite(obstacle_margin) or obstacle_margin < 0):
-        raise ValueError(f"obstacle_margin must be a finite Python float >= 0 or None (margin), got {obstacle_margin!r}")
-    pairs = _check(n_in, n_fixed, kin, robot, x0, fixed_qpos, sphere_set, what, margin, pair_weight, penalty=True, poses=False)
-    _check_obstacles(n_in, n_fixed, kin, robot, x0, fixed_qpos, sphere_set, grid, obstacle_pos, obstacle_rot, what, margin, penalty=True,
-                     grid=True)  # (ends with the device)
-    if pair_weight is not None:
-        named = named + [("pair_weight", pair_weight)]
-    for name, t in named:
-        if t.device != x0.device:
-            raise ValueError(f"{name} is on {t.device}, {what} on {x0.device}: all tensors must be on one CUDA device")
-    B = x0.shape[0]
-    xc, fixed = _inputs(x0, fixed_qpos)
-    c = lambda a: None if a is None else a.detach().contiguous()  # noqa: E731
-    xr, tp, tr, wl, wa, pw = (c(a) for a in (q_ref, target_pos, target_rot, pos_weight, rot_weight, pair_weight))
-    pos, rot = _obstacle_pose(obstacle_pos, obstacle_rot)
-    lo, hi = (None, None) if limits is None else (limits.detach()[:, 0].contiguous(), limits.detach()[:, 1].contiguous())
-    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
-    with torch.cuda.device(x0.device):
-        if isinstance(posture_weight, torch.Tensor):
-            u = c(posture_weight)
-        else:
-            u = None if not posture_weight else torch.full((n_in,), float(posture_weight), dtype=torch.float32, device=x0.device)
-        model = model_of(sphere_set, pairs, tuple(link_names or ()))
-        q = torch.empty((B, model.n_in), dtype=torch.float32, device=x0.device)
-        iters = torch.empty((B,), dtype=torch.int32, device=x0.device)
-        energy = torch.empty((B, 4), dtype=torch.float32, device=x0.device)
-        status = torch.empty((B,), dtype=torch.int32, device=x0.device)
-        if B > 0:
-            model.resolve_grid_dev(grid.device_grid(torch.cuda.current_device()), B, xc.data_ptr(), ptr(fixed), float(margin), float(damping),
-                                   int(max_iters), q.data_ptr(), iters.data_ptr(), energy.data_ptr(), status.data_ptr(), x_ref_ptr=ptr(xr),
-                                   posture_weight_ptr=ptr(u), n_target=len(link_names or ()), target_pos_ptr=ptr(tp), target_rot_ptr=ptr(tr),
-                                   pos_weight_ptr=ptr(wl), rot_weight_ptr=ptr(wa), collision_weight=float(collision_weight),
-                                   pair_weight_ptr=ptr(pw), lo_ptr=ptr(lo), hi_ptr=ptr(hi), tol=float(tol), max_step=float(max_step),
-                                   obstacle_pos_ptr=ptr(pos), obstacle_rot_ptr=ptr(rot),
-                                   obstacle_margin=float(margin if obstacle_margin is None else obstacle_margin),
-                                   obstacle_weight=float(obstacle_weight), stream=torch.cuda.current_stream(x0.device).cuda_stream)
-    return q, iters, energy, status
+    return _resolve_contacts(robot.sphere_model, robot.dof, 0, robot.kin, robot, qpos0, "qpos", None, sphere_set, obstacles, False, margin,
+                             obstacle_margin, obstacle_pos, obstacle_rot, obstacle_weight, prim_weight, damping, max_iters, posture_weight,
+                             q_ref, collision_weight, pair_weight, link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step,
+                             limits)
 
 
 def resolve_grid_collisions(optimizer, q0, sphere_set: SphereSet, grid: SdfGrid, margin, obstacle_margin=None, obstacle_pos=None,
@@ -1155,10 +1105,10 @@ def resolve_grid_collisions(optimizer, q0, sphere_set: SphereSet, grid: SdfGrid,
     the damping are those of `resolve_self_collision`.  -> (q (B, n_opt) float32, iters (B) int32, energy (B, 4) float32: pose,
     posture, self-collision and grid term at q, status (B) int32).  A sphere has at most one contact with a grid: every contact
     enters the curvature and _lib.RESOLVE_CONTACTS_TRUNCATED is never set.  No autograd graph."""
-    return _resolve_grid(optimizer.sphere_model, optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q0, "q",
-                         fixed_qpos, sphere_set, grid, margin, obstacle_margin, obstacle_pos, obstacle_rot, obstacle_weight, damping, max_iters,
-                         posture_weight, q_ref, collision_weight, pair_weight, link_names, target_pos, target_rot, pos_weight, rot_weight, tol,
-                         max_step, limits)
+    return _resolve_contacts(optimizer.sphere_model, optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q0,
+                             "q", fixed_qpos, sphere_set, grid, True, margin, obstacle_margin, obstacle_pos, obstacle_rot, obstacle_weight, None,
+                             damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight, link_names, target_pos, target_rot,
+                             pos_weight, rot_weight, tol, max_step, limits)
 
 
 def robot_resolve_grid_collisions(robot, qpos0, sphere_set: SphereSet, grid: SdfGrid, margin, obstacle_margin=None, obstacle_pos=None,
@@ -1166,9 +1116,9 @@ def robot_resolve_grid_collisions(robot, qpos0, sphere_set: SphereSet, grid: Sdf
                                   q_ref=None, collision_weight=1.0, pair_weight=None, link_names=None, target_pos=None, target_rot=None,
                                   pos_weight=None, rot_weight=None, tol=0.0, max_step=0.0, limits=None):
     """The same for a full robot qpos (B, robot.dof) in dof order; every joint is a column of its own, limits (robot.dof, 2)."""
-    return _resolve_grid(robot.sphere_model, robot.dof, 0, robot.kin, robot, qpos0, "qpos", None, sphere_set, grid, margin, obstacle_margin,
-                         obstacle_pos, obstacle_rot, obstacle_weight, damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight,
-                         link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits)
+    return _resolve_contacts(robot.sphere_model, robot.dof, 0, robot.kin, robot, qpos0, "qpos", None, sphere_set, grid, True, margin,
+                             obstacle_margin, obstacle_pos, obstacle_rot, obstacle_weight, None, damping, max_iters, posture_weight, q_ref,
+                             collision_weight, pair_weight, link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits)
 
 
 __all__ = ["SphereSet", "default_pairs", "sphere_distances", "self_collision_penalty", "robot_sphere_distances",

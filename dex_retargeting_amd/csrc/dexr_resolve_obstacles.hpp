@@ -1,25 +1,34 @@
 // dexr_resolve_obstacles.hpp -- the collision-aware posture solve against obstacles (include/dexr_resolve_obstacles.h): a fragment
-// of dexr_pose.hip, which includes it once after dexr_obstacles.hpp.  pose_resolve_obstacle_kernel<T> is the resident loop of
-// pose_resolve_kernel (dexr_resolve.hpp, whose layout, arguments, resolve_link, resolve_force_entry and resolve_row_entry it
-// shares) with phase B of pose_obstacle_kernel inside it (obstacle_sdf and the primitive table of dexr_obstacles.hpp).
+// of dexr_pose.hip, which includes it once after dexr_obstacles.hpp.  It owns two things:
+//   resolve_contact_loop<T, Src>  the resident loop of the two contact kernels, made of the phases of dexr_resolve.hpp (whose
+//                                 layout, arguments and resolve_* helpers it uses) and of a contact source Src for what an obstacle
+//                                 term adds; pose_resolve_grid_kernel (dexr_resolve_grid.hpp) is its other instantiation;
+//   ObstacleContacts<T>           the contact source of a primitive table (obstacle_sdf of dexr_obstacles.hpp), with
+//                                 pose_resolve_obstacle_kernel<T>, its launcher and its two entry points.
 //
-// What a pass does beyond dexr_resolve.hpp:
+// What a pass of resolve_contact_loop does beyond pose_resolve_kernel:
 //   A  pass 0 also parks the frame's obstacle pose (p_o, R_o; zeros and the identity where the caller left them out);
-//   B  after the pair forces of a sphere the thread moves the centre into the obstacle frame once, y = R_o^T (c - p_o), and loops
-//      over the primitives in set order through obstacle_sdf -- the table is uniform data read through the scalar load path, the
-//      index is the loop counter alone.  The sphere's force becomes w_col f_pairs + w_obs R_o sum_m w_m h n, so that g needs no new
-//      code; w_m h^2 goes to a second set of sixteen partial energies; the sphere's active primitives are ONE 64-bit mask in LDS,
-//      stored at the CALLER's index of the sphere (n_prim <= 64: 8 B per sphere instead of a byte per contact);
-//   C  thread t counts the contacts of its contiguous slice of caller indices by popcount; thread 0 adds the sixteen partial
+//   B  after the pair forces of a sphere the thread moves the centre into the obstacle frame once, y = R_o^T (c - p_o), and asks
+//      the source for the sphere's obstacle term: the force sum w h grad sdf in that frame, w h^2 onto a second set of sixteen
+//      partial energies, and the sphere's active contacts in LDS at the CALLER's index of the sphere.  The sphere's force becomes
+//      w_col f_pairs + w_obs R_o f_obstacle, so that g needs no new code;
+//   C  thread t has the source count the contacts of its contiguous slice of caller indices; thread 0 adds the sixteen partial
 //      obstacle energies in order and decides on E = ((E_pose + E_post) + E_col) + E_obs;
-//   D  the contact list (sorted sphere | primitive << 7, 16 bits) by a prefix over the sixteen counts: caller's sphere order, then
-//      set order, no atomics.  After the pair chunks the contact curvature goes through the same rank-16 staging: the thread
-//      recomputes the normal of (s, m) from the parked centre and pose and takes the row through resolve_row_entry with one sphere.
+//   D  the source appends the thread's contacts to the frame's contact list at a prefix over the sixteen counts: caller's sphere
+//      order, no atomics.  After the pair chunks the contact curvature goes through the same rank-16 staging: the source recomputes
+//      a contact's normal from the parked centre and pose, the row goes through resolve_row_entry with one sphere.
 // Kept system, phase E, factor / solve and the outputs are those of pose_resolve_kernel; energy_out has four columns.
+// The rule's constants are the header's, read where the rule stands and nowhere as numbers of this file's own: lam times
+// DEXR_RESOLVE_LAM_UP on a rejection, over DEXR_RESOLVE_LAM_DOWN on an accepted trial, DEXR_RESOLVE_MAXREJECT rejections in a row
+// end a frame (resolve_decide); the first DEXR_RESOLVE_MAXACTIVE active pairs enter the curvature (resolve_pair_total,
+// resolve_list_pairs).
 //
-// THE LOOP CANNOT HANG, for the reasons of dexr_resolve.hpp: k = 0 .. max_iters at most, every barrier outside every condition that
-// differs between the threads of a block, both chunk counts the block's largest (read by every thread from LDS after a barrier),
-// the one early exit on the AND of all stop flags.  Every sum is taken by one thread in a fixed order.
+// A contact source is a small struct with: head_words(n_sphere) and tail_bytes(n_sphere), the LDS it adds per frame (64-bit words
+// behind the frozen masks, bytes behind the contact counts); place(L, own, n_sphere), which takes its frame's share; term, count,
+// capped, append and contact, the five things above.  ObstacleContacts: a loop over the primitives in set order -- the table is
+// uniform data read through the scalar load path, the index is the loop counter alone -- and ONE 64-bit mask per sphere
+// (n_prim <= 64: 8 B per sphere instead of a byte per contact); counts by popcount; list entries sorted sphere | primitive << 7
+// (16 bits), sphere order then set order, capped at DEXR_RESOLVE_MAXCONTACT with DEXR_RESOLVE_CONTACTS_TRUNCATED.
 //
 // LDS of a block: sixteen 64-bit partial frozen masks per frame | a 64-bit contact mask per sphere and frame | the fork slots | per
 // frame a region [frame][stride], odd stride (ResolveLayout, then the obstacle pose and the sixteen partial obstacle energies) |
@@ -28,8 +37,6 @@
 #include "dexr_resolve_obstacles.h"
 
 namespace {
-
-constexpr int RSV_OBS = 7;  // the one scalar of a frame's RSV_SCALARS that dexr_resolve.hpp leaves free: E_obs at the accepted point
 
 template <typename T>
 struct ResolveObstacleArgs {
@@ -53,6 +60,201 @@ __device__ __forceinline__ void obstacle_to_world(const T* po, const T v[3], T w
   for (int i = 0; i < 3; ++i) w[i] = fma(po[3 + 3 * i + 2], v[2], fma(po[3 + 3 * i + 1], v[1], po[3 + 3 * i] * v[0]));
 }
 
+// bytes per frame of the counts every contact source has: sixteen contact counts and the curvature contacts
+constexpr int RESOLVE_CONTACT_COUNTS = (SPH_FANOUT + 1) * (int)sizeof(int32_t);
+
+template <typename T>
+struct ObstacleContacts {
+  const ObstacleD<T>* prims;
+  const int32_t* kinds;
+  const T* ow;  // (n_prim) or NULL
+  int n_prim;
+  unsigned long long* msk;  // [n_sphere] the frame's contact masks, by the caller's sphere index
+  uint16_t* clst;           // [DEXR_RESOLVE_MAXCONTACT] the frame's contact list
+
+  static __host__ __device__ int head_words(int n_sphere) { return n_sphere; }
+  static __host__ __device__ int tail_bytes(int) { return DEXR_RESOLVE_MAXCONTACT * (int)sizeof(uint16_t); }
+
+  __device__ __forceinline__ void place(const ResolveLds<T>& L, unsigned char* own, int n_sphere) {
+    msk = L.head + L.fr * n_sphere;
+    clst = reinterpret_cast<uint16_t*>(own) + L.fr * DEXR_RESOLVE_MAXCONTACT;
+  }
+
+  // the term of the sphere of radius rs at yo (obstacle frame), c its caller's index: sum_m w_m h grad sdf_m into fo, w_m h^2 onto eo
+  __device__ __forceinline__ void term(const ResolveObstacleArgs<T>& O, const T yo[3], T rs, int c, T& eo, T fo[3]) const {
+    fo[0] = fo[1] = fo[2] = T(0);
+    unsigned long long bits = 0;
+    for (int m = 0; m < n_prim; ++m) {
+      T gm[3];
+      const T d = obstacle_sdf(kinds[m], prims[m], yo, gm) - rs;
+      T h = O.omargin - d;
+      if (h <= T(0)) h = T(0);  // (a comparison: a NaN stays a NaN)
+      const T wh = ow ? ow[m] * h : h;
+      eo = fma(wh, h, eo);
+      if (h > T(0)) bits |= 1ull << m;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) fo[i] = fma(wh, gm[i], fo[i]);
+    }
+    msk[c] = bits;
+  }
+
+  __device__ __forceinline__ int count(int c0, int c1) const {
+    int n = 0;
+    for (int c = c0; c < c1; ++c) n += __popcll(msk[c]);
+    return n;
+  }
+
+  __device__ __forceinline__ bool capped(int& ctotal) const {
+    if (ctotal <= DEXR_RESOLVE_MAXCONTACT) return false;
+    ctotal = DEXR_RESOLVE_MAXCONTACT;
+    return true;
+  }
+
+  // the contacts of the caller's spheres [c0, c1) from entry coff on: the caller's sphere order, then set order
+  __device__ __forceinline__ void append(int c0, int c1, int coff, const int32_t* __restrict__ sph_in) const {
+    for (int c = c0; c < c1 && coff < DEXR_RESOLVE_MAXCONTACT; ++c) {
+      unsigned long long bits = msk[c];
+      const uint32_t s = (uint32_t)sph_in[c];
+      while (bits != 0 && coff < DEXR_RESOLVE_MAXCONTACT) {
+        const uint32_t m = (uint32_t)__ffsll((long long)bits) - 1u;
+        clst[coff++] = (uint16_t)(s | (m << 7));
+        bits &= bits - 1;
+      }
+    }
+  }
+
+  // the q-th contact of the list: its sorted sphere, its world normal and its weight
+  __device__ __forceinline__ void contact(const ResolveObstacleArgs<T>& O, const T* po, const T* cen, int q, int& si, T n[3], T& w) const {
+    const uint32_t cm = clst[q];
+    const int m = cm >> 7;
+    si = cm & 127;
+    T yo[3], gm[3];
+    obstacle_point(po, cen + 3 * si, yo);
+    (void)obstacle_sdf(kinds[m], prims[m], yo, gm);
+    obstacle_to_world(po, gm, n);
+    w = ow ? O.wobs * ow[m] : O.wobs;
+  }
+};
+
+// The resident loop of a contact kernel: the skeleton of pose_resolve_kernel (dexr_resolve.hpp, where the reasons why THE LOOP
+// CANNOT HANG are written down; here both chunk counts are the block's largest, read by every thread from LDS after a barrier)
+// with the contact source C in it.  obase, oebase: the obstacle pose and the sixteen partial obstacle energies in a frame's region.
+template <typename T, typename Src>
+__device__ __forceinline__ void resolve_contact_loop(unsigned char* pose_lds, const ResolveModel<T>& M, const PoseArgs<T>& P,
+                                                     const int32_t* __restrict__ sph_in, const ResolveLayout Y, int obase, int oebase, int fstride,
+                                                     const ResolveArgs<T> A, const ResolveObstacleArgs<T>& O, Src C) {
+  const int nl = blockDim.x / SPH_FANOUT, tid = threadIdx.x;  // nl: frames of this block
+  const SphereIndex& S = M.S;
+  const int fr = tid / SPH_FANOUT, t = tid % SPH_FANOUT;
+  const ResolveLds<T> L = resolve_lds<T>(pose_lds, nl, fr, t, Y, P.n_slot, M.n_act, S.n_pair, fstride, Src::head_words(S.n_sphere),
+                                         RESOLVE_CONTACT_COUNTS + Src::tail_bytes(S.n_sphere));
+  int32_t* ccnt = reinterpret_cast<int32_t*>(L.tail);  // [nl][SPH_FANOUT]: contacts of a thread's slice of spheres
+  int32_t* ncon = ccnt + nl * SPH_FANOUT;              // [nl]: curvature contacts
+  C.place(L, reinterpret_cast<unsigned char*>(ncon + nl), S.n_sphere);
+  const int64_t first = (int64_t)blockIdx.x * nl;
+  const bool inb = first + fr < P.B;
+  const T* po = L.pk + obase;  // the frame's obstacle pose
+  const T* xr = A.xref + (inb ? first + fr : 0) * P.n_in;  // (read by working frames alone)
+  const int schunk = (S.n_sphere + SPH_FANOUT - 1) / SPH_FANOUT;  // thread t owns the caller's spheres [t schunk, (t + 1) schunk)
+  const int c0 = t * schunk < S.n_sphere ? t * schunk : S.n_sphere, c1 = c0 + schunk < S.n_sphere ? c0 + schunk : S.n_sphere;
+  resolve_start(L, A, P.n_in, first + fr, inb);
+  if (t == 0) ncon[fr] = 0;
+  __syncthreads();
+  for (int k = 0; k <= A.max_iters; ++k) {
+    if (tid < nl && L.stopf[tid] == 0) {  // phase A; pass 0: the obstacle pose
+      if (k == 0) {
+        const int64_t b = first + tid;
+        T* oa = L.park + tid * Y.stride + obase;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) oa[i] = O.opos ? O.opos[b * 3 + i] : T(0);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) oa[3 + i] = O.orot ? O.orot[b * 9 + i] : ((i % 4 == 0) ? T(1) : T(0));
+      }
+      resolve_walk(L, M.joints, M.links, M.spheres, S, P, Y, A, tid, first);
+    }
+    __syncthreads();
+    const bool work = L.stopf[fr] == 0;
+    if (work) {  // phase B: a thread per sphere; its pair forces, then its obstacle term: forces, energies, both kinds of active flag
+      T e = T(0), eo = T(0);
+      for (int s = t; s < S.n_sphere; s += SPH_FANOUT) {
+        const T cs[3] = {L.cen[3 * s], L.cen[3 * s + 1], L.cen[3 * s + 2]};
+        T f[3], yo[3], fo[3], fw[3];
+        resolve_pair_forces(L, M, A, s, cs, e, f);
+        obstacle_point(po, cs, yo);
+        C.term(O, yo, M.spheres[s].r, S.sph_out[s], eo, fo);
+        obstacle_to_world(po, fo, fw);
+        L.frc[3 * s] = fma(O.wobs, fw[0], A.wcol * f[0]);
+        L.frc[3 * s + 1] = fma(O.wobs, fw[1], A.wcol * f[1]);
+        L.frc[3 * s + 2] = fma(O.wobs, fw[2], A.wcol * f[2]);
+      }
+      L.pk[Y.pebase + t] = e;
+      L.pk[oebase + t] = eo;
+    }
+    __syncthreads();
+    if (work) {  // phase C: the counts of both lists, and the decision
+      resolve_count_pairs(L);
+      ccnt[fr * SPH_FANOUT + t] = C.count(c0, c1);
+      if (t == 0) resolve_decide<true>(L, M, A, k, resolve_sum16(L.pk + Y.pebase) * A.wcol, resolve_sum16(L.pk + oebase) * O.wobs);
+    }
+    __syncthreads();
+    if (work && t == 0) {  // (stat, nact and ncon of a frame are its thread 0's alone until the next barrier)
+      const int total = resolve_pair_total(L);
+      int ctotal = 0;
+      for (int u = 0; u < SPH_FANOUT; ++u) ctotal += ccnt[fr * SPH_FANOUT + u];
+      if (C.capped(ctotal)) L.stat[fr] |= DEXR_RESOLVE_CONTACTS_TRUNCATED;
+      const bool keep = L.accf[fr] != 0 && L.stopf[fr] == 0;
+      L.nact[fr] = keep ? total : 0;
+      ncon[fr] = keep ? ctotal : 0;
+    }
+    if (resolve_all_stopped(L)) break;
+    const bool go = L.stopf[fr] == 0;          // the frame goes on: it needs a next trial
+    const bool build = go && L.accf[fr] != 0;  // ... from a new point: its lists, g and H are formed and kept
+    if (build) {  // phase D: both lists in their orders, then g
+      resolve_list_pairs(L);
+      int coff = 0;
+      for (int u = 0; u < t; ++u) coff += ccnt[fr * SPH_FANOUT + u];
+      C.append(c0, c1, coff, sph_in);
+      resolve_gradient<true>(L, M, Y, A, xr);
+    }
+    __syncthreads();
+    const unsigned long long frozen = resolve_frozen(L);
+    if (build) resolve_base_h(L, M, Y, A, frozen);
+    int nmax = 0, cmax = 0;  // the block's largest lists: the same in every thread
+    for (int f = 0; f < nl; ++f) {
+      nmax = L.nact[f] > nmax ? L.nact[f] : nmax;
+      cmax = ncon[f] > cmax ? ncon[f] : cmax;
+    }
+    const int mine_n = L.nact[fr], mine_c = ncon[fr];  // (0 unless `build`)
+    nmax = (nmax + SPH_FANOUT - 1) / SPH_FANOUT * SPH_FANOUT;  // whole chunks: the contacts start at a chunk boundary of their own
+    for (int base = 0; base < nmax + cmax; base += SPH_FANOUT) {  // the curvature, sixteen rows at a time: the pairs' grad d_p, then
+      const bool pairs = base < nmax;                               // the contacts' grad d (the same choice in every thread)
+      const int at = pairs ? base : base - nmax;
+      const int have = pairs ? mine_n : mine_c;
+      if (at + t < have) {
+        T n[3], w;
+        int si, sj;
+        if (pairs) {
+          resolve_pair_contact(L, M, A, at + t, si, sj, n, w);
+        } else {
+          sj = -1;
+          C.contact(O, po, L.cen, at + t, si, n, w);
+        }
+        resolve_stage_row(L, M, frozen, si, sj, n, w);
+      }
+      __syncthreads();
+      const int nk = have - at < SPH_FANOUT ? have - at : SPH_FANOUT;
+      if (nk > 0) resolve_rank16(L, M, nk);
+      __syncthreads();
+    }
+    if (go) resolve_damp(L, M, frozen);  // phase E
+    __syncthreads();
+    ik_factor_solve(L.H, L.g, L.y, L.dg, M.n_act, t, go);
+    if (go) resolve_step(L, M, A);
+    __syncthreads();
+  }
+  if (inb) resolve_output(L, A, P.n_in, first + fr, 4);
+}
+
 template <typename T>
 __global__ void __launch_bounds__(SPH_FANOUT * SPH_FRAMES)
     pose_resolve_obstacle_kernel(const JointD<T>* __restrict__ joints, const LinkD<T>* __restrict__ links, PoseArgs<T> P,
@@ -62,448 +264,54 @@ __global__ void __launch_bounds__(SPH_FANOUT * SPH_FRAMES)
                                  const ObstacleD<T>* __restrict__ prims, const T* __restrict__ ow, int n_prim, int n_jx, int n_act,
                                  ResolveLayout Y, int obase, int oebase, int fstride, ResolveArgs<T> A, ResolveObstacleArgs<T> O) {
   extern __shared__ __attribute__((aligned(16))) unsigned char pose_lds[];
-  const int nl = blockDim.x / SPH_FANOUT, tid = threadIdx.x;  // nl: frames of this block
-  unsigned long long* part = reinterpret_cast<unsigned long long*>(pose_lds);  // [nl][SPH_FANOUT]
-  unsigned long long* masks = part + nl * SPH_FANOUT;                            // [nl][n_sphere], by the caller's sphere index
-  T* slots = reinterpret_cast<T*>(masks + (size_t)nl * S.n_sphere);
-  T* park = slots + (size_t)P.n_slot * 12 * nl;
-  uint32_t* lists = reinterpret_cast<uint32_t*>(park + (size_t)nl * Y.stride);  // [nl][DEXR_RESOLVE_MAXACTIVE]
-  int32_t* cnt = reinterpret_cast<int32_t*>(lists + nl * DEXR_RESOLVE_MAXACTIVE);  // [nl][SPH_FANOUT]
-  int32_t* stopf = cnt + nl * SPH_FANOUT;  // [nl] each: stop flag, trial steps, accepted?, status, rejections in a row, curvature pairs
-  int32_t* itv = stopf + nl;
-  int32_t* accf = itv + nl;
-  int32_t* stat = accf + nl;
-  int32_t* rej = stat + nl;
-  int32_t* nact = rej + nl;
-  int32_t* ccnt = nact + nl;              // [nl][SPH_FANOUT]: contacts of a thread's slice of spheres
-  int32_t* ncon = ccnt + nl * SPH_FANOUT;  // [nl]: curvature contacts
-  uint16_t* clists = reinterpret_cast<uint16_t*>(ncon + nl);  // [nl][DEXR_RESOLVE_MAXCONTACT]
-  unsigned char* flags = reinterpret_cast<unsigned char*>(clists + nl * DEXR_RESOLVE_MAXCONTACT);  // [nl][fstride]
-  const int n_tri = n_act * (n_act + 1) / 2;
-  const bool targets = A.n_target > 0;
-  const int64_t first = (int64_t)blockIdx.x * nl;
-  const int fr = tid / SPH_FANOUT, t = tid % SPH_FANOUT;
-  const bool inb = first + fr < P.B;
-  T* pk = park + (size_t)fr * Y.stride;
-  const T* cen = pk + Y.cbase;
-  T* frc = pk + Y.fbase;
-  T* H = pk + Y.hbase;
-  T* Hs = pk + Y.hsbase;
-  T* g = pk + Y.gbase;
-  T* gs = pk + Y.gsbase;
-  T* y = pk + Y.ybase;
-  T* dg = pk + Y.dbase;
-  T* xt = pk + Y.xbase;
-  T* xs = pk + Y.xsbase;
-  T* sc = pk + Y.sbase;
-  const T* po = pk + obase;  // the frame's obstacle pose
-  T* rows = H;  // [SPH_FANOUT][n_act], then SPH_FANOUT weights
-  T* rw = rows + SPH_FANOUT * n_act;
-  uint32_t* lst = lists + fr * DEXR_RESOLVE_MAXACTIVE;
-  uint16_t* clst = clists + fr * DEXR_RESOLVE_MAXCONTACT;
-  unsigned long long* msk = masks + (size_t)fr * S.n_sphere;
-  unsigned char* fl = flags + (size_t)fr * fstride;
-  const int32_t* kinds = obstacle_kinds(prims);
-  const T* xr = A.xref + (inb ? first + fr : 0) * P.n_in;  // (read by working frames alone)
-  const int pchunk = (S.n_pair + SPH_FANOUT - 1) / SPH_FANOUT;  // thread t owns the pairs [t pchunk, (t + 1) pchunk)
-  const int p0 = t * pchunk < S.n_pair ? t * pchunk : S.n_pair, p1 = p0 + pchunk < S.n_pair ? p0 + pchunk : S.n_pair;
-  const int schunk = (S.n_sphere + SPH_FANOUT - 1) / SPH_FANOUT;  // ... and the caller's spheres [t schunk, (t + 1) schunk)
-  const int c0 = t * schunk < S.n_sphere ? t * schunk : S.n_sphere, c1 = c0 + schunk < S.n_sphere ? c0 + schunk : S.n_sphere;
-  for (int c = t; c < P.n_in; c += SPH_FANOUT) {
-    const T v = inb ? A.x0[(first + fr) * P.n_in + c] : T(0);
-    xt[c] = v;
-    xs[c] = v;
-  }
-  part[fr * SPH_FANOUT + t] = 0;
-  if (t == 0) {
-    stopf[fr] = inb ? 0 : 1;  // idle lanes of a ragged last block never start
-    itv[fr] = accf[fr] = stat[fr] = rej[fr] = nact[fr] = ncon[fr] = 0;
-    for (int i = 0; i < RSV_SCALARS; ++i) sc[i] = T(0);
-    sc[RSV_LAM] = A.damping;
-  }
-  __syncthreads();
-  PoseArgs<T> PL = P;  // the walk's view of x: the frames' trial rows in LDS
-  PL.n_in = Y.stride;
-  const T* xl = park + Y.xbase;
-  const T* fixl = A.fixed + first * P.n_fixed;
-  for (int k = 0; k <= A.max_iters; ++k) {
-    if (tid < nl && stopf[tid] == 0) {  // phase A: lane = frame; the walk at the trial, E_pose and E_post; pass 0: the obstacle pose
-      const int lane = tid;
-      T* pa = park + (size_t)lane * Y.stride;
-      T* ca = pa + Y.cbase;
-      const int64_t b = first + lane;
-      if (k == 0) {
-        T* oa = pa + obase;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) oa[i] = O.opos ? O.opos[b * 3 + i] : T(0);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) oa[3 + i] = O.orot ? O.orot[b * 9 + i] : ((i % 4 == 0) ? T(1) : T(0));
-      }
-      T Ep = T(0);
-      for (int l = 0; l < P.n_base; ++l) {  // links on the fixed base: below no joint, but their error and their spheres count
-        const LinkD<T>& L = links[l];
-        if (targets) Ep += resolve_link(L.R, L.p, L.out, b, A, pa + Y.lbase + IK_LINK * l);
-        for (int s = S.link_sph[l]; s < S.link_sph[l + 1]; ++s) sphere_centre(L.R, L.p, spheres[s], ca + 3 * s);
-      }
-      Xf<T> tf;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) tf.R[i] = (i % 4 == 0) ? T(1) : T(0);
-      tf.p[0] = tf.p[1] = tf.p[2] = T(0);
-      int xi = 0;
-      for (int j = 0; j < P.n_joint; ++j) {
-        const JointD<T>& J = joints[j];
-        T a[3];
-        joint_step(J, PL, xl, fixl, (int64_t)lane, slots, nl, lane, tf, a);
-        if (J.src_kind == DEXR_POSE_SRC_X) {
-          T* d = pa + 6 * xi;
-#pragma unroll
-          for (int i = 0; i < 3; ++i) {
-            d[i] = a[i];
-            d[3 + i] = tf.p[i];
-          }
-          ++xi;
-        }
-        for (int l = J.link_begin; l < J.link_end; ++l) {
-          const int s0 = S.link_sph[l], s1 = S.link_sph[l + 1];
-          if (!targets && s0 == s1) continue;
-          const LinkD<T>& L = links[l];
-          T R[9], p[3];
-          link_pose(L, tf, R, p);
-          if (targets) Ep += resolve_link(R, p, L.out, b, A, pa + Y.lbase + IK_LINK * l);
-          for (int s = s0; s < s1; ++s) sphere_centre(R, p, spheres[s], ca + 3 * s);
-        }
-      }
-      T Eq = T(0);
-      if (A.u) {
-        const T* xa = pa + Y.xbase;
-        const T* ra = A.xref + b * P.n_in;
-        for (int c = 0; c < P.n_in; ++c) {
-          const T d = xa[c] - ra[c];
-          Eq = fma(A.u[c] * d, d, Eq);
-        }
-      }
-      pa[Y.sbase + RSV_TPOSE] = Ep;
-      pa[Y.sbase + RSV_TPOST] = Eq;
-    }
-    __syncthreads();
-    const bool work = stopf[fr] == 0;
-    if (work) {  // phase B: a thread per sphere; its pair forces, then its primitives: forces, energies, active flags and masks
-      T e = T(0), eo = T(0);
-      for (int s = t; s < S.n_sphere; s += SPH_FANOUT) {
-        const T cs[3] = {cen[3 * s], cen[3 * s + 1], cen[3 * s + 2]};
-        T f0 = T(0), f1 = T(0), f2 = T(0);
-        const int i1 = S.inc_ptr[s + 1];
-        for (int i = S.inc_ptr[s]; i < i1; ++i) {
-          const uint32_t u = S.inc[i];
-          const int o = u & 127, p = u >> 8;
-          const T d0 = cs[0] - cen[3 * o], d1 = cs[1] - cen[3 * o + 1], d2 = cs[2] - cen[3 * o + 2];
-          const T sp = sqrt(fma(d2, d2, fma(d1, d1, d0 * d0)));
-          T h = A.margin - (sp - rsum[p]);
-          if (h <= T(0)) h = T(0);  // (a comparison: a NaN stays a NaN)
-          const T wh = A.pw ? A.pw[p] * h : h;
-          if (u & SPH_FIRST) {
-            e = fma(wh, h, e);
-            fl[p] = h > T(0) ? 1 : 0;
-          }
-          const T q = sp > T(0) ? wh / sp : wh * (sp * T(0));  // coincident centres: no direction
-          f0 = fma(q, d0, f0);
-          f1 = fma(q, d1, f1);
-          f2 = fma(q, d2, f2);
-        }
-        T yo[3];
-        obstacle_point(po, cs, yo);
-        const T rs = spheres[s].r;
-        T fo[3] = {T(0), T(0), T(0)};  // sum_m w_m h grad sdf_m in the obstacle frame
-        unsigned long long bits = 0;
-        for (int m = 0; m < n_prim; ++m) {
-          T gm[3];
-          const T d = obstacle_sdf(kinds[m], prims[m], yo, gm) - rs;
-          T h = O.omargin - d;
-          if (h <= T(0)) h = T(0);  // (a comparison: a NaN stays a NaN)
-          const T wh = ow ? ow[m] * h : h;
-          eo = fma(wh, h, eo);
-          if (h > T(0)) bits |= 1ull << m;
-#pragma unroll
-          for (int i = 0; i < 3; ++i) fo[i] = fma(wh, gm[i], fo[i]);
-        }
-        T fw[3];
-        obstacle_to_world(po, fo, fw);
-        frc[3 * s] = fma(O.wobs, fw[0], A.wcol * f0);
-        frc[3 * s + 1] = fma(O.wobs, fw[1], A.wcol * f1);
-        frc[3 * s + 2] = fma(O.wobs, fw[2], A.wcol * f2);
-        msk[S.sph_out[s]] = bits;
-      }
-      pk[Y.pebase + t] = e;
-      pk[oebase + t] = eo;
-    }
-    __syncthreads();
-    if (work) {  // phase C: the counts of both lists, and the decision
-      int n = 0;
-      for (int p = p0; p < p1; ++p) n += fl[p];
-      cnt[fr * SPH_FANOUT + t] = n;
-      n = 0;
-      for (int c = c0; c < c1; ++c) n += __popcll(msk[c]);
-      ccnt[fr * SPH_FANOUT + t] = n;
-      if (t == 0) {
-        T Ec = pk[Y.pebase], Eo = pk[oebase];
-        for (int i = 1; i < SPH_FANOUT; ++i) Ec += pk[Y.pebase + i];
-        for (int i = 1; i < SPH_FANOUT; ++i) Eo += pk[oebase + i];
-        Ec *= A.wcol;
-        Eo *= O.wobs;
-        const T Et = ((sc[RSV_TPOSE] + sc[RSV_TPOST]) + Ec) + Eo;
-        const bool acc = k == 0 || Et <= sc[RSV_E];  // (a comparison: a NaN rejects)
-        int st = stat[fr];
-        bool stop = false;
-        if (acc) {
-          T step = T(0);
-          for (int i = 0; i < n_act; ++i) {
-            const int c = act_col[i];
-            const T d = fabs(xt[c] - xs[c]);
-            step = d > step ? d : step;
-            xs[c] = xt[c];
-          }
-          sc[RSV_E] = Et;
-          sc[RSV_POSE] = sc[RSV_TPOSE];
-          sc[RSV_POST] = sc[RSV_TPOST];
-          sc[RSV_COL] = Ec;
-          sc[RSV_OBS] = Eo;
-          if (k > 0) {
-            const T l = sc[RSV_LAM] / T(DEXR_RESOLVE_LAM_DOWN);
-            sc[RSV_LAM] = l > A.damping ? l : A.damping;
-            rej[fr] = 0;
-            if (step <= A.tol) {
-              st |= DEXR_RESOLVE_CONVERGED;
-              stop = true;
-            }
-          }
-        } else {
-          sc[RSV_LAM] *= T(DEXR_RESOLVE_LAM_UP);
-          if (++rej[fr] == DEXR_RESOLVE_MAXREJECT) {
-            st |= DEXR_RESOLVE_STALLED;
-            stop = true;
-          }
-        }
-        itv[fr] = k;
-        accf[fr] = acc ? 1 : 0;
-        stat[fr] = st;
-        if (stop || k == A.max_iters) stopf[fr] = 1;
-      }
-    }
-    __syncthreads();
-    if (work && t == 0) {  // (stat, nact and ncon of a frame are its thread 0's alone until the next barrier)
-      int total = 0, ctotal = 0;
-      for (int u = 0; u < SPH_FANOUT; ++u) {
-        total += cnt[fr * SPH_FANOUT + u];
-        ctotal += ccnt[fr * SPH_FANOUT + u];
-      }
-      if (total > DEXR_RESOLVE_MAXACTIVE) {
-        stat[fr] |= DEXR_RESOLVE_TRUNCATED;
-        total = DEXR_RESOLVE_MAXACTIVE;
-      }
-      if (ctotal > DEXR_RESOLVE_MAXCONTACT) {
-        stat[fr] |= DEXR_RESOLVE_CONTACTS_TRUNCATED;
-        ctotal = DEXR_RESOLVE_MAXCONTACT;
-      }
-      const bool keep = accf[fr] != 0 && stopf[fr] == 0;
-      nact[fr] = keep ? total : 0;
-      ncon[fr] = keep ? ctotal : 0;
-    }
-    bool all = true;  // the block's vote, the same in every thread
-    for (int f = 0; f < nl; ++f) all = all && stopf[f] != 0;
-    if (all) break;
-    const bool go = stopf[fr] == 0;            // the frame goes on: it needs a next trial
-    const bool build = go && accf[fr] != 0;  // ... from a new point: its lists, g and H are formed and kept
-    if (build) {  // phase D: both lists in their orders, then g with the freeze test of its columns
-      int off = 0, coff = 0;
-      for (int u = 0; u < t; ++u) {
-        off += cnt[fr * SPH_FANOUT + u];
-        coff += ccnt[fr * SPH_FANOUT + u];
-      }
-      for (int p = p0; p < p1 && off < DEXR_RESOLVE_MAXACTIVE; ++p)
-        if (fl[p]) lst[off++] = (uint32_t)p;
-      for (int c = c0; c < c1 && coff < DEXR_RESOLVE_MAXCONTACT; ++c) {  // the caller's sphere order, then set order
-        unsigned long long bits = msk[c];
-        const uint32_t s = (uint32_t)sph_in[c];
-        while (bits != 0 && coff < DEXR_RESOLVE_MAXCONTACT) {
-          const uint32_t m = (uint32_t)__ffsll((long long)bits) - 1u;
-          clst[coff++] = (uint16_t)(s | (m << 7));
-          bits &= bits - 1;
-        }
-      }
-      unsigned long long mine = 0;
-      for (int i = t; i < n_act; i += SPH_FANOUT) {
-        const int c = act_col[i];
-        const uint32_t r = act_rng[i];
-        T s = targets ? ik_g_entry(r, ents, pk, Y.lbase) : T(0);
-        if (A.u) s = fma(A.u[c], xr[c] - xs[c], s);
-        s += resolve_force_entry(r, ents, S.link_sph, pk, cen, frc);  // (the forces carry w_col and w_obs)
-        if (A.lo) {
-          const T xc = xs[c];
-          if ((xc <= A.lo[c] && s < T(0)) || (xc >= A.hi[c] && s > T(0))) {
-            mine |= 1ull << i;
-            s = T(0);
-          }
-        }
-        gs[i] = s;
-      }
-      part[fr * SPH_FANOUT + t] = mine;
-    }
-    __syncthreads();
-    unsigned long long frozen = 0;  // of the last accepted point: a frame that rejected keeps its partial masks
-    for (int u = 0; u < SPH_FANOUT; ++u) frozen |= part[fr * SPH_FANOUT + u];
-    if (build) {
-      for (int e = t; e < n_tri; e += SPH_FANOUT) {  // a frozen column's row and column of H are the identity's
-        const uint2 d = tri[e];
-        const int i = d.x & 63, j = d.x >> 6;
-        T h;
-        if (((frozen >> i) | (frozen >> j)) & 1ull) {
-          h = i == j ? T(1) : T(0);
-        } else {
-          h = targets ? ik_h_entry(d, ents, pk, Y.lbase) : T(0);
-          if (i == j && A.u) h += A.u[act_col[i]];
-        }
-        Hs[e] = h;
-      }
-    }
-    int nmax = 0, cmax = 0;  // the block's largest lists: the same in every thread
-    for (int f = 0; f < nl; ++f) {
-      nmax = nact[f] > nmax ? nact[f] : nmax;
-      cmax = ncon[f] > cmax ? ncon[f] : cmax;
-    }
-    const int mine_n = nact[fr], mine_c = ncon[fr];  // (0 unless `build`)
-    nmax = (nmax + SPH_FANOUT - 1) / SPH_FANOUT * SPH_FANOUT;  // whole chunks: the contacts start at a chunk boundary of their own
-    for (int base = 0; base < nmax + cmax; base += SPH_FANOUT) {  // the curvature, sixteen rows at a time: the pairs' grad d_p, then
-      const bool pairs = base < nmax;                               // the contacts' grad d_sm (the same choice in every thread)
-      const int at = pairs ? base : base - nmax;
-      const int have = pairs ? mine_n : mine_c;
-      if (at + t < have) {
-        T n[3], w;
-        int si, sj;
-        if (pairs) {
-          const uint32_t p = lst[at + t], ps = pair_sph[p];
-          si = ps & 127, sj = (ps >> 7) & 127;
-          const T d[3] = {cen[3 * si] - cen[3 * sj], cen[3 * si + 1] - cen[3 * sj + 1], cen[3 * si + 2] - cen[3 * sj + 2]};
-          const T sp = sqrt(fma(d[2], d[2], fma(d[1], d[1], d[0] * d[0])));
-          const T inv = sp > T(0) ? T(1) / sp : T(0);
-#pragma unroll
-          for (int i = 0; i < 3; ++i) n[i] = d[i] * inv;
-          w = A.pw ? A.wcol * A.pw[p] : A.wcol;
-        } else {
-          const uint32_t cm = clst[at + t];
-          const int m = cm >> 7;
-          si = cm & 127, sj = -1;  // one sphere: no link holds sphere -1
-          T yo[3], gm[3];
-          obstacle_point(po, cen + 3 * si, yo);
-          (void)obstacle_sdf(kinds[m], prims[m], yo, gm);
-          obstacle_to_world(po, gm, n);
-          w = ow ? O.wobs * ow[m] : O.wobs;
-        }
-        T* row = rows + t * n_act;
-        for (int i = 0; i < n_act; ++i)
-          row[i] = ((frozen >> i) & 1ull) ? T(0) : resolve_row_entry(act_rng[i], ents, S.link_sph, pk, cen, si, sj, n);
-        rw[t] = w;
-      }
-      __syncthreads();
-      const int nk = have - at < SPH_FANOUT ? have - at : SPH_FANOUT;
-      if (nk > 0) {
-        for (int e = t; e < n_tri; e += SPH_FANOUT) {
-          const uint2 dd = tri[e];
-          const int i = dd.x & 63, j = dd.x >> 6;
-          T h = Hs[e];
-          for (int q = 0; q < nk; ++q) h = fma(rw[q] * rows[q * n_act + i], rows[q * n_act + j], h);
-          Hs[e] = h;
-        }
-      }
-      __syncthreads();
-    }
-    if (go) {  // phase E: the kept system with the frame's lam
-      const T lam = sc[RSV_LAM];
-      for (int e = t; e < n_tri; e += SPH_FANOUT) {
-        const uint2 d = tri[e];
-        const int i = d.x & 63, j = d.x >> 6;
-        H[e] = (i == j && !((frozen >> i) & 1ull)) ? Hs[e] + lam : Hs[e];
-      }
-      for (int i = t; i < n_act; i += SPH_FANOUT) g[i] = gs[i];
-    }
-    __syncthreads();
-    ik_factor_solve(H, g, y, dg, n_act, t, go);
-    if (go) {  // limit the step, move, clamp: by comparisons, a NaN stays a NaN
-      T scale = T(1);
-      if (A.max_step > T(0)) {
-        T m = T(0);
-        for (int i = 0; i < n_act; ++i) {
-          const T a = fabs(g[i]);
-          m = a > m ? a : m;
-        }
-        if (m > A.max_step) scale = A.max_step / m;
-      }
-      for (int i = t; i < n_act; i += SPH_FANOUT) {
-        const int c = act_col[i];
-        T v = xs[c] + g[i] * scale;
-        if (A.lo) {
-          const T l = A.lo[c], h = A.hi[c];
-          v = v < l ? l : (v > h ? h : v);
-        }
-        xt[c] = v;
-      }
-    }
-    __syncthreads();
-  }
-  if (inb) {
-    T* o = A.x_out + (first + fr) * P.n_in;
-    for (int c = t; c < P.n_in; c += SPH_FANOUT) o[c] = xs[c];
-    if (t == 0) {
-      if (A.iters_out) A.iters_out[first + fr] = itv[fr];
-      if (A.status_out) A.status_out[first + fr] = stat[fr];
-      if (A.e_out) {
-        T* eo = A.e_out + (first + fr) * 4;
-        eo[0] = sc[RSV_POSE];
-        eo[1] = sc[RSV_POST];
-        eo[2] = sc[RSV_COL];
-        eo[3] = sc[RSV_OBS];
-      }
-    }
-  }
+  const ResolveModel<T> M = {joints, links, spheres, rsum, S, pair_sph, ents, act_rng, act_col, tri, n_act, n_act * (n_act + 1) / 2};
+  const ObstacleContacts<T> C = {prims, obstacle_kinds(prims), ow, n_prim, nullptr, nullptr};
+  resolve_contact_loop<T>(pose_lds, M, P, sph_in, Y, obase, oebase, fstride, A, O, C);
 }
 
-// the argument rules of both entry points: those of check_resolve_call and the obstacle side's; < 0 error, 1 nothing to do, 0 go on
-int check_resolve_obstacle_call(const dexr_sphere_model* sm, const dexr_obstacle_set* os, double omargin, double wobs, int64_t B, const void* x0,
-                                const void* fixed, int32_t n_target, const void* tp, const void* tr, const void* wl, const void* wa, double margin,
-                                double wcol, const void* lo, const void* hi, double damping, double max_step, double tol, int32_t max_iters,
-                                const void* x_out) {
+// the argument rules of the four contact entry points: the obstacle side's, then those of check_resolve_call; < 0 error, 1 nothing
+// to do, 0 go on.  obstacle: the set or the grid, no_obstacle: what to say where it is NULL
+int check_resolve_contact_call(const dexr_sphere_model* sm, const void* obstacle, const char* no_obstacle, double omargin, double wobs, int64_t B,
+                               const void* x0, const void* fixed, int32_t n_target, const void* tp, const void* tr, const void* wl, const void* wa,
+                               double margin, double wcol, const void* lo, const void* hi, double damping, double max_step, double tol,
+                               int32_t max_iters, const void* x_out) {
   const double big = 1.7976931348623157e308;
   if (!sm) return dexr_set_error(DEXR_ERR_INVALID, "null sphere model");
-  if (!os) return dexr_set_error(DEXR_ERR_INVALID, "null obstacle set");
+  if (!obstacle) return dexr_set_error(DEXR_ERR_INVALID, "%s", no_obstacle);
   if (!(omargin >= 0.0) || omargin > big) return dexr_set_error(DEXR_ERR_INVALID, "obstacle_margin must be finite and >= 0, got %g", omargin);
   if (!(wobs >= 0.0) || wobs > big) return dexr_set_error(DEXR_ERR_INVALID, "obstacle_weight must be finite and >= 0, got %g", wobs);
   return check_resolve_call(sm, B, x0, fixed, n_target, tp, tr, wl, wa, margin, wcol, lo, hi, damping, max_step, tol, max_iters, x_out);
+}
+
+// the layout of a contact kernel's frame: behind the scalars of ResolveLayout the obstacle pose, then sixteen partial energies
+template <typename T>
+ResolveLayout resolve_contact_layout(const dexr_sphere_model* sm, int n_target, int* obase, int* oebase) {
+  ResolveLayout Y = resolve_layout<T>(sm, n_target);
+  *obase = Y.sbase + RSV_SCALARS, *oebase = *obase + OBS_POSE;
+  Y.stride = (*oebase + SPH_FANOUT) | 1;
+  return Y;
 }
 
 template <typename T>
 int launch_resolve_obstacles(const dexr_sphere_model* sm, const dexr_obstacle_set* os, int64_t B, ResolveArgs<T> A, const ResolveObstacleArgs<T>& O,
                              const T* ow, hipStream_t st) {
   const dexr_pose_model* m = sm->pose;
-  ResolveLayout Y = resolve_layout<T>(sm, A.n_target);
-  const int obase = Y.sbase + RSV_SCALARS, oebase = obase + OBS_POSE;  // behind the scalars: the pose, sixteen partial energies
-  Y.stride = (oebase + SPH_FANOUT) | 1;
-  const int fstride = (sm->n_pair + 3) & ~3;
+  int obase, oebase;
+  const ResolveLayout Y = resolve_contact_layout<T>(sm, A.n_target, &obase, &oebase);
   // (the formula of include/dexr_resolve_obstacles.h)
-  const size_t per_frame = SPH_FANOUT * sizeof(unsigned long long) + (size_t)sm->n_sphere * sizeof(unsigned long long) +
-                           ((size_t)m->h.n_slot * 12 + (size_t)Y.stride) * sizeof(T) + (DEXR_RESOLVE_MAXACTIVE + SPH_FANOUT + 6) * sizeof(int32_t) +
-                           (SPH_FANOUT + 1) * sizeof(int32_t) + DEXR_RESOLVE_MAXCONTACT * sizeof(uint16_t) + (size_t)fstride;
-  int nl = SPH_FRAMES;
-  while (nl > 1 && per_frame * nl > 64 * 1024) nl /= 2;
-  if (per_frame * nl > 64 * 1024)
-    return dexr_set_error(DEXR_ERR_UNSUPPORTED, "the sphere model needs %zu B of LDS per frame: one frame does not fit a block", per_frame);
-  const int64_t blocks = (B + nl - 1) / nl;
-  if (blocks > 0x7fffffffLL) return dexr_set_error(DEXR_ERR_INVALID, "batch too large for one launch");
+  const size_t per_frame = resolve_lds_bytes<T>(sm, Y, ObstacleContacts<T>::head_words(sm->n_sphere),
+                                                RESOLVE_CONTACT_COUNTS + ObstacleContacts<T>::tail_bytes(sm->n_sphere));
+  int nl;
+  int64_t blocks;
+  if (const int rc = resolve_launch_shape(per_frame, B, &nl, &blocks)) return rc;
   const SphereIndex S = {sm->link_sph, sm->sph_out, sm->inc_ptr, sm->inc, sm->n_sphere, sm->n_pair};
   if (!A.xref) A.xref = A.x0;
   hipLaunchKernelGGL(pose_resolve_obstacle_kernel<T>, dim3((unsigned)blocks), dim3(nl * SPH_FANOUT), per_frame * nl, st,
                      (const JointD<T>*)tables_of<T>(m).joints, (const LinkD<T>*)tables_of<T>(m).links, args_of<T>(m, B),
                      (const SphereD<T>*)sphere_tables_of<T>(sm).spheres, (const T*)sphere_tables_of<T>(sm).rsum, S, (const int32_t*)sm->sph_in,
                      (const uint32_t*)sm->pair_sph, (const JacEnt*)m->jac_ents, (const uint32_t*)m->ik_act_rng, (const int32_t*)m->ik_act_col,
-                     (const uint2*)m->ik_tri, obstacle_table_of<T>(os), ow, os->n_prim, m->n_jx, m->n_act, Y, obase, oebase, fstride, A, O);
+                     (const uint2*)m->ik_tri, obstacle_table_of<T>(os), ow, os->n_prim, m->n_jx, m->n_act, Y, obase, oebase,
+                     (sm->n_pair + 3) & ~3, A, O);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return dexr_set_error(DEXR_ERR_HIP, "obstacle resolve kernel launch failed: %s", hipGetErrorString(e));
   return DEXR_OK;
@@ -520,9 +328,9 @@ int dexr_sphere_resolve_obstacles_dev(const dexr_sphere_model* m, int64_t B, con
                                       int32_t max_iters, const dexr_obstacle_set* obstacles, const float* obstacle_pos, const float* obstacle_rot,
                                       float obstacle_margin, float obstacle_weight, const float* prim_weight, float* x_out, int32_t* iters_out,
                                       float* energy_out, int32_t* status_out, void* stream) {
-  const int c = check_resolve_obstacle_call(m, obstacles, (double)obstacle_margin, (double)obstacle_weight, B, x0, fixed, n_target, target_pos,
-                                            target_rot, pos_weight, rot_weight, (double)margin, (double)collision_weight, lo, hi, (double)damping,
-                                            (double)max_step, (double)tol, max_iters, x_out);
+  const int c = check_resolve_contact_call(m, obstacles, "null obstacle set", (double)obstacle_margin, (double)obstacle_weight, B, x0, fixed,
+                                           n_target, target_pos, target_rot, pos_weight, rot_weight, (double)margin, (double)collision_weight, lo,
+                                           hi, (double)damping, (double)max_step, (double)tol, max_iters, x_out);
   if (c) return c < 0 ? c : DEXR_OK;
   const ResolveArgs<float> A = {x0, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi,
                                 margin, collision_weight, damping, max_step, tol, n_target, max_iters, x_out, iters_out, energy_out, status_out};
@@ -537,45 +345,22 @@ int dexr_sphere_resolve_obstacles(const dexr_sphere_model* m, int64_t B, const d
                                   int32_t max_iters, const dexr_obstacle_set* obstacles, const double* obstacle_pos, const double* obstacle_rot,
                                   double obstacle_margin, double obstacle_weight, const double* prim_weight, double* x_out, int32_t* iters_out,
                                   double* energy_out, int32_t* status_out) {
-  const int c = check_resolve_obstacle_call(m, obstacles, obstacle_margin, obstacle_weight, B, x0, fixed, n_target, target_pos, target_rot,
-                                            pos_weight, rot_weight, margin, collision_weight, lo, hi, damping, max_step, tol, max_iters, x_out);
+  const int c = check_resolve_contact_call(m, obstacles, "null obstacle set", obstacle_margin, obstacle_weight, B, x0, fixed, n_target,
+                                           target_pos, target_rot, pos_weight, rot_weight, margin, collision_weight, lo, hi, damping, max_step,
+                                           tol, max_iters, x_out);
   if (c) return c < 0 ? c : DEXR_OK;
-  const dexr_pose_model* pm = m->pose;
-  const size_t nx = (size_t)B * pm->h.n_in * sizeof(double), nf = (size_t)B * pm->h.n_fixed * sizeof(double);
-  const size_t nw = (size_t)B * n_target * sizeof(double), nb = (size_t)pm->h.n_in * sizeof(double), n1 = (size_t)B * sizeof(double);
-  DevBuf dx, dfix, dref, du, dp, dr, dwl, dwa, dpw, dlo, dhi, dop, dor, dow, dout, dit, den, dst;
-  POSE_HIP(dx.put(x0, nx));
-  POSE_HIP(dfix.put(fixed, nf));
-  if (x_ref) POSE_HIP(dref.put(x_ref, nx));
-  if (posture_weight) POSE_HIP(du.put(posture_weight, nb));
-  if (target_pos) POSE_HIP(dp.put(target_pos, 3 * nw));
-  if (target_rot) POSE_HIP(dr.put(target_rot, 9 * nw));
-  if (pos_weight) POSE_HIP(dwl.put(pos_weight, nw));
-  if (rot_weight) POSE_HIP(dwa.put(rot_weight, nw));
-  if (pair_weight) POSE_HIP(dpw.put(pair_weight, (size_t)m->n_pair * sizeof(double)));
-  if (lo) POSE_HIP(dlo.put(lo, nb));
-  if (hi) POSE_HIP(dhi.put(hi, nb));
-  if (obstacle_pos) POSE_HIP(dop.put(obstacle_pos, 3 * n1));
-  if (obstacle_rot) POSE_HIP(dor.put(obstacle_rot, 9 * n1));
+  ResolveRoundTrip D;
+  ResolveArgs<double> A;
+  if (const int rc = D.up(m, B, x0, fixed, x_ref, posture_weight, n_target, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi))
+    return rc;
+  DevBuf dop, dor, dow;
+  if (obstacle_pos) POSE_HIP(dop.put(obstacle_pos, (size_t)B * 3 * sizeof(double)));
+  if (obstacle_rot) POSE_HIP(dor.put(obstacle_rot, (size_t)B * 9 * sizeof(double)));
   if (prim_weight) POSE_HIP(dow.put(prim_weight, (size_t)obstacles->n_prim * sizeof(double)));
-  POSE_HIP(dout.put(nullptr, nx));
-  POSE_HIP(dit.put(nullptr, (size_t)B * sizeof(int32_t)));
-  POSE_HIP(den.put(nullptr, 4 * n1));
-  POSE_HIP(dst.put(nullptr, (size_t)B * sizeof(int32_t)));
-  const ResolveArgs<double> A = {(const double*)dx.p,  (const double*)dfix.p, (const double*)dref.p, (const double*)du.p,  (const double*)dp.p,
-                                 (const double*)dr.p,  (const double*)dwl.p,  (const double*)dwa.p,  (const double*)dpw.p, (const double*)dlo.p,
-                                 (const double*)dhi.p, margin,                collision_weight,      damping,              max_step,
-                                 tol,                  n_target,              max_iters,             (double*)dout.p,      (int32_t*)dit.p,
-                                 (double*)den.p,       (int32_t*)dst.p};
+  if (const int rc = D.out(B, 4, margin, collision_weight, damping, max_step, tol, n_target, max_iters, &A)) return rc;
   const ResolveObstacleArgs<double> O = {(const double*)dop.p, (const double*)dor.p, obstacle_margin, obstacle_weight};
-  const int rc = launch_resolve_obstacles<double>(m, obstacles, B, A, O, (const double*)dow.p, nullptr);
-  if (rc) return rc;
-  POSE_HIP(hipDeviceSynchronize());
-  if (nx) POSE_HIP(hipMemcpy(x_out, dout.p, nx, hipMemcpyDeviceToHost));
-  if (iters_out) POSE_HIP(hipMemcpy(iters_out, dit.p, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (energy_out) POSE_HIP(hipMemcpy(energy_out, den.p, 4 * n1, hipMemcpyDeviceToHost));
-  if (status_out) POSE_HIP(hipMemcpy(status_out, dst.p, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return DEXR_OK;
+  if (const int rc = launch_resolve_obstacles<double>(m, obstacles, B, A, O, (const double*)dow.p, nullptr)) return rc;
+  return D.down(x_out, iters_out, energy_out, status_out);
 }
 
 }  // extern "C"

@@ -15,14 +15,6 @@ joint limits; 8 and 16 trial steps, tol = 0.
 HIP events around `--reps` back-to-back runs after `--warmup`; the variants alternate inside a round so both see the same box;
 the MEDIAN over `--rounds` rounds is reported, the rounds beside it.
 
-THE TWO WAYS OF FORMING THE PAIR CURVATURE.  The library is built with the rank-16 update (sixteen rows grad d_p staged in LDS at
-a time); csrc/dexr_resolve.hpp keeps the other way -- every entry of H walks the active list -- behind
--DDEXR_RESOLVE_CURVATURE_WALK=1.  Build that variant beside the library and time (a) with it:
-
-    DEXR_EXTRA_FLAGS=-DDEXR_RESOLVE_CURVATURE_WALK=1 DEXR_BUILD_DIR=variants/walk DEXR_LIB_OUT=variants/walk/libdexr.so \\
-        python -m dex_retargeting_amd._build
-    DEXR_LIB=variants/walk/libdexr.so python tools/resolve_probe.py --no-torch
-
     python tools/resolve_probe.py [--reps 5] [--rounds 5] [--iters 8,16] [--batch 65536] [--no-torch]
 """
 import argparse
