@@ -91,12 +91,21 @@ SDF_GRID_EXPORTS = ["dexr_sdf_grid_create", "dexr_sdf_grid_destroy", "dexr_sdf_g
 SDF_GRID_MIN_DIM, SDF_GRID_MAX_DIM, SDF_GRID_MAX_SAMPLES = 2, 1024, 1 << 24  # DEXR_SDF_GRID_*
 # include/dexr_resolve_grid.h (the posture solve with the grid term, iterated inside one kernel): a list of its own
 RESOLVE_GRID_EXPORTS = ["dexr_sphere_resolve_grid_dev", "dexr_sphere_resolve_grid"]
+# include/dexr_resolve_scene.h (the posture solve against several posed bodies, sets and grids, in one kernel): a list of its own
+RESOLVE_SCENE_EXPORTS = ["dexr_sphere_resolve_scene_dev", "dexr_sphere_resolve_scene"]
+SCENE_MAXBODY = 4  # DEXR_SCENE_MAXBODY
 # include/dexr_mesh_sdf.h (signed distances of points and of grid samples to a triangle mesh, brute force): a list of its own
 MESH_SDF_EXPORTS = ["dexr_mesh_create", "dexr_mesh_destroy", "dexr_mesh_info", "dexr_mesh_distances_dev", "dexr_mesh_distances",
                     "dexr_mesh_sample_grid_dev", "dexr_mesh_sample_grid"]
 MESH_MAX_VERTICES, MESH_MAX_TRIANGLES = 1 << 20, 1 << 20  # DEXR_MESH_MAX_*
 MESH_TILE, MESH_BLOCK_POINTS, MESH_PAIRS_PER_LAUNCH = 256, 512, 1 << 34  # DEXR_MESH_TILE, DEXR_MESH_BLOCK_POINTS, DEXR_MESH_PAIRS_PER_LAUNCH
 UNIQUE_ID_BYTES = 128
+
+
+class SceneBodyRecord(C.Structure):
+    """dexr_scene_body: one body of a scene as the two entry points of include/dexr_resolve_scene.h read it."""
+    _fields_ = [("set", C.c_void_p), ("grid", C.c_void_p), ("pos", C.c_void_p), ("rot", C.c_void_p), ("prim_weight", C.c_void_p),
+                ("margin", C.c_double), ("weight", C.c_double)]
 
 
 def load() -> C.CDLL:
@@ -228,6 +237,12 @@ def load() -> C.CDLL:
     lib.dexr_sphere_resolve_grid.argtypes = [vp, i64, f64p, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, C.c_double, f64p,
                                              f64p, f64p, C.c_double, C.c_double, C.c_double, C.c_int32, vp, f64p, f64p, C.c_double, C.c_double,
                                              f64p, i32p, f64p, i32p]
+    bodyp = C.POINTER(SceneBodyRecord)
+    lib.dexr_sphere_resolve_scene_dev.argtypes = [vp, i64, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, C.c_float,
+                                                  C.c_float, C.c_float, C.c_int32, C.c_int32, bodyp, vp, vp, vp, vp, vp, vp]
+    lib.dexr_sphere_resolve_scene.argtypes = [vp, i64, f64p, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, C.c_double, f64p,
+                                              f64p, f64p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, bodyp, f64p, i32p, f64p,
+                                              f64p, i32p]
     lib.dexr_mesh_create.argtypes = [C.c_int32, f64p, C.c_int32, i32p, C.POINTER(vp)]
     lib.dexr_mesh_destroy.argtypes = [vp]
     lib.dexr_mesh_destroy.restype = None
@@ -1060,6 +1075,67 @@ class SphereModel:
             float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi), float(damping), float(max_step), float(tol), int(max_iters),
             grid.handle, d(pos), d(rot), float(om), float(obstacle_weight), d(x), _ptr(iters, C.c_int32), d(energy), _ptr(status, C.c_int32)))
         return out
+
+    # the posture solve against a scene of several bodies (include/dexr_resolve_scene.h) --------------------------
+    @staticmethod
+    def _scene_records(bodies, margin, address):
+        """the dexr_scene_body array of `bodies`: (obstacle, pos, rot, margin or None (the solve's), weight, prim_weight) each, obstacle
+        an ObstacleSet or an SdfGrid of this module; `address` turns pos, rot and prim_weight into addresses (0 / None: NULL)."""
+        bodies = list(bodies)
+        rec = (SceneBodyRecord * max(len(bodies), 1))()
+        for r, (obstacle, pos, rot, bmargin, weight, prim_weight) in zip(rec, bodies):
+            if isinstance(obstacle, ObstacleSet):
+                r.set = obstacle.handle.value
+            elif isinstance(obstacle, SdfGrid):
+                r.grid = obstacle.handle.value
+            elif obstacle is not None:
+                raise ValueError(f"a body's obstacle must be an _lib.ObstacleSet or an _lib.SdfGrid, got {type(obstacle).__name__}")
+            r.pos, r.rot, r.prim_weight = address(pos), address(rot), address(prim_weight)
+            r.margin, r.weight = float(margin if bmargin is None else bmargin), float(weight)
+        return len(bodies), (rec if bodies else None)
+
+    def resolve_scene_dev(self, bodies, B: int, x0_ptr: int, fixed_ptr: int, margin: float, damping: float, max_iters: int, x_ptr: int,
+                          iters_ptr: int = 0, energy_ptr: int = 0, status_ptr: int = 0, x_ref_ptr: int = 0, posture_weight_ptr: int = 0,
+                          n_target: int = 0, target_pos_ptr: int = 0, target_rot_ptr: int = 0, pos_weight_ptr: int = 0,
+                          rot_weight_ptr: int = 0, collision_weight: float = 1.0, pair_weight_ptr: int = 0, lo_ptr: int = 0, hi_ptr: int = 0,
+                          tol: float = 0.0, max_step: float = 0.0, body_energy_ptr: int = 0, stream: int = 0):
+        """the arguments of resolve_dev, and bodies: 1 .. SCENE_MAXBODY of (obstacle: ObstacleSet or SdfGrid, pos_ptr (B, 3) or 0,
+        rot_ptr (B, 3, 3) or 0, margin or None (the solve's), weight, prim_weight_ptr (n_prim) or 0) -> x (B, n_in), iters (B) int32,
+        energy (B, 4), status (B) int32, body_energy (B, n_body), each of the last four or 0 (dexr_sphere_resolve_scene_dev)."""
+        n_body, rec = self._scene_records(bodies, margin, lambda a: a or None)
+        check(load().dexr_sphere_resolve_scene_dev(
+            self._h, B, x0_ptr or None, fixed_ptr or None, x_ref_ptr or None, posture_weight_ptr or None, int(n_target), target_pos_ptr or None,
+            target_rot_ptr or None, pos_weight_ptr or None, rot_weight_ptr or None, float(margin), float(collision_weight), pair_weight_ptr or None,
+            lo_ptr or None, hi_ptr or None, float(damping), float(max_step), float(tol), int(max_iters), n_body, rec, x_ptr or None,
+            iters_ptr or None, energy_ptr or None, body_energy_ptr or None, status_ptr or None, stream or None))
+
+    def resolve_scene(self, bodies, x0, margin=None, damping=None, max_iters=None, fixed=None, x_ref=None, posture_weight=None,
+                      target_pos=None, target_rot=None, pos_weight=None, rot_weight=None, collision_weight: float = 1.0, pair_weight=None,
+                      lo=None, hi=None, tol: float = 0.0, max_step: float = 0.0, n_target=None):
+        """-> (x (B, n_in) float64, iters (B) int32, energy (B, 4) float64, status (B) int32, body_energy (B, n_body) float64)
+        (dexr_sphere_resolve_scene): the arguments of `resolve`, and bodies: 1 .. SCENE_MAXBODY of (obstacle: ObstacleSet or SdfGrid,
+        pos (B, 3) or None, rot (B, 3, 3) or None, margin or None (the solve's), weight, prim_weight (n_prim) or None)."""
+        (x0, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi), n_target, B, out = \
+            self._resolve_host(x0, margin, damping, max_iters, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight,
+                               pair_weight, lo, hi, n_target, 4)
+        x, iters, energy, status = out
+        kept = []  # the float64 copies the records point into
+        for b, (obstacle, pos, rot, bmargin, weight, prim_weight) in enumerate(bodies):
+            pos, rot = self._host_pose(B, pos, rot)
+            if prim_weight is not None:
+                prim_weight = np.ascontiguousarray(prim_weight, dtype=np.float64)
+                want = (getattr(obstacle, "n_prim", None),)
+                if want[0] is not None and prim_weight.shape != want:
+                    raise ValueError(f"prim_weight of body {b} must have shape {want}, got {prim_weight.shape}")
+            kept.append((obstacle, pos, rot, bmargin, weight, prim_weight))
+        n_body, rec = self._scene_records(kept, margin, lambda a: None if a is None else a.ctypes.data)
+        body_energy = np.zeros((B, n_body), dtype=np.float64)
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        check(load().dexr_sphere_resolve_scene(
+            self._h, B, d(x0), d(fixed), d(x_ref), d(posture_weight), n_target, d(target_pos), d(target_rot), d(pos_weight), d(rot_weight),
+            float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi), float(damping), float(max_step), float(tol), int(max_iters),
+            n_body, rec, d(x), _ptr(iters, C.c_int32), d(energy), d(body_energy), _ptr(status, C.c_int32)))
+        return x, iters, energy, status, body_energy
 
 
 class ObstacleSet:

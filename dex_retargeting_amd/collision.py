@@ -1121,8 +1121,140 @@ def robot_resolve_grid_collisions(robot, qpos0, sphere_set: SphereSet, grid: Sdf
                              collision_weight, pair_weight, link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits)
 
 
+# ---- the posture solve against a scene: several posed bodies, sets and grids, in one launch (include/dexr_resolve_scene.h) ---------------
+class SceneBody:
+    """One body of a scene, plain data: `obstacle` an ObstacleSet or an SdfGrid; pos (B, 3), rot (B, 3, 3) float32 tensors or None
+    (a world-fixed body: zero translation / the identity); margin a finite Python float >= 0 or None (the solve's `margin`); weight a
+    finite Python float >= 0; prim_weight (M,) float32 >= 0 or None (1), an ObstacleSet alone.  Nothing is checked here: the solve
+    that takes the body checks it."""
+
+    def __init__(self, obstacle, pos=None, rot=None, margin=None, weight=1.0, prim_weight=None):
+        self.obstacle, self.pos, self.rot, self.margin, self.weight, self.prim_weight = obstacle, pos, rot, margin, weight, prim_weight
+
+    def __repr__(self):
+        return (f"SceneBody({self.obstacle!r}, pos={'None' if self.pos is None else 'given'}, rot={'None' if self.rot is None else 'given'}, "
+                f"margin={self.margin!r}, weight={self.weight!r}, prim_weight={'None' if self.prim_weight is None else 'given'})")
+
+
+def _scene_rules(x0, bodies):
+    """The argument rules of the bodies that look at no device: the list, then per body the type, the scalars, then types, dtypes
+    and shapes of its tensors.  Returns the tensors by name, for the device rule that comes last."""
+    import torch
+
+    if isinstance(bodies, SceneBody) or not isinstance(bodies, (list, tuple)):
+        raise ValueError("bodies must be a list of collision.SceneBody")
+    if not 1 <= len(bodies) <= _lib.SCENE_MAXBODY:
+        raise ValueError(f"a scene has 1..{_lib.SCENE_MAXBODY} bodies, got {len(bodies)}")
+    B = x0.shape[0] if isinstance(x0, torch.Tensor) and x0.ndim == 2 else None
+    named = []
+    for b, body in enumerate(bodies):
+        if not isinstance(body, SceneBody):
+            raise ValueError(f"bodies[{b}] must be a collision.SceneBody, got {type(body).__name__}")
+        if not isinstance(body.obstacle, (ObstacleSet, SdfGrid)):
+            raise ValueError(f"bodies[{b}].obstacle must be a collision.ObstacleSet or a collision.SdfGrid, got {type(body.obstacle).__name__}")
+        grid = isinstance(body.obstacle, SdfGrid)
+        if grid and body.prim_weight is not None:
+            raise ValueError(f"bodies[{b}] is an SdfGrid and has a prim_weight: a grid has no primitives to weigh")
+        w, m = body.weight, body.margin
+        if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < 0:
+            raise ValueError(f"bodies[{b}].weight must be a finite Python float >= 0, got {w!r}")
+        if m is not None and (isinstance(m, bool) or not isinstance(m, (int, float)) or not math.isfinite(m) or m < 0):
+            raise ValueError(f"bodies[{b}].margin must be a finite Python float >= 0 or None (margin), got {m!r}")
+        mine = [(n, t, s) for n, t, s in ((f"bodies[{b}].pos", body.pos, (B, 3)), (f"bodies[{b}].rot", body.rot, (B, 3, 3))) if t is not None]
+        if body.prim_weight is not None:
+            mine.append((f"bodies[{b}].prim_weight", body.prim_weight, (body.obstacle.n_prim,)))
+        for name, t, _ in mine:
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor")
+        for name, t, _ in mine:
+            if t.dtype != torch.float32:
+                raise ValueError(f"{name} must be float32, got {t.dtype}")
+        for name, t, shape in mine:
+            if (B is not None or shape[0] is not None) and tuple(t.shape) != shape:
+                raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        named += [(n, t) for n, t, _ in mine]
+    return named
+
+
+def _resolve_scene(model_of, n_in, n_fixed, kin, robot, x0, what, fixed_qpos, sphere_set, bodies, margin, damping, max_iters, posture_weight,
+                   q_ref, collision_weight, pair_weight, link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits,
+                   body_energy):
+    """every rule (those of `_resolve`, then the bodies'), then one model and one launch."""
+    import torch
+
+    named = _resolve_rules(n_in, x0, sphere_set, damping, max_iters, posture_weight, q_ref, collision_weight, link_names, target_pos,
+                           target_rot, pos_weight, rot_weight, tol, max_step, limits)
+    for n in link_names or ():
+        kin.body_frame_index(n)  # ValueError on an unknown link
+    named = named + _scene_rules(x0, bodies)
+    pairs = _check(n_in, n_fixed, kin, robot, x0, fixed_qpos, sphere_set, what, margin, pair_weight, penalty=True)  # (ends with the device)
+    for name, t in named:
+        if t.device != x0.device:
+            raise ValueError(f"{name} is on {t.device}, {what} on {x0.device}: all tensors must be on one CUDA device")
+    B, nb = x0.shape[0], len(bodies)
+    xc, fixed = _inputs(x0, fixed_qpos)
+    c = lambda a: None if a is None else a.detach().contiguous()  # noqa: E731
+    xr, tp, tr, wl, wa, pw = (c(a) for a in (q_ref, target_pos, target_rot, pos_weight, rot_weight, pair_weight))
+    held = [(c(body.pos), c(body.rot), c(body.prim_weight)) for body in bodies]  # (alive until the launch is enqueued)
+    lo, hi = (None, None) if limits is None else (limits.detach()[:, 0].contiguous(), limits.detach()[:, 1].contiguous())
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    with torch.cuda.device(x0.device):
+        if isinstance(posture_weight, torch.Tensor):
+            u = c(posture_weight)
+        else:
+            u = None if not posture_weight else torch.full((n_in,), float(posture_weight), dtype=torch.float32, device=x0.device)
+        model = model_of(sphere_set, pairs, tuple(link_names or ()))
+        q = torch.empty((B, model.n_in), dtype=torch.float32, device=x0.device)
+        iters = torch.empty((B,), dtype=torch.int32, device=x0.device)
+        energy = torch.empty((B, 4), dtype=torch.float32, device=x0.device)
+        status = torch.empty((B,), dtype=torch.int32, device=x0.device)
+        be = torch.empty((B, nb), dtype=torch.float32, device=x0.device) if body_energy else None
+        if B > 0:
+            dev = torch.cuda.current_device()
+            recs = [(body.obstacle.device_grid(dev) if isinstance(body.obstacle, SdfGrid) else body.obstacle.device_set(dev), ptr(p), ptr(r),
+                     None if body.margin is None else float(body.margin), float(body.weight), ptr(w)) for body, (p, r, w) in zip(bodies, held)]
+            model.resolve_scene_dev(recs, B, xc.data_ptr(), ptr(fixed), float(margin), float(damping), int(max_iters), q.data_ptr(),
+                                    iters.data_ptr(), energy.data_ptr(), status.data_ptr(), x_ref_ptr=ptr(xr), posture_weight_ptr=ptr(u),
+                                    n_target=len(link_names or ()), target_pos_ptr=ptr(tp), target_rot_ptr=ptr(tr), pos_weight_ptr=ptr(wl),
+                                    rot_weight_ptr=ptr(wa), collision_weight=float(collision_weight), pair_weight_ptr=ptr(pw), lo_ptr=ptr(lo),
+                                    hi_ptr=ptr(hi), tol=float(tol), max_step=float(max_step), body_energy_ptr=ptr(be),
+                                    stream=torch.cuda.current_stream(x0.device).cuda_stream)
+    return (q, iters, energy, status, be) if body_energy else (q, iters, energy, status)
+
+
+def resolve_scene_collisions(optimizer, q0, sphere_set: SphereSet, bodies, margin, damping=_REQUIRED, max_iters=_REQUIRED, posture_weight=None,
+                             q_ref=None, collision_weight=1.0, pair_weight=None, link_names=None, target_pos=None, target_rot=None,
+                             pos_weight=None, rot_weight=None, tol=0.0, max_step=0.0, limits=None, fixed_qpos=None, body_energy=False):
+    """`resolve_collisions` / `resolve_grid_collisions` against a SCENE: `bodies`, a list of 1..4 `SceneBody`, each an ObstacleSet or
+    an SdfGrid with a pose per frame (or none), a margin and a weight of its own -- a hand holding an object that sits on a table, a
+    world-fixed fixture and a held object, primitives and a scanned mesh together.  ONE launch descends on ONE energy
+
+        E = E of resolve_self_collision + sum_b weight_b * (the obstacle term of body b with margin_b and its pose)
+
+    where running the single-body solves one after the other would push the hand back into the body each of them does not know.
+    Every other argument, the accept / reject rule and the damping are those of `resolve_self_collision`.  -> (q (B, n_opt) float32,
+    iters (B) int32, energy (B, 4) float32: pose, posture, self-collision and the sum of the bodies' terms at q, status (B) int32)
+    and, with body_energy=True, a fifth value (B, n_body) float32: each body's term at q.  The curvature uses the first 256 active
+    contacts over all bodies together, in the set's sphere order, then the bodies' order, then a set's primitives' order; a point
+    with more sets _lib.RESOLVE_CONTACTS_TRUNCATED -- grids count here, unlike in `resolve_grid_collisions`.  The matching penalty
+    is the sum of `obstacle_penalty` / `grid_penalty` over the bodies.  No autograd graph."""
+    return _resolve_scene(optimizer.sphere_model, optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q0, "q",
+                          fixed_qpos, sphere_set, bodies, margin, damping, max_iters, posture_weight, q_ref, collision_weight, pair_weight,
+                          link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits, body_energy)
+
+
+def robot_resolve_scene_collisions(robot, qpos0, sphere_set: SphereSet, bodies, margin, damping=_REQUIRED, max_iters=_REQUIRED,
+                                   posture_weight=None, q_ref=None, collision_weight=1.0, pair_weight=None, link_names=None, target_pos=None,
+                                   target_rot=None, pos_weight=None, rot_weight=None, tol=0.0, max_step=0.0, limits=None, body_energy=False):
+    """The same for a full robot qpos (B, robot.dof) in dof order; every joint is a column of its own, limits (robot.dof, 2)."""
+    return _resolve_scene(robot.sphere_model, robot.dof, 0, robot.kin, robot, qpos0, "qpos", None, sphere_set, bodies, margin, damping,
+                          max_iters, posture_weight, q_ref, collision_weight, pair_weight, link_names, target_pos, target_rot, pos_weight,
+                          rot_weight, tol, max_step, limits, body_energy)
+
+
 __all__ = ["SphereSet", "default_pairs", "sphere_distances", "self_collision_penalty", "robot_sphere_distances",
            "robot_self_collision_penalty", "resolve_self_collision", "robot_resolve_self_collision", "ObstacleSet", "obstacle_distances",
            "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty", "resolve_collisions", "robot_resolve_collisions", "SdfGrid",
            "grid_distances", "grid_penalty", "robot_grid_distances", "robot_grid_penalty", "resolve_grid_collisions",
-           "robot_resolve_grid_collisions", "TriangleMesh", "mesh_distances"]
+           "robot_resolve_grid_collisions", "TriangleMesh", "mesh_distances", "SceneBody", "resolve_scene_collisions",
+           "robot_resolve_scene_collisions"]
