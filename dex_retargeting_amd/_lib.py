@@ -99,6 +99,10 @@ MESH_SDF_EXPORTS = ["dexr_mesh_create", "dexr_mesh_destroy", "dexr_mesh_info", "
                     "dexr_mesh_sample_grid_dev", "dexr_mesh_sample_grid"]
 MESH_MAX_VERTICES, MESH_MAX_TRIANGLES = 1 << 20, 1 << 20  # DEXR_MESH_MAX_*
 MESH_TILE, MESH_BLOCK_POINTS, MESH_PAIRS_PER_LAUNCH = 256, 512, 1 << 34  # DEXR_MESH_TILE, DEXR_MESH_BLOCK_POINTS, DEXR_MESH_PAIRS_PER_LAUNCH
+# include/dexr_cross.h (the spheres of one posed robot against another's: distances, their VJP, the fused penalty): a list of its own
+CROSS_EXPORTS = ["dexr_cross_distances_dev", "dexr_cross_distances_vjp_dev", "dexr_cross_penalty_dev", "dexr_cross_distances",
+                 "dexr_cross_distances_vjp", "dexr_cross_penalty"]
+CROSS_FRAMES, CROSS_LDS = 16, 65536  # DEXR_CROSS_*
 UNIQUE_ID_BYTES = 128
 
 
@@ -222,6 +226,12 @@ def load() -> C.CDLL:
     lib.dexr_obstacle_distances.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, f64p, i32p]
     lib.dexr_obstacle_distances_vjp.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, f64p, f64p]
     lib.dexr_obstacle_penalty.argtypes = [vp, vp, i64, f64p, f64p, f64p, f64p, C.c_double, f64p, f64p, f64p, f64p]
+    lib.dexr_cross_distances_dev.argtypes = [vp, vp, i64] + [vp] * 8 + [vp, vp, vp, vp, vp]
+    lib.dexr_cross_distances_vjp_dev.argtypes = [vp, vp, i64] + [vp] * 8 + [vp, vp, vp, vp, vp, vp, vp]
+    lib.dexr_cross_penalty_dev.argtypes = [vp, vp, i64] + [vp] * 8 + [C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    lib.dexr_cross_distances.argtypes = [vp, vp, i64] + [f64p] * 8 + [f64p, i32p, f64p, i32p]
+    lib.dexr_cross_distances_vjp.argtypes = [vp, vp, i64] + [f64p] * 8 + [f64p] * 6
+    lib.dexr_cross_penalty.argtypes = [vp, vp, i64] + [f64p] * 8 + [C.c_double] + [f64p] * 6
     lib.dexr_sdf_grid_create.argtypes = [i32p, f64p, f64p, f32p, C.POINTER(vp)]
     lib.dexr_sdf_grid_destroy.argtypes = [vp]
     lib.dexr_sdf_grid_destroy.restype = None
@@ -984,6 +994,100 @@ class SphereModel:
         check(load().dexr_obstacle_penalty(self._h, obstacles.handle, B, d(x), d(fixed), d(pos), d(rot), float(margin), d(prim_weight), d(e),
                                            d(gx), d(wr)))
         return e, gx, wr
+
+    # the model's spheres against another posed model's (include/dexr_cross.h); self is robot A, neither pair list plays a part ----
+    def cross_distances_dev(self, other: "SphereModel", B: int, x_a_ptr: int, fixed_a_ptr: int, x_b_ptr: int, fixed_b_ptr: int,
+                            dist_a_ptr: int = 0, nearest_a_ptr: int = 0, dist_b_ptr: int = 0, nearest_b_ptr: int = 0, pos_a_ptr: int = 0,
+                            rot_a_ptr: int = 0, pos_b_ptr: int = 0, rot_b_ptr: int = 0, stream: int = 0):
+        """x_a (B, n_in_a), x_b (B, n_in_b), fixed_* or 0, pos_* (B, 3) or 0, rot_* (B, 3, 3) or 0 -> dist_a (B, S_a), nearest_a
+        (B, S_a) int32, dist_b (B, S_b), nearest_b (B, S_b) int32, each may be 0, not all (dexr_cross_distances_dev)."""
+        check(load().dexr_cross_distances_dev(self._h, other.handle, B, x_a_ptr or None, fixed_a_ptr or None, x_b_ptr or None,
+                                              fixed_b_ptr or None, pos_a_ptr or None, rot_a_ptr or None, pos_b_ptr or None, rot_b_ptr or None,
+                                              dist_a_ptr or None, nearest_a_ptr or None, dist_b_ptr or None, nearest_b_ptr or None,
+                                              stream or None))
+
+    def cross_distances_vjp_dev(self, other: "SphereModel", B: int, x_a_ptr: int, fixed_a_ptr: int, x_b_ptr: int, fixed_b_ptr: int,
+                                grad_dist_a_ptr: int, grad_dist_b_ptr: int, grad_xa_ptr: int, grad_xb_ptr: int, wrench_a_ptr: int = 0,
+                                wrench_b_ptr: int = 0, pos_a_ptr: int = 0, rot_a_ptr: int = 0, pos_b_ptr: int = 0, rot_b_ptr: int = 0,
+                                stream: int = 0):
+        """grad_dist_a (B, S_a) or 0, grad_dist_b (B, S_b) or 0 -> grad_xa (B, n_in_a), grad_xb (B, n_in_b), wrench_a, wrench_b
+        (B, 6) or 0, every entry written (dexr_cross_distances_vjp_dev)."""
+        check(load().dexr_cross_distances_vjp_dev(self._h, other.handle, B, x_a_ptr or None, fixed_a_ptr or None, x_b_ptr or None,
+                                                  fixed_b_ptr or None, pos_a_ptr or None, rot_a_ptr or None, pos_b_ptr or None,
+                                                  rot_b_ptr or None, grad_dist_a_ptr or None, grad_dist_b_ptr or None, grad_xa_ptr or None,
+                                                  grad_xb_ptr or None, wrench_a_ptr or None, wrench_b_ptr or None, stream or None))
+
+    def cross_penalty_dev(self, other: "SphereModel", B: int, x_a_ptr: int, fixed_a_ptr: int, x_b_ptr: int, fixed_b_ptr: int, margin: float,
+                          pair_weight_ptr: int, energy_ptr: int, grad_xa_ptr: int, grad_xb_ptr: int, wrench_a_ptr: int = 0,
+                          wrench_b_ptr: int = 0, pos_a_ptr: int = 0, rot_a_ptr: int = 0, pos_b_ptr: int = 0, rot_b_ptr: int = 0,
+                          stream: int = 0):
+        """margin >= 0, pair_weight (S_a, S_b) or 0 -> energy (B), grad_xa (B, n_in_a), grad_xb (B, n_in_b), wrench_a, wrench_b
+        (B, 6), each may be 0, not all, from one launch (dexr_cross_penalty_dev)."""
+        check(load().dexr_cross_penalty_dev(self._h, other.handle, B, x_a_ptr or None, fixed_a_ptr or None, x_b_ptr or None,
+                                            fixed_b_ptr or None, pos_a_ptr or None, rot_a_ptr or None, pos_b_ptr or None, rot_b_ptr or None,
+                                            float(margin), pair_weight_ptr or None, energy_ptr or None, grad_xa_ptr or None,
+                                            grad_xb_ptr or None, wrench_a_ptr or None, wrench_b_ptr or None, stream or None))
+
+    def _cross_host(self, other, x_a, x_b, fixed_a, fixed_b, pos_a, rot_a, pos_b, rot_b):
+        x_a, fixed_a, B = self._host_inputs(x_a, fixed_a)
+        x_b, fixed_b, Bb = other._host_inputs(x_b, fixed_b)
+        if Bb != B:
+            raise ValueError(f"x_a has {B} frames, x_b {Bb}: both robots need one row per frame")
+        poses = []
+        for name, a, shape in (("pos_a", pos_a, (B, 3)), ("rot_a", rot_a, (B, 3, 3)), ("pos_b", pos_b, (B, 3)), ("rot_b", rot_b, (B, 3, 3))):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != shape:
+                    raise ValueError(f"{name} must have shape {shape}, got {a.shape}")
+            poses.append(a)
+        return B, [_ptr(a, C.c_double) for a in (x_a, fixed_a, x_b, fixed_b, *poses)], (x_a, fixed_a, x_b, fixed_b, poses)
+
+    def cross_distances(self, other: "SphereModel", x_a, x_b, fixed_a=None, fixed_b=None, pos_a=None, rot_a=None, pos_b=None, rot_b=None,
+                        nearest: bool = True):
+        """-> dist_a (B, S_a), nearest_a (B, S_a) int32 or None, dist_b (B, S_b), nearest_b or None; float64 (dexr_cross_distances)."""
+        B, ptrs, _keep = self._cross_host(other, x_a, x_b, fixed_a, fixed_b, pos_a, rot_a, pos_b, rot_b)
+        da, db = np.zeros((B, self.n_sphere), dtype=np.float64), np.zeros((B, other.n_sphere), dtype=np.float64)
+        na = np.zeros((B, self.n_sphere), dtype=np.int32) if nearest else None
+        nb = np.zeros((B, other.n_sphere), dtype=np.int32) if nearest else None
+        check(load().dexr_cross_distances(self._h, other.handle, B, *ptrs, _ptr(da, C.c_double), _ptr(na, C.c_int32), _ptr(db, C.c_double),
+                                          _ptr(nb, C.c_int32)))
+        return da, na, db, nb
+
+    def cross_distances_vjp(self, other: "SphereModel", x_a, x_b, grad_dist_a=None, grad_dist_b=None, fixed_a=None, fixed_b=None,
+                            pos_a=None, rot_a=None, pos_b=None, rot_b=None, want_wrench: bool = True):
+        """-> (grad_xa (B, n_in_a), grad_xb (B, n_in_b), wrench_a, wrench_b (B, 6) or None) float64 (dexr_cross_distances_vjp)."""
+        B, ptrs, _keep = self._cross_host(other, x_a, x_b, fixed_a, fixed_b, pos_a, rot_a, pos_b, rot_b)
+        gd = []
+        for name, g, n in (("grad_dist_a", grad_dist_a, self.n_sphere), ("grad_dist_b", grad_dist_b, other.n_sphere)):
+            if g is not None:
+                g = np.ascontiguousarray(g, dtype=np.float64)
+                if g.shape != (B, n):
+                    raise ValueError(f"{name} must have shape ({B}, {n}), got {g.shape}")
+            gd.append(g)
+        gxa, gxb = np.zeros((B, self.n_in), dtype=np.float64), np.zeros((B, other.n_in), dtype=np.float64)
+        wa = np.zeros((B, 6), dtype=np.float64) if want_wrench else None
+        wb = np.zeros((B, 6), dtype=np.float64) if want_wrench else None
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        check(load().dexr_cross_distances_vjp(self._h, other.handle, B, *ptrs, d(gd[0]), d(gd[1]), d(gxa), d(gxb), d(wa), d(wb)))
+        return gxa, gxb, wa, wb
+
+    def cross_penalty(self, other: "SphereModel", x_a, x_b, margin, pair_weight=None, fixed_a=None, fixed_b=None, pos_a=None, rot_a=None,
+                      pos_b=None, rot_b=None, want_energy: bool = True, want_grad_a: bool = True, want_grad_b: bool = True,
+                      want_wrench_a: bool = True, want_wrench_b: bool = True):
+        """-> (energy (B), grad_xa, grad_xb, wrench_a (B, 6), wrench_b (B, 6)) float64, None where not wanted (dexr_cross_penalty)."""
+        B, ptrs, _keep = self._cross_host(other, x_a, x_b, fixed_a, fixed_b, pos_a, rot_a, pos_b, rot_b)
+        if pair_weight is not None:
+            pair_weight = np.ascontiguousarray(pair_weight, dtype=np.float64)
+            if pair_weight.shape != (self.n_sphere, other.n_sphere):
+                raise ValueError(f"pair_weight must have shape ({self.n_sphere}, {other.n_sphere}), got {pair_weight.shape}")
+        e = np.zeros(B, dtype=np.float64) if want_energy else None
+        gxa = np.zeros((B, self.n_in), dtype=np.float64) if want_grad_a else None
+        gxb = np.zeros((B, other.n_in), dtype=np.float64) if want_grad_b else None
+        wa = np.zeros((B, 6), dtype=np.float64) if want_wrench_a else None
+        wb = np.zeros((B, 6), dtype=np.float64) if want_wrench_b else None
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        check(load().dexr_cross_penalty(self._h, other.handle, B, *ptrs, float(margin), d(pair_weight), d(e), d(gxa), d(gxb), d(wa), d(wb)))
+        return e, gxa, gxb, wa, wb
 
     # the model's spheres against a sampled signed-distance field (include/dexr_sdf_grid.h); the pair list plays no part ----
     def grid_distances_dev(self, grid: "SdfGrid", B: int, x_ptr: int, fixed_ptr: int, dist_ptr: int, obstacle_pos_ptr: int = 0,

@@ -769,7 +769,148 @@ def robot_grid_penalty(robot, qpos, sphere_set, grid, margin, obstacle_pos=None,
         return _grid_fns()[1].apply(qpos, None, obstacle_pos, obstacle_rot, robot.sphere_model(sphere_set, pairs), grid, float(margin))
 
 
+# ---- the spheres of one posed robot against another's: differentiable in both q and both base positions ---------------------------
+def _make_cross_functions():
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _CrossDistances(torch.autograd.Function):
+        """Saves the inputs only: the VJP kernel recomputes both walks, the nearest spheres and their normals."""
+
+        @staticmethod
+        def forward(ctx, x_a, fixed_a, x_b, fixed_b, pos_a, rot_a, pos_b, rot_b, model_a, model_b):
+            from . import collision
+
+            da, db = collision._cross_distances(model_a, model_b, x_a, fixed_a, x_b, fixed_b, pos_a, rot_a, pos_b, rot_b, False)
+            inputs = collision._cross_inputs(x_a, fixed_a, x_b, fixed_b, pos_a, rot_a, pos_b, rot_b)
+            ctx.models = (model_a, model_b)
+            ctx.have = [a is not None for a in inputs]
+            ctx.save_for_backward(*[a for a in inputs if a is not None])
+            return da, db
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_a, grad_b):
+            from . import collision
+
+            need = ctx.needs_input_grad
+            if not (need[0] or need[2] or need[4] or need[6]):
+                return (None,) * 10
+            saved = list(ctx.saved_tensors)
+            inputs = tuple(saved.pop(0) if h else None for h in ctx.have)
+            c = lambda g: None if g is None else g.detach().to(torch.float32).contiguous()  # noqa: E731
+            want_p = (bool(need[4]) and inputs[4] is not None, bool(need[6]) and inputs[6] is not None)
+            ga, gb, wa, wb = collision._cross_distances_vjp(*ctx.models, inputs, c(grad_a), c(grad_b), want_wrench=want_p)
+            return (ga if need[0] else None, None, gb if need[2] else None, None, wa[:, :3] if want_p[0] else None, None,
+                    wb[:, :3] if want_p[1] else None, None, None, None)
+
+    class _CrossPenalty(torch.autograd.Function):
+        """The forward launch gives E and whichever of dE/dx_a, dE/dx_b and the two wrenches an input needs; backward scales what
+        it saved."""
+
+        @staticmethod
+        def forward(ctx, x_a, fixed_a, x_b, fixed_b, pos_a, rot_a, pos_b, rot_b, model_a, model_b, margin, pair_weight):
+            from . import collision
+
+            need = ctx.needs_input_grad
+            want = (True, bool(need[0]), bool(need[2]), pos_a is not None and bool(need[4]), pos_b is not None and bool(need[6]))
+            out = collision._cross_penalty(model_a, model_b, x_a, fixed_a, x_b, fixed_b, margin, pair_weight, pos_a, rot_a, pos_b, rot_b,
+                                           want=want)
+            ctx.want = want
+            ctx.save_for_backward(*[a for a in out[1:] if a is not None])
+            return out[0]
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_e):
+            saved = list(ctx.saved_tensors)
+            ge = grad_e.to(torch.float32)[:, None]
+            ga, gb, wa, wb = (saved.pop(0) if k else None for k in ctx.want[1:])
+            s = lambda t: None if t is None else ge * t  # noqa: E731
+            # dE/d(base translation): the force half of that base's wrench
+            return (s(ga), None, s(gb), None, None if wa is None else ge * wa[:, :3], None, None if wb is None else ge * wb[:, :3], None) + \
+                (None,) * 4
+
+    return _CrossDistances, _CrossPenalty
+
+
+_CROSS_FNS = None
+
+
+def _cross_fns():
+    global _CROSS_FNS
+    if _CROSS_FNS is None:
+        _CROSS_FNS = _make_cross_functions()
+    return _CROSS_FNS
+
+
+def cross_distances(optimizer_a, q_a, spheres_a, optimizer_b, q_b, spheres_b, pos_a=None, rot_a=None, pos_b=None, rot_b=None,
+                    fixed_qpos_a=None, fixed_qpos_b=None):
+    """`collision.cross_distances` with an autograd graph: (dist_a (B, S_a), dist_b (B, S_b)) float32, the same bits; backward is
+    the distance VJP kernel (dexr_cross_distances_vjp_dev), one launch for both cotangents.  Gradients flow to q_a, q_b and -- the
+    force halves of the VJP's wrenches -- to pos_a, pos_b; a rotation that requires grad is a ValueError; once differentiable."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(rot_a)
+    _no_rot_grad(rot_b)
+    ma, mb = collision._check_cross(collision._optimizer_side(optimizer_a, q_a, spheres_a, fixed_qpos_a, "a"),
+                                    collision._optimizer_side(optimizer_b, q_b, spheres_b, fixed_qpos_b, "b"), pos_a, rot_a, pos_b, rot_b)
+    with torch.cuda.device(q_a.device):
+        return _cross_fns()[0].apply(q_a, fixed_qpos_a, q_b, fixed_qpos_b, pos_a, rot_a, pos_b, rot_b, ma, mb)
+
+
+def cross_penalty(optimizer_a, q_a, spheres_a, optimizer_b, q_b, spheres_b, margin, pos_a=None, rot_a=None, pos_b=None, rot_b=None,
+                  pair_weight=None, fixed_qpos_a=None, fixed_qpos_b=None):
+    """`collision.cross_penalty` with an autograd graph: E (B,) float32.  The forward launch computes E and only what some input
+    needs of dE/dq_a, dE/dq_b and the two wrenches (one launch, the same bits as the no-graph call); backward is grad_E[:, None] *
+    dE/dq for q_a and q_b and grad_E[:, None] * wrench[:, :3] for pos_a and pos_b.  No gradient flows to a rotation (one that
+    requires grad is a ValueError: `collision.cross_penalty(..., wrench=True)` gives the torques), pair_weight or fixed_qpos; once
+    differentiable."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(rot_a)
+    _no_rot_grad(rot_b)
+    ma, mb = collision._check_cross(collision._optimizer_side(optimizer_a, q_a, spheres_a, fixed_qpos_a, "a"),
+                                    collision._optimizer_side(optimizer_b, q_b, spheres_b, fixed_qpos_b, "b"), pos_a, rot_a, pos_b, rot_b,
+                                    margin, pair_weight, penalty=True)
+    with torch.cuda.device(q_a.device):
+        return _cross_fns()[1].apply(q_a, fixed_qpos_a, q_b, fixed_qpos_b, pos_a, rot_a, pos_b, rot_b, ma, mb, float(margin), pair_weight)
+
+
+def robot_cross_distances(robot_a, qpos_a, spheres_a, robot_b, qpos_b, spheres_b, pos_a=None, rot_a=None, pos_b=None, rot_b=None):
+    """The same for full robot qpos (B, robot.dof) float32 in dof order."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(rot_a)
+    _no_rot_grad(rot_b)
+    ma, mb = collision._check_cross(collision._robot_side(robot_a, qpos_a, spheres_a, "a"), collision._robot_side(robot_b, qpos_b, spheres_b, "b"),
+                                    pos_a, rot_a, pos_b, rot_b)
+    with torch.cuda.device(qpos_a.device):
+        return _cross_fns()[0].apply(qpos_a, None, qpos_b, None, pos_a, rot_a, pos_b, rot_b, ma, mb)
+
+
+def robot_cross_penalty(robot_a, qpos_a, spheres_a, robot_b, qpos_b, spheres_b, margin, pos_a=None, rot_a=None, pos_b=None, rot_b=None,
+                        pair_weight=None):
+    """The same for full robot qpos (B, robot.dof) float32 in dof order."""
+    import torch
+
+    from . import collision
+
+    _no_rot_grad(rot_a)
+    _no_rot_grad(rot_b)
+    ma, mb = collision._check_cross(collision._robot_side(robot_a, qpos_a, spheres_a, "a"), collision._robot_side(robot_b, qpos_b, spheres_b, "b"),
+                                    pos_a, rot_a, pos_b, rot_b, margin, pair_weight, penalty=True)
+    with torch.cuda.device(qpos_a.device):
+        return _cross_fns()[1].apply(qpos_a, None, qpos_b, None, pos_a, rot_a, pos_b, rot_b, ma, mb, float(margin), pair_weight)
+
+
 __all__ = ["retarget", "ref_value_from_keypoints", "link_poses", "robot_link_poses", "link_velocities", "robot_link_velocities",
            "sphere_distances", "self_collision_penalty", "robot_sphere_distances", "robot_self_collision_penalty", "obstacle_distances",
            "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty", "grid_distances", "grid_penalty", "robot_grid_distances",
-           "robot_grid_penalty"]
+           "robot_grid_penalty", "cross_distances", "cross_penalty", "robot_cross_distances", "robot_cross_penalty"]

@@ -29,9 +29,16 @@ trilinear lookup per sphere however complex the shape is, the distance continued
 box.  ``SdfGrid.from_obstacles`` samples an ``ObstacleSet``.  ``resolve_grid_collisions`` is ``resolve_collisions`` against a grid
 (include/dexr_resolve_grid.h): a sphere has one contact at most, so nothing is capped.
 
+The other robot is the one obstacle that has its own q per frame (include/dexr_cross.h, csrc/dexr_cross.hpp): the other hand of a
+two-handed recording, a second gripper, the arm beside the hand.  ``cross_distances`` and ``cross_penalty`` take two optimisers,
+two q, two ``SphereSet`` and a base pose per robot and frame (``pos_a``, ``rot_a``, ``pos_b``, ``rot_b``), and give the distance of
+every sphere of either robot to the nearest sphere of the other, and the squared-hinge energy over every (sphere of A, sphere of
+B) pair with its gradient in both q and, asked for, the wrench on either base -- ONE launch that walks both robots.
+
 The outputs of this module carry NO autograd graph; ``autograd.sphere_distances``, ``autograd.self_collision_penalty``,
-``autograd.obstacle_distances``, ``autograd.obstacle_penalty``, ``autograd.grid_distances`` and ``autograd.grid_penalty`` are the
-same kernels with one, so that a penetration loss composes with ``autograd.retarget`` and reaches the keypoints.
+``autograd.obstacle_distances``, ``autograd.obstacle_penalty``, ``autograd.grid_distances``, ``autograd.grid_penalty``,
+``autograd.cross_distances`` and ``autograd.cross_penalty`` are the same kernels with one, so that a penetration loss composes
+with ``autograd.retarget`` and reaches the keypoints.
 """
 from __future__ import annotations
 
@@ -1252,9 +1259,188 @@ def robot_resolve_scene_collisions(robot, qpos0, sphere_set: SphereSet, bodies, 
                           rot_weight, tol, max_step, limits, body_energy)
 
 
+# ---- the other robot: the spheres of one posed robot against the spheres of another (include/dexr_cross.h) -----------------------------
+def _optimizer_side(optimizer, q, sphere_set, fixed_qpos, tag):
+    return (optimizer.opt_dof, len(optimizer.idx_pin2fixed), optimizer.robot.kin, optimizer.robot, q, fixed_qpos, sphere_set, f"q_{tag}",
+            optimizer.sphere_model)
+
+
+def _robot_side(robot, qpos, sphere_set, tag):
+    return robot.dof, 0, robot.kin, robot, qpos, None, sphere_set, f"qpos_{tag}", robot.sphere_model
+
+
+def _check_cross(side_a, side_b, pos_a, rot_a, pos_b, rot_b, margin=None, pair_weight=None, penalty=False):
+    """Every argument rule in the order of `_check`, for both robots -- the sphere sets, the links, the pairs, the scalars, then types,
+    dtypes and shapes, and last the device -- before anything touches the GPU.  Returns the two sphere models."""
+    import torch
+
+    pairs = []
+    for side in (side_a, side_b):
+        kin, robot, sphere_set = side[2], side[3], side[6]
+        if not isinstance(sphere_set, SphereSet):
+            raise ValueError("spheres_a and spheres_b must each be a collision.SphereSet")
+        for n in sphere_set.table_links:
+            kin.body_frame_index(n)  # ValueError on an unknown link
+        pairs.append(_resolved_pairs(robot, sphere_set))
+    if penalty and (isinstance(margin, bool) or not isinstance(margin, (int, float)) or not math.isfinite(margin) or margin < 0):
+        raise ValueError(f"margin must be a finite Python float >= 0, got {margin!r}")
+    q_a, q_b = side_a[4], side_b[4]
+    B = q_a.shape[0] if isinstance(q_a, torch.Tensor) and q_a.ndim == 2 else None
+    named = [(n, t, s) for n, t, s in (("pos_a", pos_a, (B, 3)), ("rot_a", rot_a, (B, 3, 3)), ("pos_b", pos_b, (B, 3)), ("rot_b", rot_b, (B, 3, 3)))
+             if t is not None]
+    if penalty and pair_weight is not None:
+        named.append(("pair_weight", pair_weight, (side_a[6].n_sphere, side_b[6].n_sphere)))
+    for name, t, _ in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+    for name, t, _ in named:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    for name, t, shape in named:
+        if (B is not None or shape[0] is not None) and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    tensors = []
+    for (n_in, n_fixed, _, _, q, fixed_qpos, _, what, _), tag in ((side_a, "a"), (side_b, "b")):  # the rules of _check_poses, the device last
+        if not isinstance(q, torch.Tensor):
+            raise ValueError(f"{what} must be a torch tensor")
+        both = [(what, q)]
+        if fixed_qpos is not None:
+            if not isinstance(fixed_qpos, torch.Tensor):
+                raise ValueError(f"fixed_qpos_{tag} must be a torch tensor")
+            both.append((f"fixed_qpos_{tag}", fixed_qpos))
+        for name, t in both:
+            if t.dtype != torch.float32:
+                raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if q.ndim != 2 or q.shape[1] != n_in:
+            raise ValueError(f"{what} must have shape (B, {n_in}), got {tuple(q.shape)}")
+        if n_fixed > 0 and fixed_qpos is None:
+            raise ValueError(f"the optimizer has {n_fixed} fixed joints: fixed_qpos_{tag} of shape ({q.shape[0]}, {n_fixed}) is required")
+        if fixed_qpos is not None and tuple(fixed_qpos.shape) != (q.shape[0], n_fixed):
+            raise ValueError(f"fixed_qpos_{tag} must have shape ({q.shape[0]}, {n_fixed}), got {tuple(fixed_qpos.shape)}")
+        tensors += both
+    if q_b.shape[0] != q_a.shape[0]:
+        raise ValueError(f"{side_a[7]} has {q_a.shape[0]} frames, {side_b[7]} {q_b.shape[0]}: both robots need one row per frame")
+    if q_a.device.type != "cuda":
+        raise ValueError(f"the tensors must be CUDA (HIP) tensors, got device {q_a.device}")
+    for name, t in tensors[1:] + [(n, t) for n, t, _ in named]:
+        if t.device != q_a.device:
+            raise ValueError(f"{name} is on {t.device}, {side_a[7]} on {q_a.device}: all tensors must be on one CUDA device")
+    return side_a[8](side_a[6], pairs[0]), side_b[8](side_b[6], pairs[1])
+
+
+def _cross_inputs(x_a, fixed_a, x_b, fixed_b, pos_a, rot_a, pos_b, rot_b):
+    """the eight inputs of a cross launch, detached and contiguous (None where left out)."""
+    xa, fa = _inputs(x_a, fixed_a)
+    xb, fb = _inputs(x_b, fixed_b)
+    return (xa, fa, xb, fb) + _obstacle_pose(pos_a, rot_a) + _obstacle_pose(pos_b, rot_b)
+
+
+def _cross_ptrs(inputs):
+    xa, fa, xb, fb, pa, ra, pb, rb = (0 if a is None else a.data_ptr() for a in inputs)
+    return (xa, fa, xb, fb), dict(pos_a_ptr=pa, rot_a_ptr=ra, pos_b_ptr=pb, rot_b_ptr=rb)
+
+
+def _cross_distances(model_a, model_b, x_a, fixed_a, x_b, fixed_b, pos_a, rot_a, pos_b, rot_b, nearest):
+    import torch
+
+    B, dev = x_a.shape[0], x_a.device
+    inputs = _cross_inputs(x_a, fixed_a, x_b, fixed_b, pos_a, rot_a, pos_b, rot_b)
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        da = torch.empty((B, model_a.n_sphere), dtype=torch.float32, device=dev)
+        db = torch.empty((B, model_b.n_sphere), dtype=torch.float32, device=dev)
+        na = torch.empty((B, model_a.n_sphere), dtype=torch.int32, device=dev) if nearest else None
+        nb = torch.empty((B, model_b.n_sphere), dtype=torch.int32, device=dev) if nearest else None
+        if B > 0:
+            head, poses = _cross_ptrs(inputs)
+            model_a.cross_distances_dev(model_b, B, *head, da.data_ptr(), ptr(na), db.data_ptr(), ptr(nb), **poses,
+                                        stream=torch.cuda.current_stream(dev).cuda_stream)
+    return (da, na, db, nb) if nearest else (da, db)
+
+
+def _cross_penalty(model_a, model_b, x_a, fixed_a, x_b, fixed_b, margin, pair_weight, pos_a, rot_a, pos_b, rot_b, want=(True,) * 5):
+    """one launch -> (E (B,), grad_a, grad_b, wrench_a (B, 6), wrench_b (B, 6)), None where `want` (in that order) says so."""
+    import torch
+
+    B, dev = x_a.shape[0], x_a.device
+    inputs = _cross_inputs(x_a, fixed_a, x_b, fixed_b, pos_a, rot_a, pos_b, rot_b)
+    w = None if pair_weight is None else pair_weight.detach().contiguous()
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    shapes = ((B,), (B, model_a.n_in), (B, model_b.n_in), (B, 6), (B, 6))
+    with torch.cuda.device(dev):
+        out = [torch.empty(s, dtype=torch.float32, device=dev) if k else None for s, k in zip(shapes, want)]
+        if B > 0:
+            head, poses = _cross_ptrs(inputs)
+            model_a.cross_penalty_dev(model_b, B, *head, float(margin), ptr(w), *[ptr(o) for o in out], **poses,
+                                      stream=torch.cuda.current_stream(dev).cuda_stream)
+    return tuple(out)
+
+
+def _cross_distances_vjp(model_a, model_b, inputs, grad_dist_a, grad_dist_b, want_wrench=(False, False)):
+    """the VJP launch on detached, contiguous `inputs` (_cross_inputs) -> (grad_a, grad_b, wrench_a or None, wrench_b or None)."""
+    import torch
+
+    xa, xb = inputs[0], inputs[2]
+    B, dev = xa.shape[0], xa.device
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        ga, gb = torch.empty_like(xa), torch.empty_like(xb)  # (the kernel writes every entry)
+        wa, wb = (torch.empty((B, 6), dtype=torch.float32, device=dev) if k else None for k in want_wrench)
+        if B > 0:
+            head, poses = _cross_ptrs(inputs)
+            model_a.cross_distances_vjp_dev(model_b, B, *head, ptr(grad_dist_a), ptr(grad_dist_b), ga.data_ptr(), gb.data_ptr(), ptr(wa), ptr(wb),
+                                            **poses, stream=torch.cuda.current_stream(dev).cuda_stream)
+    return ga, gb, wa, wb
+
+
+def cross_distances(optimizer_a, q_a, spheres_a: SphereSet, optimizer_b, q_b, spheres_b: SphereSet, pos_a=None, rot_a=None, pos_b=None,
+                    rot_b=None, fixed_qpos_a=None, fixed_qpos_b=None, nearest: bool = False):
+    """Signed distance of every sphere of robot A to the nearest sphere of robot B and the other way round, each robot at its own
+    optimiser's variables and with its own base pose per frame: q_a (B, n_opt_a), q_b (B, n_opt_b) float32 CUDA; pos_* (B, 3) and
+    rot_* (B, 3, 3) float32 the world pose of that robot's root per frame, or None (zero translation / identity) -> (dist_a (B, S_a),
+    dist_b (B, S_b)) float32 in the sets' sphere orders, negative where two spheres interpenetrate; with `nearest=True` ->
+    (dist_a, nearest_a, dist_b, nearest_b), nearest_* int32 the first sphere of the other set that attains the minimum.  The pair
+    lists of the sets play no part; the two optimisers may be one.  No autograd graph."""
+    ma, mb = _check_cross(_optimizer_side(optimizer_a, q_a, spheres_a, fixed_qpos_a, "a"), _optimizer_side(optimizer_b, q_b, spheres_b, fixed_qpos_b, "b"),
+                          pos_a, rot_a, pos_b, rot_b)
+    return _cross_distances(ma, mb, q_a, fixed_qpos_a, q_b, fixed_qpos_b, pos_a, rot_a, pos_b, rot_b, nearest)
+
+
+def cross_penalty(optimizer_a, q_a, spheres_a: SphereSet, optimizer_b, q_b, spheres_b: SphereSet, margin, pos_a=None, rot_a=None, pos_b=None,
+                  rot_b=None, pair_weight=None, fixed_qpos_a=None, fixed_qpos_b=None, wrench: bool = False):
+    """(E (B,), dE/dq_a (B, n_opt_a), dE/dq_b (B, n_opt_b)) float32 from ONE launch: E = sum_s sum_t w_st max(0, margin - d_st)^2
+    over every sphere s of A and every sphere t of B, d_st the signed distance of the two surfaces, and its gradient in both
+    robots' variables.  margin: a finite Python float >= 0 (metres); pair_weight (S_a, S_b) float32 >= 0 or None (1), shared by
+    the batch, a zero masks a pair; the poses as in `cross_distances`.  With `wrench=True` -> (E, dE/dq_a, dE/dq_b, wrench_a,
+    wrench_b), each (B, 6): dE/d(translation of that base) and dE/d(a world-aligned small rotation of that base about its
+    origin).  No autograd graph: `autograd.cross_penalty` is the same launch with one."""
+    ma, mb = _check_cross(_optimizer_side(optimizer_a, q_a, spheres_a, fixed_qpos_a, "a"), _optimizer_side(optimizer_b, q_b, spheres_b, fixed_qpos_b, "b"),
+                          pos_a, rot_a, pos_b, rot_b, margin, pair_weight, penalty=True)
+    out = _cross_penalty(ma, mb, q_a, fixed_qpos_a, q_b, fixed_qpos_b, margin, pair_weight, pos_a, rot_a, pos_b, rot_b,
+                         want=(True, True, True, wrench, wrench))
+    return out if wrench else out[:3]
+
+
+def robot_cross_distances(robot_a, qpos_a, spheres_a: SphereSet, robot_b, qpos_b, spheres_b: SphereSet, pos_a=None, rot_a=None, pos_b=None,
+                          rot_b=None, nearest: bool = False):
+    """The same for full robot qpos (B, robot.dof) in dof order; every joint is a column of its own."""
+    ma, mb = _check_cross(_robot_side(robot_a, qpos_a, spheres_a, "a"), _robot_side(robot_b, qpos_b, spheres_b, "b"), pos_a, rot_a, pos_b, rot_b)
+    return _cross_distances(ma, mb, qpos_a, None, qpos_b, None, pos_a, rot_a, pos_b, rot_b, nearest)
+
+
+def robot_cross_penalty(robot_a, qpos_a, spheres_a: SphereSet, robot_b, qpos_b, spheres_b: SphereSet, margin, pos_a=None, rot_a=None,
+                        pos_b=None, rot_b=None, pair_weight=None, wrench: bool = False):
+    """(E (B,), dE/dqpos_a, dE/dqpos_b[, wrench_a, wrench_b]) for full robot qpos in dof order."""
+    ma, mb = _check_cross(_robot_side(robot_a, qpos_a, spheres_a, "a"), _robot_side(robot_b, qpos_b, spheres_b, "b"), pos_a, rot_a, pos_b, rot_b,
+                          margin, pair_weight, penalty=True)
+    out = _cross_penalty(ma, mb, qpos_a, None, qpos_b, None, margin, pair_weight, pos_a, rot_a, pos_b, rot_b,
+                         want=(True, True, True, wrench, wrench))
+    return out if wrench else out[:3]
+
+
 __all__ = ["SphereSet", "default_pairs", "sphere_distances", "self_collision_penalty", "robot_sphere_distances",
            "robot_self_collision_penalty", "resolve_self_collision", "robot_resolve_self_collision", "ObstacleSet", "obstacle_distances",
            "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty", "resolve_collisions", "robot_resolve_collisions", "SdfGrid",
            "grid_distances", "grid_penalty", "robot_grid_distances", "robot_grid_penalty", "resolve_grid_collisions",
            "robot_resolve_grid_collisions", "TriangleMesh", "mesh_distances", "SceneBody", "resolve_scene_collisions",
-           "robot_resolve_scene_collisions"]
+           "robot_resolve_scene_collisions", "cross_distances", "cross_penalty", "robot_cross_distances", "robot_cross_penalty"]
