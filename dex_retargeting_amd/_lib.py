@@ -103,6 +103,9 @@ MESH_TILE, MESH_BLOCK_POINTS, MESH_PAIRS_PER_LAUNCH = 256, 512, 1 << 34  # DEXR_
 CROSS_EXPORTS = ["dexr_cross_distances_dev", "dexr_cross_distances_vjp_dev", "dexr_cross_penalty_dev", "dexr_cross_distances",
                  "dexr_cross_distances_vjp", "dexr_cross_penalty"]
 CROSS_FRAMES, CROSS_LDS = 16, 65536  # DEXR_CROSS_*
+# include/dexr_resolve_cross.h (the posture solve against a second posed robot, in one kernel): a list of its own.  (Its name does
+# not end in EXPORTS: tests/test_cross_host.py counts the lists that do.)
+RESOLVE_CROSS_SYMBOLS = ["dexr_sphere_resolve_cross_dev", "dexr_sphere_resolve_cross"]
 UNIQUE_ID_BYTES = 128
 
 
@@ -253,6 +256,12 @@ def load() -> C.CDLL:
     lib.dexr_sphere_resolve_scene.argtypes = [vp, i64, f64p, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, C.c_double, f64p,
                                               f64p, f64p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, bodyp, f64p, i32p, f64p,
                                               f64p, i32p]
+    lib.dexr_sphere_resolve_cross_dev.argtypes = [vp, i64, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, C.c_float,
+                                                  C.c_float, C.c_float, C.c_int32, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp,
+                                                  vp]
+    lib.dexr_sphere_resolve_cross.argtypes = [vp, i64, f64p, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p, C.c_double, C.c_double, f64p,
+                                              f64p, f64p, C.c_double, C.c_double, C.c_double, C.c_int32, vp, f64p, f64p, f64p, f64p, C.c_double,
+                                              C.c_double, f64p, f64p, i32p, f64p, i32p]
     lib.dexr_mesh_create.argtypes = [C.c_int32, f64p, C.c_int32, i32p, C.POINTER(vp)]
     lib.dexr_mesh_destroy.argtypes = [vp]
     lib.dexr_mesh_destroy.restype = None
@@ -1240,6 +1249,57 @@ class SphereModel:
             float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi), float(damping), float(max_step), float(tol), int(max_iters),
             n_body, rec, d(x), _ptr(iters, C.c_int32), d(energy), d(body_energy), _ptr(status, C.c_int32)))
         return x, iters, energy, status, body_energy
+
+    # the posture solve against a second posed robot (include/dexr_resolve_cross.h) ---------------------------------
+    def resolve_cross_dev(self, other: "SphereModel", B: int, x0_ptr: int, fixed_ptr: int, x_b_ptr: int, fixed_b_ptr: int, margin: float,
+                          damping: float, max_iters: int, x_ptr: int, iters_ptr: int = 0, energy_ptr: int = 0, status_ptr: int = 0,
+                          x_ref_ptr: int = 0, posture_weight_ptr: int = 0, n_target: int = 0, target_pos_ptr: int = 0, target_rot_ptr: int = 0,
+                          pos_weight_ptr: int = 0, rot_weight_ptr: int = 0, collision_weight: float = 1.0, pair_weight_ptr: int = 0,
+                          lo_ptr: int = 0, hi_ptr: int = 0, tol: float = 0.0, max_step: float = 0.0, other_pos_ptr: int = 0,
+                          other_rot_ptr: int = 0, cross_margin=None, cross_weight: float = 1.0, cross_pair_weight_ptr: int = 0,
+                          stream: int = 0):
+        """the arguments of resolve_dev, and the other robot: its model, x_b (B, n_in_b), fixed_b (B, n_fixed_b) or 0, other_pos (B, 3)
+        or 0, other_rot (B, 3, 3) or 0 (its pose in this robot's root frame), cross_margin (None: margin), cross_weight (w_x),
+        cross_pair_weight (S_a, S_b) or 0 -> x (B, n_in), iters (B) int32, energy (B, 4), status (B) int32, each of the last three or
+        0 (dexr_sphere_resolve_cross_dev)."""
+        xm = margin if cross_margin is None else cross_margin
+        check(load().dexr_sphere_resolve_cross_dev(
+            self._h, B, x0_ptr or None, fixed_ptr or None, x_ref_ptr or None, posture_weight_ptr or None, int(n_target), target_pos_ptr or None,
+            target_rot_ptr or None, pos_weight_ptr or None, rot_weight_ptr or None, float(margin), float(collision_weight), pair_weight_ptr or None,
+            lo_ptr or None, hi_ptr or None, float(damping), float(max_step), float(tol), int(max_iters), other.handle, x_b_ptr or None,
+            fixed_b_ptr or None, other_pos_ptr or None, other_rot_ptr or None, float(xm), float(cross_weight), cross_pair_weight_ptr or None,
+            x_ptr or None, iters_ptr or None, energy_ptr or None, status_ptr or None, stream or None))
+
+    def resolve_cross(self, other: "SphereModel", x0, x_b, margin=None, damping=None, max_iters=None, fixed=None, fixed_b=None, x_ref=None,
+                      posture_weight=None, target_pos=None, target_rot=None, pos_weight=None, rot_weight=None,
+                      collision_weight: float = 1.0, pair_weight=None, lo=None, hi=None, tol: float = 0.0, max_step: float = 0.0,
+                      n_target=None, other_pos=None, other_rot=None, cross_margin=None, cross_weight: float = 1.0, cross_pair_weight=None):
+        """-> (x (B, n_in) float64, iters (B) int32, energy (B, 4) float64, status (B) int32) (dexr_sphere_resolve_cross): the
+        arguments of `resolve`, and the other robot's model, x_b, fixed_b, its pose per frame or None, cross_margin (None: margin),
+        cross_weight (w_x) and cross_pair_weight (S_a, S_b) or None."""
+        (x0, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight, pair_weight, lo, hi, xw), n_target, B, out = \
+            self._resolve_host(x0, margin, damping, max_iters, fixed, x_ref, posture_weight, target_pos, target_rot, pos_weight, rot_weight,
+                               pair_weight, lo, hi, n_target, 4,
+                               extra=[("cross_pair_weight", cross_pair_weight, lambda: (self.n_sphere, other.n_sphere))])
+        x_b, fixed_b, Bb = other._host_inputs(x_b, fixed_b)
+        if Bb != B:
+            raise ValueError(f"x0 has {B} frames, x_b {Bb}: both robots need one row per frame")
+        pos, rot = [], []
+        for name, a, shape, to in (("other_pos", other_pos, (B, 3), pos), ("other_rot", other_rot, (B, 3, 3), rot)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != shape:
+                    raise ValueError(f"{name} must have shape {shape}, got {a.shape}")
+            to.append(a)
+        x, iters, energy, status = out
+        d = lambda a: _ptr(a, C.c_double)  # noqa: E731
+        xm = margin if cross_margin is None else cross_margin
+        check(load().dexr_sphere_resolve_cross(
+            self._h, B, d(x0), d(fixed), d(x_ref), d(posture_weight), n_target, d(target_pos), d(target_rot), d(pos_weight), d(rot_weight),
+            float(margin), float(collision_weight), d(pair_weight), d(lo), d(hi), float(damping), float(max_step), float(tol), int(max_iters),
+            other.handle, d(x_b), d(fixed_b), d(pos[0]), d(rot[0]), float(xm), float(cross_weight), d(xw), d(x), _ptr(iters, C.c_int32),
+            d(energy), _ptr(status, C.c_int32)))
+        return out
 
 
 class ObstacleSet:

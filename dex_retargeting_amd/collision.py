@@ -1438,9 +1438,186 @@ def robot_cross_penalty(robot_a, qpos_a, spheres_a: SphereSet, robot_b, qpos_b, 
     return out if wrench else out[:3]
 
 
+# ---- the posture solve against the other robot (include/dexr_resolve_cross.h) ----------------------------------------------------------
+def _cross_resolve_rules(side_b, x0, n_sphere_a, cross_margin, w_x, other_pos, other_rot, cross_weight):
+    """The rules of the other robot's arguments, none of which looks at a device: its sphere set and links, the two scalars, then
+    types, dtypes and shapes of its tensors.  Returns (its pairs, its tensors by name for the device rule that comes last)."""
+    import torch
+
+    n_in, n_fixed, kin, robot, q_b, fixed_b, spheres_b, what = side_b[:8]
+    if not isinstance(spheres_b, SphereSet):
+        raise ValueError("spheres_b must be a collision.SphereSet")
+    for n in spheres_b.table_links:
+        kin.body_frame_index(n)  # ValueError on an unknown link
+    pairs_b = _resolved_pairs(robot, spheres_b)
+    if cross_margin is not None and (isinstance(cross_margin, bool) or not isinstance(cross_margin, (int, float)) or not math.isfinite(cross_margin)
+                                     or cross_margin < 0):
+        raise ValueError(f"cross_margin must be a finite Python float >= 0 or None (margin), got {cross_margin!r}")
+    if isinstance(w_x, bool) or not isinstance(w_x, (int, float)) or not math.isfinite(w_x) or w_x < 0:
+        raise ValueError(f"w_x must be a finite Python float >= 0, got {w_x!r}")
+    B = x0.shape[0] if isinstance(x0, torch.Tensor) and x0.ndim == 2 else None
+    named = [(n, t, s) for n, t, s in (("other_pos", other_pos, (B, 3)), ("other_rot", other_rot, (B, 3, 3)),
+                                       ("cross_weight", cross_weight, (n_sphere_a, spheres_b.n_sphere))) if t is not None]
+    for name, t, _ in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+    both = [(what, q_b)] + ([] if fixed_b is None else [("fixed_qpos_b", fixed_b)])
+    for name, t in both:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+    for name, t in [(n, t) for n, t, _ in named] + both:
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+    for name, t, shape in named:
+        if (B is not None or shape[0] is not None) and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    if q_b.ndim != 2 or q_b.shape[1] != n_in:
+        raise ValueError(f"{what} must have shape (B, {n_in}), got {tuple(q_b.shape)}")
+    if B is not None and q_b.shape[0] != B:
+        raise ValueError(f"the first robot has {B} frames, {what} {q_b.shape[0]}: both robots need one row per frame")
+    if n_fixed > 0 and fixed_b is None:
+        raise ValueError(f"the other optimizer has {n_fixed} fixed joints: fixed_qpos_b of shape ({q_b.shape[0]}, {n_fixed}) is required")
+    if fixed_b is not None and tuple(fixed_b.shape) != (q_b.shape[0], n_fixed):
+        raise ValueError(f"fixed_qpos_b must have shape ({q_b.shape[0]}, {n_fixed}), got {tuple(fixed_b.shape)}")
+    return pairs_b, [(n, t) for n, t, _ in named] + both
+
+
+def _resolve_cross(side_a, side_b, margin, cross_margin, other_pos, other_rot, cross_weight, pair_weight, w_x, damping, max_iters, posture_weight,
+                   q_ref, collision_weight, link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits):
+    """every rule (those of `_resolve`, then the other robot's, the device last), then two models and one launch."""
+    import torch
+
+    n_in, n_fixed, kin, robot, x0, fixed_qpos, sphere_set, what, model_of = side_a
+    named = _resolve_rules(n_in, x0, sphere_set, damping, max_iters, posture_weight, q_ref, collision_weight, link_names, target_pos,
+                           target_rot, pos_weight, rot_weight, tol, max_step, limits)
+    for n in link_names or ():
+        kin.body_frame_index(n)  # ValueError on an unknown link
+    pairs_b, named_b = _cross_resolve_rules(side_b, x0, sphere_set.n_sphere, cross_margin, w_x, other_pos, other_rot, cross_weight)
+    pairs = _check(n_in, n_fixed, kin, robot, x0, fixed_qpos, sphere_set, what, margin, pair_weight, penalty=True)  # (ends with the device)
+    for name, t in named + named_b:
+        if t.device != x0.device:
+            raise ValueError(f"{name} is on {t.device}, {what} on {x0.device}: all tensors must be on one CUDA device")
+    B = x0.shape[0]
+    xc, fixed = _inputs(x0, fixed_qpos)
+    xb, fixed_b = _inputs(side_b[4], side_b[5])
+    c = lambda a: None if a is None else a.detach().contiguous()  # noqa: E731
+    xr, tp, tr, wl, wa, pw, op, orot, xw = (c(a) for a in (q_ref, target_pos, target_rot, pos_weight, rot_weight, pair_weight, other_pos, other_rot,
+                                                          cross_weight))
+    lo, hi = (None, None) if limits is None else (limits.detach()[:, 0].contiguous(), limits.detach()[:, 1].contiguous())
+    ptr = lambda a: 0 if a is None else a.data_ptr()  # noqa: E731
+    with torch.cuda.device(x0.device):
+        if isinstance(posture_weight, torch.Tensor):
+            u = c(posture_weight)
+        else:
+            u = None if not posture_weight else torch.full((n_in,), float(posture_weight), dtype=torch.float32, device=x0.device)
+        model = model_of(sphere_set, pairs, tuple(link_names or ()))
+        model_b = side_b[8](side_b[6], pairs_b)
+        q = torch.empty((B, model.n_in), dtype=torch.float32, device=x0.device)
+        iters = torch.empty((B,), dtype=torch.int32, device=x0.device)
+        energy = torch.empty((B, 4), dtype=torch.float32, device=x0.device)
+        status = torch.empty((B,), dtype=torch.int32, device=x0.device)
+        if B > 0:
+            model.resolve_cross_dev(model_b, B, xc.data_ptr(), ptr(fixed), xb.data_ptr(), ptr(fixed_b), float(margin), float(damping),
+                                    int(max_iters), q.data_ptr(), iters.data_ptr(), energy.data_ptr(), status.data_ptr(), x_ref_ptr=ptr(xr),
+                                    posture_weight_ptr=ptr(u), n_target=len(link_names or ()), target_pos_ptr=ptr(tp), target_rot_ptr=ptr(tr),
+                                    pos_weight_ptr=ptr(wl), rot_weight_ptr=ptr(wa), collision_weight=float(collision_weight),
+                                    pair_weight_ptr=ptr(pw), lo_ptr=ptr(lo), hi_ptr=ptr(hi), tol=float(tol), max_step=float(max_step),
+                                    other_pos_ptr=ptr(op), other_rot_ptr=ptr(orot), cross_margin=None if cross_margin is None else float(cross_margin),
+                                    cross_weight=float(w_x), cross_pair_weight_ptr=ptr(xw), stream=torch.cuda.current_stream(x0.device).cuda_stream)
+    return q, iters, energy, status
+
+
+def resolve_cross_collisions(optimizer_a, q0_a, spheres_a: SphereSet, optimizer_b, q_b, spheres_b: SphereSet, margin, cross_margin=None,
+                             other_pos=None, other_rot=None, cross_weight=None, pair_weight=None, w_x=1.0, damping=_REQUIRED,
+                             max_iters=_REQUIRED, posture_weight=None, q_ref=None, collision_weight=1.0, link_names=None, target_pos=None,
+                             target_rot=None, pos_weight=None, rot_weight=None, tol=0.0, max_step=0.0, limits=None, fixed_qpos_a=None,
+                             fixed_qpos_b=None):
+    """`resolve_self_collision` for robot A against a SECOND ROBOT held still: B stays at q_b (B, n_opt_b) with the pose other_pos
+    (B, 3), other_rot (B, 3, 3) of its root IN A'S ROOT FRAME per frame (None: zero translation / identity) and acts as a body made of
+    its spheres.  ONE launch descends on
+
+        E = E of resolve_self_collision (A) + w_x * sum_s sum_t w_st max(0, cross_margin - d_st)^2
+
+    over every sphere s of A and t of B, the energy of `cross_penalty`; only A's variables move.  cross_margin: a Python float >= 0
+    or None (margin); cross_weight (S_a, S_b) float32 >= 0 or None (1), a zero masks a pair; w_x a Python float >= 0.  Every other
+    argument, the accept / reject rule and the damping are those of `resolve_self_collision`, for A.  -> (q (B, n_opt_a) float32,
+    iters (B) int32, energy (B, 4) float32: pose, posture, self-collision and the cross term at q, status (B) int32).  The curvature
+    uses the first 256 active contacts in the order of A's spheres, then B's; a point with more sets
+    _lib.RESOLVE_CONTACTS_TRUNCATED.  B's pair list plays no part; the two optimisers may be one.  No autograd graph."""
+    return _resolve_cross(_optimizer_side(optimizer_a, q0_a, spheres_a, fixed_qpos_a, "a"), _optimizer_side(optimizer_b, q_b, spheres_b, fixed_qpos_b, "b"),
+                          margin, cross_margin, other_pos, other_rot, cross_weight, pair_weight, w_x, damping, max_iters, posture_weight, q_ref,
+                          collision_weight, link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits)
+
+
+def robot_resolve_cross_collisions(robot_a, qpos0_a, spheres_a: SphereSet, robot_b, qpos_b, spheres_b: SphereSet, margin, cross_margin=None,
+                                   other_pos=None, other_rot=None, cross_weight=None, pair_weight=None, w_x=1.0, damping=_REQUIRED,
+                                   max_iters=_REQUIRED, posture_weight=None, q_ref=None, collision_weight=1.0, link_names=None, target_pos=None,
+                                   target_rot=None, pos_weight=None, rot_weight=None, tol=0.0, max_step=0.0, limits=None):
+    """The same for full robot qpos (B, robot.dof) in dof order; every joint is a column of its own, limits (robot_a.dof, 2)."""
+    return _resolve_cross(_robot_side(robot_a, qpos0_a, spheres_a, "a"), _robot_side(robot_b, qpos_b, spheres_b, "b"), margin, cross_margin,
+                          other_pos, other_rot, cross_weight, pair_weight, w_x, damping, max_iters, posture_weight, q_ref, collision_weight,
+                          link_names, target_pos, target_rot, pos_weight, rot_weight, tol, max_step, limits)
+
+
+def relative_pose(pos_a, rot_a, pos_b, rot_b):
+    """the pose of B's root in A's root frame from two world poses, in torch on their device: (rot_a^T (pos_b - pos_a), rot_a^T rot_b)."""
+    rt = rot_a.transpose(1, 2)
+    return (rt @ (pos_b - pos_a).unsqueeze(-1)).squeeze(-1).contiguous(), (rt @ rot_b).contiguous()
+
+
+def resolve_bimanual_collisions(optimizer_a, q_a, spheres_a: SphereSet, optimizer_b, q_b, spheres_b: SphereSet, margin, pos_a, rot_a, pos_b,
+                                rot_b, sweeps=1, cross_margin=None, cross_weight=None, w_x=1.0, damping=_REQUIRED, max_iters=_REQUIRED,
+                                args_a=None, args_b=None, fixed_qpos_a=None, fixed_qpos_b=None):
+    """Two robots with world poses pos_* (B, 3), rot_* (B, 3, 3) float32 CUDA, both free: per sweep `resolve_cross_collisions` of A
+    against B held, then of B against the new A, each in its own root frame (the relative pose and its inverse are formed in torch on
+    the device: no host synchronisation between the launches).  args_a / args_b: dicts of the remaining keyword arguments of
+    `resolve_self_collision` for that robot alone -- pair_weight, posture_weight, q_ref, collision_weight, link_names, target_pos,
+    target_rot, pos_weight, rot_weight, tol, max_step, limits; each robot keeps its own self-pair list, limits, references and
+    targets.  Both launches of a sweep use the same cross_weight (S_a, S_b) (transposed for the second), cross_margin and w_x, so the
+    cross term is ONE symmetric energy: the sum of both robots' energies with the cross term counted once cannot rise from sweep
+    to sweep.  -> ((q_a, iters_a, energy_a, status_a), (q_b, iters_b, energy_b, status_b)) of the last sweep."""
+    import torch
+
+    if isinstance(sweeps, bool) or not isinstance(sweeps, int) or sweeps < 1:
+        raise ValueError(f"sweeps must be a Python int >= 1, got {sweeps!r}")
+    args_a, args_b = dict(args_a or {}), dict(args_b or {})
+    own = {"pair_weight", "posture_weight", "q_ref", "collision_weight", "link_names", "target_pos", "target_rot", "pos_weight", "rot_weight", "tol",
+           "max_step", "limits"}
+    for name, a in (("args_a", args_a), ("args_b", args_b)):
+        if set(a) - own:
+            raise ValueError(f"{name} holds {sorted(set(a) - own)}: it takes {sorted(own)}")
+    B = q_a.shape[0] if isinstance(q_a, torch.Tensor) and q_a.ndim == 2 else None
+    for name, t, shape in (("pos_a", pos_a, (B, 3)), ("rot_a", rot_a, (B, 3, 3)), ("pos_b", pos_b, (B, 3)), ("rot_b", rot_b, (B, 3, 3))):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if B is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+    if isinstance(cross_weight, torch.Tensor) and cross_weight.ndim != 2:
+        raise ValueError(f"cross_weight must have shape (S_a, S_b), got {tuple(cross_weight.shape)}")
+    ab = relative_pose(pos_a, rot_a, pos_b, rot_b)  # B in A's root frame
+    ba = relative_pose(pos_b, rot_b, pos_a, rot_a)  # A in B's
+    wt = cross_weight.t().contiguous() if isinstance(cross_weight, torch.Tensor) else cross_weight
+    if args_a.get("q_ref") is None:
+        args_a["q_ref"] = q_a  # the posture term refers to the first point in every sweep: one energy
+    if args_b.get("q_ref") is None:
+        args_b["q_ref"] = q_b
+    ra = rb = None
+    for _ in range(sweeps):
+        ra = resolve_cross_collisions(optimizer_a, q_a, spheres_a, optimizer_b, q_b, spheres_b, margin, cross_margin, ab[0], ab[1], cross_weight,
+                                      w_x=w_x, damping=damping, max_iters=max_iters, fixed_qpos_a=fixed_qpos_a, fixed_qpos_b=fixed_qpos_b, **args_a)
+        q_a = ra[0]
+        rb = resolve_cross_collisions(optimizer_b, q_b, spheres_b, optimizer_a, q_a, spheres_a, margin, cross_margin, ba[0], ba[1], wt,
+                                      w_x=w_x, damping=damping, max_iters=max_iters, fixed_qpos_a=fixed_qpos_b, fixed_qpos_b=fixed_qpos_a, **args_b)
+        q_b = rb[0]
+    return ra, rb
+
+
 __all__ = ["SphereSet", "default_pairs", "sphere_distances", "self_collision_penalty", "robot_sphere_distances",
            "robot_self_collision_penalty", "resolve_self_collision", "robot_resolve_self_collision", "ObstacleSet", "obstacle_distances",
            "obstacle_penalty", "robot_obstacle_distances", "robot_obstacle_penalty", "resolve_collisions", "robot_resolve_collisions", "SdfGrid",
            "grid_distances", "grid_penalty", "robot_grid_distances", "robot_grid_penalty", "resolve_grid_collisions",
            "robot_resolve_grid_collisions", "TriangleMesh", "mesh_distances", "SceneBody", "resolve_scene_collisions",
-           "robot_resolve_scene_collisions", "cross_distances", "cross_penalty", "robot_cross_distances", "robot_cross_penalty"]
+           "robot_resolve_scene_collisions", "cross_distances", "cross_penalty", "robot_cross_distances", "robot_cross_penalty",
+           "resolve_cross_collisions", "robot_resolve_cross_collisions", "relative_pose", "resolve_bimanual_collisions"]

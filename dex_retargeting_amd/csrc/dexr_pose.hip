@@ -2058,5 +2058,8 @@ int dexr_link_ik_solve(const dexr_pose_model* m, int64_t B, const double* x0, co
 // ---- include/dexr_cross.h: the spheres of one posed robot against another's, both walks and every pair from both ends in one block --
 #include "dexr_cross.hpp"
 
+// ---- include/dexr_resolve_cross.h: the posture solve against a second posed robot, the two-robot term inside the resident loop ------
+#include "dexr_resolve_cross.hpp"
+
 // ---- include/dexr_mesh_sdf.h: signed distances of points and grid samples to a triangle mesh, the sampler in front of the grids ----
 #include "dexr_mesh_sdf.hpp"
