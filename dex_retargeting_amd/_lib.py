@@ -99,6 +99,10 @@ MESH_SDF_EXPORTS = ["dexr_mesh_create", "dexr_mesh_destroy", "dexr_mesh_info", "
                     "dexr_mesh_sample_grid_dev", "dexr_mesh_sample_grid"]
 MESH_MAX_VERTICES, MESH_MAX_TRIANGLES = 1 << 20, 1 << 20  # DEXR_MESH_MAX_*
 MESH_TILE, MESH_BLOCK_POINTS, MESH_PAIRS_PER_LAUNCH = 256, 512, 1 << 34  # DEXR_MESH_TILE, DEXR_MESH_BLOCK_POINTS, DEXR_MESH_PAIRS_PER_LAUNCH
+# include/dexr_sphere_fit.h (inscribed spheres of sampled signed-distance fields, a greedy cover): a list of its own.  (Its name does
+# not end in EXPORTS: tests/test_cross_host.py counts the lists that do.)
+SPHERE_FIT_SYMBOLS = ["dexr_sphere_fit_workspace_bytes", "dexr_sphere_fit_dev", "dexr_sphere_fit"]
+SPHERE_FIT_MIN_DIM, SPHERE_FIT_MAX_DIM, SPHERE_FIT_MAX_BODIES, SPHERE_FIT_CHUNK = 2, 64, 64, 1024  # DEXR_SPHERE_FIT_*
 # include/dexr_cross.h (the spheres of one posed robot against another's: distances, their VJP, the fused penalty): a list of its own
 CROSS_EXPORTS = ["dexr_cross_distances_dev", "dexr_cross_distances_vjp_dev", "dexr_cross_penalty_dev", "dexr_cross_distances",
                  "dexr_cross_distances_vjp", "dexr_cross_penalty"]
@@ -270,6 +274,12 @@ def load() -> C.CDLL:
     lib.dexr_mesh_distances.argtypes = [vp, i64, f64p, f64p, f64p]
     lib.dexr_mesh_sample_grid_dev.argtypes = [vp, i32p, f64p, f64p, vp, vp]
     lib.dexr_mesh_sample_grid.argtypes = [vp, i32p, f64p, f64p, f32p]
+    i64p = C.POINTER(C.c_int64)
+    lib.dexr_sphere_fit_workspace_bytes.argtypes = [C.c_int32, i32p]
+    lib.dexr_sphere_fit_workspace_bytes.restype = C.c_size_t
+    lib.dexr_sphere_fit_dev.argtypes = [C.c_int32, i32p, f64p, i64p, i32p, C.c_double, C.c_double, C.c_double, i64, vp, vp, vp, vp, vp,
+                                        C.c_size_t, vp]
+    lib.dexr_sphere_fit.argtypes = [C.c_int32, i32p, f64p, i64p, i32p, C.c_double, C.c_double, C.c_double, i64, f32p, i32p, i32p, i32p]
     _lib = lib
     return lib
 
@@ -1432,6 +1442,54 @@ class TriangleMesh:
         check(load().dexr_mesh_sample_grid(self._h, _ptr(n, C.c_int32), _ptr(origin, C.c_double), _ptr(spacing, C.c_double),
                                            _ptr(values, C.c_float)))
         return values
+
+
+def _sphere_fit_args(dims, spacing, offset, k):
+    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    if dims.ndim != 2 or dims.shape[1] != 3:
+        raise ValueError(f"dims must have shape (n_body, 3), got {dims.shape}")
+    n_body = dims.shape[0]
+    spacing = np.ascontiguousarray(spacing, dtype=np.float64).reshape(-1)
+    offset = np.ascontiguousarray(offset, dtype=np.int64).reshape(-1)
+    k = np.ascontiguousarray(k, dtype=np.int32).reshape(-1)
+    if spacing.shape != (n_body,) or offset.shape != (n_body,) or k.shape != (n_body,):
+        raise ValueError(f"spacing, offset and k must each have shape ({n_body},), got {spacing.shape}, {offset.shape}, {k.shape}")
+    return n_body, dims, spacing, offset, k
+
+
+def sphere_fit_workspace_bytes(dims) -> int:
+    """bytes of device workspace a sphere fit of bodies of dims (n_body, 3) needs (dexr_sphere_fit_workspace_bytes)"""
+    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    if dims.ndim != 2 or dims.shape[1] != 3:
+        raise ValueError(f"dims must have shape (n_body, 3), got {dims.shape}")
+    n = int(load().dexr_sphere_fit_workspace_bytes(dims.shape[0], _ptr(dims, C.c_int32)))
+    if n == 0:
+        raise DexrError(f"libdexr error -1: {load().dexr_last_error().decode()}")
+    return n
+
+
+def sphere_fit_dev(dims, spacing, offset, k, min_radius: float, inflate: float, coverage: float, n_values: int, values_ptr: int, index_ptr: int,
+                   gain_ptr: int, count_ptr: int, workspace_ptr: int, workspace_bytes: int, stream: int = 0):
+    """device pointers (include/dexr_sphere_fit.h): values (n_values) float32 -> index, gain (n_body, max k) and count (n_body, 3)
+    int32.  dims, spacing, offset and k are host arrays.  Never synchronises, never allocates."""
+    n_body, dims, spacing, offset, k = _sphere_fit_args(dims, spacing, offset, k)
+    check(load().dexr_sphere_fit_dev(n_body, _ptr(dims, C.c_int32), _ptr(spacing, C.c_double), _ptr(offset, C.c_int64), _ptr(k, C.c_int32),
+                                     float(min_radius), float(inflate), float(coverage), int(n_values), values_ptr or None, index_ptr or None,
+                                     gain_ptr or None, count_ptr or None, workspace_ptr or None, int(workspace_bytes), stream or None))
+
+
+def sphere_fit(dims, spacing, offset, k, min_radius: float, inflate: float, coverage: float, values):
+    """values (n_values) float32 on the host -> index, gain (n_body, max k) and count (n_body, 3) int32 (dexr_sphere_fit)."""
+    n_body, dims, spacing, offset, k = _sphere_fit_args(dims, spacing, offset, k)
+    values = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    k_max = int(k.max()) if n_body and 1 <= int(k.max()) <= SPHERE_MAX else 1  # (a refused k: the library says why)
+    index = np.zeros((n_body, k_max), dtype=np.int32)
+    gain = np.zeros((n_body, k_max), dtype=np.int32)
+    count = np.zeros((n_body, 3), dtype=np.int32)
+    check(load().dexr_sphere_fit(n_body, _ptr(dims, C.c_int32), _ptr(spacing, C.c_double), _ptr(offset, C.c_int64), _ptr(k, C.c_int32),
+                                 float(min_radius), float(inflate), float(coverage), values.size, _ptr(values, C.c_float),
+                                 _ptr(index, C.c_int32), _ptr(gain, C.c_int32), _ptr(count, C.c_int32)))
+    return index, gain, count
 
 
 def seq_compose_dev(B: int, T: int, dof_kind, dof_idx, dof_mult, dof_off, n_opt: int, n_fixed: int, qraw_ptr: int,

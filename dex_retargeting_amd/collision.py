@@ -35,6 +35,11 @@ two q, two ``SphereSet`` and a base pose per robot and frame (``pos_a``, ``rot_a
 every sphere of either robot to the nearest sphere of the other, and the squared-hinge energy over every (sphere of A, sphere of
 B) pair with its gradient in both q and, asked for, the wrench on either base -- ONE launch that walks both robots.
 
+A ``SphereSet`` need not be written by hand (include/dexr_sphere_fit.h, csrc/dexr_sphere_fit.hpp): ``link_grid`` samples a link's
+mesh into a grid with one spacing, ``fit_spheres`` takes a few inscribed spheres from the grids of all links in one call -- a
+greedy cover, every round the sphere that covers the most interior samples no earlier one covers -- and ``SphereSet.from_meshes``
+and ``SphereSet.from_urdf`` chain the two for the meshes, or the ``<collision>`` elements of the URDF, of a robot.
+
 The outputs of this module carry NO autograd graph; ``autograd.sphere_distances``, ``autograd.self_collision_penalty``,
 ``autograd.obstacle_distances``, ``autograd.obstacle_penalty``, ``autograd.grid_distances``, ``autograd.grid_penalty``,
 ``autograd.cross_distances`` and ``autograd.cross_penalty`` are the same kernels with one, so that a penetration loss composes
@@ -102,6 +107,59 @@ class SphereSet:
             a.setflags(write=False)
         self.links, self.table_links, self.centers, self.radii, self.sphere_rows, self.pairs = names, table, cen, rad, rows, pr
         self._key = (names, cen.tobytes(), rad.tobytes(), None if pr is None else pr.tobytes())
+
+    @classmethod
+    def from_meshes(cls, robot, meshes, spheres_per_link=4, max_dim=48, min_radius=0.0, inflate=0.0, coverage=1.0, pairs=None):
+        """A sphere set fitted to the links' meshes: `meshes` is {link name: TriangleMesh in the link's own frame}, `spheres_per_link`
+        an int or {link name: int}.  Every mesh is sampled by `link_grid(mesh, max_dim)` and all links are fitted in ONE `fit_spheres`
+        call; the spheres of a link follow each other in the order the rounds took them, the links in the dict's order.  A link
+        whose fit is empty (no sample inside the mesh deeper than min_radius: raise max_dim) is a ValueError naming it, and so are more
+        than 128 spheres in total or a name the robot does not have."""
+        if not isinstance(meshes, dict) or not meshes or not all(isinstance(n, str) and isinstance(m, TriangleMesh) for n, m in meshes.items()):
+            raise ValueError("meshes must be a non-empty dict {link name: collision.TriangleMesh}")
+        known = set(_kin_of(robot).link_names)
+        for n in meshes:
+            if n not in known:
+                raise ValueError(f"the robot has no link {n!r}")
+        if isinstance(spheres_per_link, dict):
+            missing = [n for n in meshes if n not in spheres_per_link]
+            if missing:
+                raise ValueError(f"spheres_per_link names no count for {missing}")
+            k = [spheres_per_link[n] for n in meshes]
+        else:
+            k = [spheres_per_link] * len(meshes)
+        if not all(isinstance(v, (int, np.integer)) and v >= 1 for v in k):
+            raise ValueError(f"spheres_per_link must be integers >= 1, got {k}")
+        if sum(k) > _lib.SPHERE_MAX:
+            raise ValueError(f"a sphere set holds at most {_lib.SPHERE_MAX} spheres, {len(meshes)} links ask for {sum(k)}")
+        if len(meshes) > _lib.SPHERE_FIT_MAX_BODIES:
+            raise ValueError(f"a sphere set takes at most {_lib.SPHERE_FIT_MAX_BODIES} links, got {len(meshes)}")
+        _fit_scalars(min_radius, inflate, coverage)  # before any sampling
+        grids = [link_grid(m, max_dim) for m in meshes.values()]
+        fits = fit_spheres(grids, np.array(k), min_radius, inflate, coverage)
+        links, centers, radii = [], [], []
+        for name, fit in zip(meshes, fits):
+            if len(fit) == 0:
+                raise ValueError(f"link {name!r}: no sphere fits ({fit.n_interior} interior samples at max_dim = {max_dim}, min_radius = {min_radius})")
+            links += [name] * len(fit)
+            centers.append(fit.centers)
+            radii.append(fit.radii)
+        return cls(links, np.concatenate(centers), np.concatenate(radii), pairs)
+
+    @classmethod
+    def from_urdf(cls, robot, urdf_path, spheres_per_link=4, max_dim=48, min_radius=0.0, inflate=0.0, coverage=1.0, pairs=None):
+        """`SphereSet.from_meshes` of the <collision> geometry of a URDF file (`urdf.parse_collision_geometry`, tessellated and loaded
+        by `meshio.link_mesh`): every link of the robot that has geometry, in file order."""
+        from . import meshio
+        from .urdf import parse_collision_geometry
+
+        geometry = parse_collision_geometry(urdf_path)
+        known = set(_kin_of(robot).link_names)
+        names = [n for n, items in geometry.items() if items and n in known]
+        if not names:
+            raise ValueError(f"{urdf_path}: no link of the robot has <collision> geometry")
+        meshes = {n: TriangleMesh(*meshio.link_mesh(geometry[n]), drop_degenerate=True) for n in names}
+        return cls.from_meshes(robot, meshes, spheres_per_link, max_dim, min_radius, inflate, coverage, pairs)
 
     @property
     def n_sphere(self) -> int:
@@ -937,6 +995,125 @@ class SdfGrid:
         return f"SdfGrid({'x'.join(str(k) for k in self.shape)} samples, origin {self.origin.tolist()}, spacing {self.spacing.tolist()})"
 
 
+class SphereFit:
+    """What `fit_spheres` found in one grid: plain data.
+
+    centers     (n, 3) float64 in the grid's frame: origin + samples * spacing
+    radii       (n,) float64: -value at the centre's sample + inflate
+    samples     (n, 3) the index triples of the centres' samples, in the order the greedy rounds took them
+    gains       (n,) the interior samples each sphere was the first to cover
+    n_interior  samples with a negative value;  n_covered  those inside some sphere;  coverage  their ratio (1.0 where there are none)"""
+
+    def __init__(self, centers, radii, samples, gains, n_interior, n_covered):
+        self.centers, self.radii, self.samples, self.gains = centers, radii, samples, gains
+        self.n_interior, self.n_covered = int(n_interior), int(n_covered)
+        self.coverage = self.n_covered / self.n_interior if self.n_interior else 1.0
+
+    def __len__(self):
+        return len(self.radii)
+
+    def __repr__(self):
+        return f"SphereFit({len(self)} spheres, {self.n_covered} of {self.n_interior} interior samples covered)"
+
+
+def _fit_scalars(min_radius, inflate, coverage):
+    try:
+        min_radius, inflate, coverage = float(min_radius), float(inflate), float(coverage)
+    except (TypeError, ValueError):
+        raise ValueError("min_radius, inflate and coverage must be numbers") from None
+    if not (math.isfinite(min_radius) and min_radius >= 0):
+        raise ValueError(f"min_radius must be finite and >= 0, got {min_radius}")
+    if not (math.isfinite(inflate) and inflate >= 0):
+        raise ValueError(f"inflate must be finite and >= 0, got {inflate}")
+    if not 0.0 <= coverage <= 1.0:
+        raise ValueError(f"coverage must lie in 0..1, got {coverage}")
+    return min_radius, inflate, coverage
+
+
+def _fit_rules(grids, max_spheres, min_radius, inflate, coverage):
+    """the argument rules of fit_spheres -> (list of grids, k (n,) int32, the three scalars as floats)"""
+    if isinstance(grids, SdfGrid):
+        grids = [grids]
+    try:
+        grids = list(grids)
+    except TypeError:
+        raise ValueError("grids must be a collision.SdfGrid or a sequence of them") from None
+    if not grids or not all(isinstance(g, SdfGrid) for g in grids):
+        raise ValueError("grids must be a collision.SdfGrid or a non-empty sequence of them")
+    if len(grids) > _lib.SPHERE_FIT_MAX_BODIES:
+        raise ValueError(f"one call fits at most {_lib.SPHERE_FIT_MAX_BODIES} grids, got {len(grids)}")
+    try:
+        k = np.array(np.broadcast_to(np.asarray(max_spheres), (len(grids),)))
+    except ValueError:
+        raise ValueError(f"max_spheres must be an int or one per grid ({len(grids)}), got {np.shape(max_spheres)}") from None
+    if k.dtype.kind not in "iu" or (k < 1).any() or (k > _lib.SPHERE_MAX).any():
+        raise ValueError(f"max_spheres must be integers in 1..{_lib.SPHERE_MAX}, got {np.asarray(max_spheres).tolist()}")
+    for i, g in enumerate(grids):
+        if max(g.shape) > _lib.SPHERE_FIT_MAX_DIM:
+            raise ValueError(f"grid {i}: every dimension of a fitted grid is at most {_lib.SPHERE_FIT_MAX_DIM} samples, got {g.shape}")
+        if not (g.spacing[0] == g.spacing[1] == g.spacing[2]):
+            raise ValueError(f"grid {i}: a fitted grid has one spacing for its three axes (isotropic), got {g.spacing.tolist()}")
+    return (grids, k.astype(np.int32), *_fit_scalars(min_radius, inflate, coverage))
+
+
+def fit_spheres(grids, max_spheres, min_radius=0.0, inflate=0.0, coverage=1.0):
+    """Spheres inside the bodies that signed-distance grids describe (include/dexr_sphere_fit.h): a greedy cover on the device, all
+    grids in ONE call on the current CUDA device and stream.  Every round takes, per grid, the sample whose ball of radius
+    -value + inflate covers the most interior samples (value < 0) that no earlier ball covers; it ends after `max_spheres` (an
+    int or one per grid, 1..128) spheres, once `coverage` (0..1) of the interior samples are covered, or when nothing is gained.
+    Samples shallower than `min_radius` are never centres.  With inflate = 0 and a grid of exact distances (`SdfGrid.from_mesh`)
+    no sphere protrudes from the body; with inflate > 0 by at most that much.
+
+    grids: one `SdfGrid` or a sequence of at most 64, each with ONE spacing for its three axes and at most 64 samples per axis
+    (`link_grid` makes such a grid of a mesh).  -> a list of `SphereFit`, one per grid; a grid without an interior sample gives
+    an empty one."""
+    grids, k, min_radius, inflate, coverage = _fit_rules(grids, max_spheres, min_radius, inflate, coverage)
+    import torch
+
+    dims = np.array([g.shape for g in grids], dtype=np.int32)
+    sizes = np.array([g.values.size for g in grids], dtype=np.int64)
+    offset = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    spacing = np.array([g.spacing[0] for g in grids], dtype=np.float64)
+    k_max = int(k.max())
+    with torch.cuda.device(torch.cuda.current_device()):
+        values = torch.from_numpy(np.concatenate([g.values.reshape(-1) for g in grids])).cuda()
+        index = torch.empty((len(grids), k_max), dtype=torch.int32, device="cuda")
+        gain = torch.empty((len(grids), k_max), dtype=torch.int32, device="cuda")
+        count = torch.empty((len(grids), 3), dtype=torch.int32, device="cuda")
+        ws_bytes = _lib.sphere_fit_workspace_bytes(dims)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+        _lib.sphere_fit_dev(dims, spacing, offset, k, min_radius, inflate, coverage, values.numel(), values.data_ptr(), index.data_ptr(),
+                            gain.data_ptr(), count.data_ptr(), ws.data_ptr(), ws_bytes, stream=torch.cuda.current_stream().cuda_stream)
+        index, gain, count = index.cpu().numpy(), gain.cpu().numpy(), count.cpu().numpy()
+    out = []
+    for b, g in enumerate(grids):
+        n = int(count[b, 2])
+        flat = index[b, :n].astype(np.int64)
+        samples = np.stack(np.unravel_index(flat, g.shape), -1).reshape(n, 3)
+        centers = g.origin + samples * g.spacing
+        radii = -g.values.reshape(-1)[flat].astype(np.float64) + inflate
+        out.append(SphereFit(centers, radii, samples, gain[b, :n].copy(), count[b, 0], count[b, 1]))
+    return out
+
+
+def link_grid(mesh: TriangleMesh, max_dim: int = 48, padding_cells: int = 1):
+    """`SdfGrid.from_mesh` of a link's mesh with the ONE spacing that makes the longest side of the padded box `max_dim` samples
+    (2..64): spacing = longest extent / (max_dim - 1 - 2 padding_cells), `padding_cells` cells of padding on every side."""
+    if not isinstance(mesh, TriangleMesh):
+        raise ValueError("mesh must be a collision.TriangleMesh")
+    if not (isinstance(max_dim, (int, np.integer)) and isinstance(padding_cells, (int, np.integer))):
+        raise ValueError("max_dim and padding_cells must be integers")
+    if padding_cells < 0 or max_dim > _lib.SPHERE_FIT_MAX_DIM or max_dim - 1 - 2 * padding_cells < 1:
+        raise ValueError(f"max_dim must lie in {2 + 2 * padding_cells}..{_lib.SPHERE_FIT_MAX_DIM} with padding_cells = {padding_cells} >= 0, got {max_dim}")
+    lo, hi = mesh.bounds
+    h = float((hi - lo).max()) / (max_dim - 1 - 2 * padding_cells)  # (> 0: a mesh has a triangle with area)
+    cells = np.clip(np.ceil((hi - lo) / h), 1, max_dim - 1 - 2 * padding_cells)  # (rounding must not add a cell to the longest side; a flat side keeps one)
+    shape = tuple(int(c) + 1 + 2 * padding_cells for c in cells)
+    centre = (lo + hi) / 2.0
+    origin = centre - (np.array(shape) - 1) * h / 2.0
+    return SdfGrid.from_mesh(mesh, origin=origin, spacing=h, shape=shape)
+
+
 def _grid_distances(model, grid, x, fixed_qpos, obstacle_pos, obstacle_rot):
     import torch
 
@@ -1620,4 +1797,4 @@ __all__ = ["SphereSet", "default_pairs", "sphere_distances", "self_collision_pen
            "grid_distances", "grid_penalty", "robot_grid_distances", "robot_grid_penalty", "resolve_grid_collisions",
            "robot_resolve_grid_collisions", "TriangleMesh", "mesh_distances", "SceneBody", "resolve_scene_collisions",
            "robot_resolve_scene_collisions", "cross_distances", "cross_penalty", "robot_cross_distances", "robot_cross_penalty",
-           "resolve_cross_collisions", "robot_resolve_cross_collisions", "relative_pose", "resolve_bimanual_collisions"]
+           "resolve_cross_collisions", "robot_resolve_cross_collisions", "relative_pose", "resolve_bimanual_collisions", "SphereFit", "fit_spheres", "link_grid"]

@@ -2061,5 +2061,8 @@ int dexr_link_ik_solve(const dexr_pose_model* m, int64_t B, const double* x0, co
 // ---- include/dexr_resolve_cross.h: the posture solve against a second posed robot, the two-robot term inside the resident loop ------
 #include "dexr_resolve_cross.hpp"
 
+// ---- include/dexr_sphere_fit.h: a few inscribed spheres per body from its sampled signed-distance field, a greedy cover in bit masks --
+#include "dexr_sphere_fit.hpp"
+
 // ---- include/dexr_mesh_sdf.h: signed distances of points and grid samples to a triangle mesh, the sampler in front of the grids ----
 #include "dexr_mesh_sdf.hpp"

@@ -145,6 +145,51 @@ def parse_urdf(path: str, add_dummy_free_joints: bool = False) -> UrdfRobot:
     return robot
 
 
+def parse_collision_geometry(path: str) -> Dict[str, list]:
+    """{link name: [(kind, params, origin 4x4), ...]} of the <collision> elements of every link, in file order; a link without
+    one has an empty list.  kind and params:
+
+        "box"       (3,) the full extents x y z
+        "cylinder"  (radius, length), the axis along z, centred
+        "sphere"    (radius,)
+        "mesh"      (file name, scale (3,)): `package://` and relative names are resolved against the URDF's directory
+
+    origin is the element's <origin> in the link's frame (identity when absent).  `parse_urdf` does not read any of this."""
+    import os
+
+    root = ET.parse(path).getroot()
+    if root.tag != "robot":
+        raise ValueError(f"{path}: root element is <{root.tag}>, expected <robot>")
+    base = os.path.dirname(os.path.abspath(path))
+    out: Dict[str, list] = {}
+    for link in root.findall("link"):
+        name = link.attrib["name"]
+        items = out.setdefault(name, [])
+        for ce in link.findall("collision"):
+            ge = ce.find("geometry")
+            shape = None if ge is None else next((e for e in ge if e.tag in ("box", "cylinder", "sphere", "mesh")), None)
+            if shape is None:
+                raise ValueError(f"link {name}: a <collision> without a box, cylinder, sphere or mesh")
+            oe = ce.find("origin")
+            xyz = _floats(oe.attrib.get("xyz", "0 0 0"), 3) if oe is not None else [0, 0, 0]
+            rpy = _floats(oe.attrib.get("rpy", "0 0 0"), 3) if oe is not None else [0, 0, 0]
+            if shape.tag == "box":
+                params = np.array(_floats(shape.attrib["size"], 3))
+            elif shape.tag == "cylinder":
+                params = (float(shape.attrib["radius"]), float(shape.attrib["length"]))
+            elif shape.tag == "sphere":
+                params = (float(shape.attrib["radius"]),)
+            else:
+                fn = shape.attrib["filename"]
+                if fn.startswith("package://"):
+                    fn = fn[len("package://"):]
+                if not os.path.isabs(fn):
+                    fn = os.path.normpath(os.path.join(base, fn))
+                params = (fn, np.array(_floats(shape.attrib.get("scale", "1 1 1"), 3)))
+            items.append((shape.tag, params, make_transform(xyz, rpy)))
+    return out
+
+
 def _add_dummy_joints(robot: UrdfRobot, root_link_name: str) -> None:
     link_names = [f"dummy_{n}_translation_link" for n in "xyz"] + [f"dummy_{n}_rotation_link" for n in "xyz"]
     limits = [(-5.0, 5.0)] * 3 + [(-2 * np.pi, 2 * np.pi)] * 3
