@@ -562,7 +562,9 @@ int launch(const dexr_model* m, int mode, int f64, dexr::KernelParams kp, hipStr
   // dispatcher places the chip's first two waves per SIMD within ~4 us and needs another ~12 us for the third and fourth
   // (tools/wave_trace.sh); with half as many workgroups to place the launch of 65 536 Allegro frames takes 45.0 instead of
   // 47.5 us (16 waves per block: 47.9; 1 wave per block: 52.3).  Smaller launches are faster in blocks of 4 (16 384 frames:
-  // 27.2 vs 33.3 us), so the policy is by size.
+  // 27.2 vs 33.3 us), so the policy is by size.  (From about this size on, up to four generations of waves, the kernel's waves steer
+  // their issue priority: it forms its own condition from the grid it sees -- blocks x waves per block, i.e. this count rounded up to
+  // whole blocks and after the LDS cap below -- DEXR_TIP_PRIO_MIN_WAVES in dexr_tip_solve.hpp.  Where the two differ, only speed does.)
   if (tip_kernel && !f64 && (kp.B + 63) / 64 * kp.n_comp >= 4096) wpb = DEXR_TIP_WPB_BIG;
   // (float64 tip kernel: 14.8 KB per wave with the parked model -- blocks of FOUR waves all the same (59 KB, two blocks per CU): the
   // four finger components of a tile of frames read the same keypoint / last_qpos lines, and in blocks of two they sat on different
@@ -598,7 +600,7 @@ int launch(const dexr_model* m, int mode, int f64, dexr::KernelParams kp, hipStr
   const int64_t blocks = (waves + wpb - 1) / wpb;
   if (blocks > 0x7fffffffLL) return fail(DEXR_ERR_INVALID, "batch too large for one launch");
   dexr::launch_fn fn = dexr::find_launcher(m->bucket, f64, mode, m->chain, ext, m->tip);
-#if !defined(DEXR_SMALL_PROF) && !defined(DEXR_WAVE_TRACE)  // (the profiling hooks live in dexr_kernel)
+#if !defined(DEXR_SMALL_PROF)  // (the stage-cycle hooks live in dexr_kernel only; the wave trace is in both kernels)
   // A plain tile launch of the float32 tip kernel -- every lane gets its one frame on entry; no queue, no sequence, no fleet
   // addressing, no objective values, no float64 hooks -- runs dexr_tip32_kernel (dexr_tip_solve.hpp): the same pass without
   // the persistent-lane loop's bookkeeping, bitwise the same answers.  dexr_tuning.kernel = DEXR_KERNEL_REGISTER_CHAIN keeps

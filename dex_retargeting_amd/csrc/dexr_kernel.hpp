@@ -146,7 +146,7 @@ struct WideTable {
 // records, on the 100 MHz wall clock (s_memrealtime: one time base for all XCDs), when it started, when its first frames
 // were loaded, the end of each of its first 16 passes, when it retired, how many passes it ran and where it ran
 // (HW_ID / XCC_ID): 24 doubles per wave in kp.g64out -- what a launch's duration is made of (dispatch ramp, first loads,
-// passes under contention, tail).
+// passes under contention, tail).  dexr_tip32_kernel (dexr_tip_solve.hpp) carries the same stamps in the same layout.
 #ifdef DEXR_WAVE_TRACE
 #define WTRACE_DECL long long wt_t0 = wall_clock64(), wt_t1 = 0, wt_p[16]; int wt_n = 0;
 #define WTRACE_LOADED() if (wt_t1 == 0) wt_t1 = wall_clock64();

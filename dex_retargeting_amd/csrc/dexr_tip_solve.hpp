@@ -15,6 +15,8 @@
 //             (a) damped 4 x 4 step from the kept model, (b) tip_eval at the trial point unless every live lane takes its
 //             blind last step, (c) accept / reject / damping / termination, (d) finished lanes store and drop out;
 //             the wave leaves when no lane holds a frame.
+//   priority  in launches that fill the chip four waves per SIMD a wave's issue priority falls with the passes it has done and
+//             ends higher in the late-placed half of the grid (DEXR_TIP_PRIO below): scheduling only.
 // Every floating-point operation the answer depends on is the one dexr_kernel does, on the same operands in the same order
 // (steps (2)-(5) of its loop with optmask = all four joints, has && !fresh = has); qpos, status and iters are bitwise
 // those of dexr_kernel (tests/test_gpu_tip32_kernel.py).  Calls that need anything else -- queue mode, sequences, fleet
@@ -69,6 +71,75 @@ static __device__ __forceinline__ bool tip32_chol(float (&H)[10], const float (&
   return ok;
 }
 
+// Issue priority of a wave among the (up to four) waves of its SIMD.  A SIMD issues by priority, then by age, and the workgroup
+// dispatcher places a full chip's third and fourth wave per SIMD microseconds after the first two: at equal priority the young
+// waves run after the old ones rather than beside them, and a slow frame in a young wave starts its passes late.  The policy is a
+// handful of s_setprio behind wave-uniform scalar conditions; no floating-point operation or operand depends on any of it.
+// DEXR_TIP_PRIO is a sum of the bits below (-DDEXR_TIP_PRIO=... through DEXR_EXTRA_FLAGS, tools/build_variant.sh);
+// -DDEXR_TIP_PRIO=0 is the kernel without any of it, the A/B partner.  What each variant measured: DESIGN.md 4.1,
+// profiles/r18_tip32_priority_ab.txt.
+//   LADDER    priority 3 from entry through the adopted start-point model and the first pass of the loop, 2 in the second
+//             pass, 1 in the third, 0 from the fourth on: it falls with the passes a wave has done.  One counter in a scalar
+//             register, one scalar compare per pass once the ladder is through
+//   LATE      waves of blocks in the second half of the grid take priority 1 on entry and keep it (leans on dispatch following
+//             the block index, which HIP does not promise: where it does not, this costs speed and nothing else)
+//   PROLOGUE  priority 3 until the frame has arrived and the start point is evaluated, then 0
+//   TAIL      (with LADDER) priority 3 again DEXR_TIP_PRIO_TAIL_AFTER passes after the ladder's end, i.e. from the seventh pass
+//             on (the late half: the eighth): the few waves still running then hold the launch's slowest frames.  Alone on the
+//             chip they gain nothing; when the next launch of another stream arrives beside them at priority 3, equal priority
+//             lets their age win instead of starving them
+// LADDER + LATE + TAIL is the default: the ladder, which ends on 1 instead of 0 in the late half, and the tail rung.
+// The policy applies to launches of DEXR_TIP_PRIO_MIN_WAVES waves or more -- the launches that fill the chip four waves per
+// SIMD, the condition launch() (dexr_api.hip) chooses blocks of eight waves by -- and fewer than DEXR_TIP_PRIO_MAX_WAVES: from
+// four generations of waves on, waves replace one another all through the launch, the block index no longer says which waves of
+// a SIMD are the late ones, and the policy measured 1-2 us slower (262 144 Allegro frames).  Other launches run at priority 0.
+// The upper limit is empirical, from that one shape (four components per frame).  The wave count is that of the grid, blocks x
+// waves per block: the launch's waves rounded up to whole blocks, in 32 bits (it wraps only past 2^32 waves, 10^11 frames of a
+// four-finger hand, and then costs speed, not answers).
+#define DEXR_TIP_PRIO_LADDER 1
+#define DEXR_TIP_PRIO_LATE 2
+#define DEXR_TIP_PRIO_PROLOGUE 4
+#define DEXR_TIP_PRIO_TAIL 8
+#ifndef DEXR_TIP_PRIO_TAIL_AFTER
+#define DEXR_TIP_PRIO_TAIL_AFTER 3
+#endif
+#ifndef DEXR_TIP_PRIO
+#define DEXR_TIP_PRIO (DEXR_TIP_PRIO_LADDER | DEXR_TIP_PRIO_LATE | DEXR_TIP_PRIO_TAIL)
+#endif
+#if DEXR_TIP_PRIO & DEXR_TIP_PRIO_TAIL
+#define DEXR_TIP_PRIO_DONE (-2 * DEXR_TIP_PRIO_TAIL_AFTER)
+#else
+#define DEXR_TIP_PRIO_DONE 1
+#endif
+#ifndef DEXR_TIP_PRIO_MIN_WAVES
+#define DEXR_TIP_PRIO_MIN_WAVES 4096
+#endif
+#ifndef DEXR_TIP_PRIO_MAX_WAVES
+#define DEXR_TIP_PRIO_MAX_WAVES 16384
+#endif
+
+// -DDEXR_WAVE_TRACE=1 (tools/wave_trace.sh; never in the shipped library): the stamps of dexr_kernel.hpp's WTRACE_*, in the
+// same 24 doubles per wave of kp.g64out -- [0] wave start, [1] frame arrived, [2] retired, [3] passes run, [4] HW_ID, [5] XCC_ID,
+// [8..23] the end of each of the first 16 passes, 100 MHz wall clock.  Lane 0 stores each stamp when it is taken (the record is
+// zeroed before the launch): kept in registers until the wave ends, as dexr_kernel keeps them, they would spill 43 VGPRs of this
+// kernel to scratch and the trace would show a different launch.  "Frame arrived" is stamped once the values named there -- the
+// last the prologue forms from the frame's loads -- exist, i.e. behind the wait for those loads.
+#ifdef DEXR_WAVE_TRACE
+#define TIP_WTRACE_PUT(i, v) { if (lane == 0 && wt_o) wt_o[i] = (double)(v); }
+#define TIP_WTRACE_START long long wt_t0 = wall_clock64();
+#define TIP_WTRACE_DECL double* wt_o = kp.g64out ? kp.g64out + (size_t)wave_global * 24 : nullptr; int wt_n = 0; TIP_WTRACE_PUT(0, wt_t0)
+#define TIP_WTRACE_ARRIVED(a, b) { asm volatile("" ::"v"(a), "v"(b)); TIP_WTRACE_PUT(1, wall_clock64()) }
+#define TIP_WTRACE_PASS() { if (wt_n < 16) TIP_WTRACE_PUT(8 + wt_n, wall_clock64()) ++wt_n; }
+#define TIP_WTRACE_FLUSH() { TIP_WTRACE_PUT(2, wall_clock64()) TIP_WTRACE_PUT(3, wt_n) \
+  TIP_WTRACE_PUT(4, __builtin_amdgcn_s_getreg(63492)) TIP_WTRACE_PUT(5, __builtin_amdgcn_s_getreg(63508)) }
+#else
+#define TIP_WTRACE_START
+#define TIP_WTRACE_DECL
+#define TIP_WTRACE_ARRIVED(a, b)
+#define TIP_WTRACE_PASS()
+#define TIP_WTRACE_FLUSH()
+#endif
+
 // One wave = 64 frames x one tip component (wave w: component w % n_comp of tile w / n_comp, as dexr_kernel in tile mode).
 // blockDim.x = 64 * waves_per_block; dynamic LDS = waves_per_block * 64 * 4 * (3 * lds_frames + 4 * lds_terms + 1) bytes, laid
 // out as dexr_kernel's: the lane's target would be at T[(0..2) * 64 + lane] (unused here), the broadcast placements of joints
@@ -77,6 +148,22 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
   extern __shared__ __align__(16) unsigned char lds_raw[];
   using RT = RealTraits<float, true>;
   constexpr auto hidx = [](int r, int c) constexpr { return r * (r + 1) / 2 + c; };
+  TIP_WTRACE_START
+#if DEXR_TIP_PRIO
+  const unsigned prio_waves = gridDim.x * (blockDim.x >> 6);
+  const bool prio_on = prio_waves >= DEXR_TIP_PRIO_MIN_WAVES && prio_waves < DEXR_TIP_PRIO_MAX_WAVES;
+  const bool prio_late = (DEXR_TIP_PRIO & DEXR_TIP_PRIO_LATE) && blockIdx.x * 2u >= gridDim.x;
+  if (prio_on) {
+    if (DEXR_TIP_PRIO & (DEXR_TIP_PRIO_LADDER | DEXR_TIP_PRIO_PROLOGUE)) __builtin_amdgcn_s_setprio(3);
+    else if (prio_late) __builtin_amdgcn_s_setprio(1);
+  }
+#endif
+#if DEXR_TIP_PRIO & DEXR_TIP_PRIO_LADDER
+  // the ladder's state, stepped down by 2 at the end of each pass until it reaches DEXR_TIP_PRIO_DONE (one scalar compare per pass
+  // from then on, and in launches outside the window from the start): 6 -> 4 -> 2 -> 0 sets priority 2, 1, 0 after passes 1, 2, 3;
+  // the late half runs 5 -> 3 -> 1, priority 2, 1, and keeps 1; with TAIL the count goes on below zero and sets 3 at DONE
+  int prio_c = prio_on ? (prio_late ? 5 : 6) : DEXR_TIP_PRIO_DONE;
+#endif
   // The prologue is a few batches of loads, one wait per level of the dependency chain
   //   kernel arguments -> the component's table (+ the lane's LDS constant) -> frame offsets, keypoint indices -> the frame
   // instead of a round trip per value: see TipTabT<float>::fetch / hold (dexr_tip.hpp).
@@ -103,6 +190,7 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
   const int64_t tile = wave_global / kp.n_comp;
   const int64_t nB = kp.B;
   if (tile * 64 >= nB) return;  // (the grid is rounded up to whole blocks)
+  TIP_WTRACE_DECL
   const int64_t item = tile * 64 + lane;  // (prologue only: the loop keeps no per-lane address, see retire)
   bool has = item < nB;  // the lane holds a frame that is not finished
   const int ld = kp.n_opt;
@@ -189,6 +277,7 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
       x[k] = RT::clamp(fl[k], tt.lo[k], tt.hi[k]);
     }
   }
+  TIP_WTRACE_ARRIVED(x[3], tg[2])
 
   // kept model: data term + regulariser at the accepted point x
   float Hs[10], gs[4], xo[4];
@@ -229,6 +318,12 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
   tt.prefetch();
   F = eval(x, gs, Hs);
   if (has && !((bool)((int)(F == F) & (int)(fabs(F) < 1e30f)))) retire(ST_FALLBACK);
+#if (DEXR_TIP_PRIO & DEXR_TIP_PRIO_PROLOGUE) && !(DEXR_TIP_PRIO & DEXR_TIP_PRIO_LADDER)
+  if (prio_on) {
+    if (prio_late) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+  }
+#endif
 
   while (__any(has)) {
     // the placements (b) needs, issued here: step (a) uses none of them and covers their way from LDS.  Not gated on (b)'s
@@ -356,7 +451,18 @@ __global__ void __launch_bounds__(DEXR_TIP_BLOCK_MAX, DEXR_CHAIN_MINW) dexr_tip3
 
     // (d) retire finished frames
     if (finished) retire(status);
+    TIP_WTRACE_PASS()
+#if DEXR_TIP_PRIO & DEXR_TIP_PRIO_LADDER
+    if (prio_c > DEXR_TIP_PRIO_DONE) {
+      prio_c -= 2;
+      if (prio_c >= 3) __builtin_amdgcn_s_setprio(2);
+      else if (prio_c >= 1) __builtin_amdgcn_s_setprio(1);
+      else if (prio_c == 0) __builtin_amdgcn_s_setprio(0);
+      else if (prio_c <= DEXR_TIP_PRIO_DONE) __builtin_amdgcn_s_setprio(3);  // (TAIL only: without it DONE is the ladder's end)
+    }
+#endif
   }
+  TIP_WTRACE_FLUSH()
 }
 
 }  // namespace dexr

@@ -1,6 +1,7 @@
 #!/bin/bash
 # What a small-component launch's duration is made of: every wave's start / first-load / per-pass / retire times on the
-# 100 MHz wall clock (-DDEXR_WAVE_TRACE=1, see dexr_kernel.hpp).
+# 100 MHz wall clock (-DDEXR_WAVE_TRACE=1, see dexr_kernel.hpp; dexr_tip32_kernel, the plain tile launch of a float32 tip
+# model, carries the same stamps).  WTRACE_EXTRA adds compiler flags to the tracing copy, e.g. -DDEXR_TIP_PRIO=1.
 #   bash tools/wave_trace.sh build              HERE: tracing copy of the library -> tools/_prof/libdexr_wtrace.so
 #   bash tools/wave_trace.sh run [config] [B]   ON THE GPU BOX: one tracking launch, summary on stdout
 set -u
@@ -10,7 +11,7 @@ if [ "${1:-run}" = build ]; then
   export DEXR_BUILD_DIR=$R/build_wtrace DEXR_LIB_OUT=$R/tools/_prof/libdexr_wtrace.so DEXR_EXTRA_FLAGS="-DDEXR_WAVE_TRACE=1 ${WTRACE_EXTRA:-}"
   mkdir -p $DEXR_BUILD_DIR $R/tools/_prof
   # reuse the objects of the normal build for everything but the small-component solve kernels and the API
-  for f in "$R"/build/*.o; do b=$(basename $f); case $b in dexr_inst_4_0_0.o|dexr_inst_8_0_0.o|dexr_inst_4_1_0.o|dexr_inst_8_1_0.o|dexr_inst_chain*|dexr_inst_ext*|dexr_inst_tip*|dexr_api.o) ;; *) cp -pu $f $DEXR_BUILD_DIR/ ;; esac; done
+  for f in "$R"/build/*.o; do b=$(basename $f); case $b in dexr_inst_4_0_0.o|dexr_inst_8_0_0.o|dexr_inst_4_1_0.o|dexr_inst_8_1_0.o|dexr_inst_chain*|dexr_inst_ext*|dexr_inst_tip*|dexr_tip32.o|dexr_api.o) ;; *) cp -pu $f $DEXR_BUILD_DIR/ ;; esac; done
   python -m dex_retargeting_amd._build
   exit $?
 fi
@@ -67,6 +68,20 @@ xcc = d[:, 5].astype(np.int64) & 0xF
 for x in sorted(set(xcc)):
     m = xcc == x
     print(f"  XCC {x}: {int(m.sum()):5d} waves, start p50 {np.median(start[m]):6.2f} us, retire max {end[m].max():6.2f} us")
+# the four age ranks of a SIMD: waves of one SIMD (XCC, SE / SH / CU, SIMD of HW_ID) in the order they started
+simd = (xcc << 10) | (((hw >> 8) & 0xFF) << 2) | ((hw >> 4) & 3)
+order = np.lexsort((start, simd))
+first = np.r_[True, simd[order][1:] != simd[order][:-1]]
+idx = np.arange(len(order))
+rank = np.empty(len(d), int)
+rank[order] = idx - np.maximum.accumulate(np.where(first, idx, 0))
+print(f"age ranks within a SIMD ({int(first.sum())} SIMDs): rank, waves, p50 / max of start, frame arrived, retired [us], p50 passes")
+for r in range(int(rank.max()) + 1):
+    m = rank == r
+    print(f"  rank {r}  {int(m.sum()):5d}   start {np.median(start[m]):6.2f} {start[m].max():6.2f}   arrived {np.median(loaded[m]):6.2f} {loaded[m].max():6.2f}"
+          f"   retired {np.median(end[m]):6.2f} {end[m].max():6.2f}   passes {np.median(n[m]):.0f}")
+easy = n <= np.median(n)
+print(f"last easy wave (at most the median {int(np.median(n))} passes) retires at {end[easy].max():.2f} us, p99 {np.percentile(end[easy], 99):.2f}; last wave at {end.max():.2f} us")
 slow = np.argsort(-end)[:8]
 print("the 8 waves that retire last: wave, start, loaded, end, passes, pass durations")
 for w in slow:
