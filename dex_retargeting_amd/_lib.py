@@ -110,6 +110,12 @@ CROSS_FRAMES, CROSS_LDS = 16, 65536  # DEXR_CROSS_*
 # include/dexr_resolve_cross.h (the posture solve against a second posed robot, in one kernel): a list of its own.  (Its name does
 # not end in EXPORTS: tests/test_cross_host.py counts the lists that do.)
 RESOLVE_CROSS_SYMBOLS = ["dexr_sphere_resolve_cross_dev", "dexr_sphere_resolve_cross"]
+# include/dexr_distance_transform.h (distance grids from point clouds and occupancy maps, the exact Euclidean distance transform): a
+# list of its own.  (Its name does not end in EXPORTS: tests/test_cross_host.py counts the lists that do.)
+EDT_SYMBOLS = ["dexr_edt_workspace_bytes", "dexr_edt_points_dev", "dexr_edt_occupancy_dev", "dexr_edt_points", "dexr_edt_occupancy"]
+EDT_NONE, EDT_MAX_POINTS, EDT_TILE_BYTES = 1 << 30, 1 << 26, 65536  # DEXR_EDT_*
+# include/dexr_sdf_grid_dev.h (a grid handle whose samples are written on the device): a list of its own, as above
+SDF_GRID_DEV_SYMBOLS = ["dexr_sdf_grid_create_dev", "dexr_sdf_grid_values_dev", "dexr_sdf_grid_download"]
 UNIQUE_ID_BYTES = 128
 
 
@@ -280,6 +286,16 @@ def load() -> C.CDLL:
     lib.dexr_sphere_fit_dev.argtypes = [C.c_int32, i32p, f64p, i64p, i32p, C.c_double, C.c_double, C.c_double, i64, vp, vp, vp, vp, vp,
                                         C.c_size_t, vp]
     lib.dexr_sphere_fit.argtypes = [C.c_int32, i32p, f64p, i64p, i32p, C.c_double, C.c_double, C.c_double, i64, f32p, i32p, i32p, i32p]
+    u8p, f64 = C.POINTER(C.c_uint8), C.c_double
+    lib.dexr_edt_workspace_bytes.argtypes = [i32p, C.POINTER(C.c_size_t)]
+    lib.dexr_edt_points_dev.argtypes = [vp, i64, i32p, f64p, f64, C.c_int32, f64, f64, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.dexr_edt_occupancy_dev.argtypes = [vp, i32p, f64, C.c_int32, f64, f64, vp, vp, vp, C.c_size_t, vp]
+    lib.dexr_edt_points.argtypes = [f32p, i64, i32p, f64p, f64, C.c_int32, f64, f64, f32p, i32p, i32p]
+    lib.dexr_edt_occupancy.argtypes = [u8p, i32p, f64, C.c_int32, f64, f64, f32p, i32p]
+    lib.dexr_sdf_grid_create_dev.argtypes = [i32p, f64p, f64p, vp, vp, C.POINTER(vp)]
+    lib.dexr_sdf_grid_values_dev.argtypes = [vp]
+    lib.dexr_sdf_grid_values_dev.restype = vp
+    lib.dexr_sdf_grid_download.argtypes = [vp, f32p, vp]
     _lib = lib
     return lib
 
@@ -1368,6 +1384,104 @@ class SdfGrid:
     @property
     def handle(self) -> C.c_void_p:
         return self._h
+
+
+class DeviceSdfGrid(SdfGrid):
+    """Owns one dexr_sdf_grid made by dexr_sdf_grid_create_dev (include/dexr_sdf_grid_dev.h): the samples are allocated on the current
+    device and set, on `stream`, to zero or to a device-to-device copy of the n[0] n[1] n[2] float32 at values_ptr.  A producer
+    writes them through `values_ptr`; keeping them finite is the producer's contract.  Everything that takes an SdfGrid takes it."""
+
+    def __init__(self, n, origin, spacing, values_ptr: int = 0, stream: int = 0):
+        lib = load()
+        self._h = C.c_void_p()
+        n, origin, spacing = TriangleMesh._grid_args(n, origin, spacing)
+        check(lib.dexr_sdf_grid_create_dev(_ptr(n, C.c_int32), _ptr(origin, C.c_double), _ptr(spacing, C.c_double), values_ptr or None,
+                                           stream or None, C.byref(self._h)))
+        self.shape = tuple(int(v) for v in n)
+
+    @property
+    def values_ptr(self) -> int:
+        """the device address of the samples (dexr_sdf_grid_values_dev)"""
+        return int(load().dexr_sdf_grid_values_dev(self._h) or 0)
+
+    def download(self, stream: int = 0) -> np.ndarray:
+        """-> the samples (nx, ny, nz) float32 on the host, as they are after everything enqueued on `stream` before this call; it
+        synchronises that stream (dexr_sdf_grid_download)."""
+        values = np.zeros(self.shape, dtype=np.float32)
+        check(load().dexr_sdf_grid_download(self._h, _ptr(values, C.c_float), stream or None))
+        return values
+
+
+def _edt_grid_args(n, origin=None):
+    n = np.ascontiguousarray(n, dtype=np.int32).reshape(-1)
+    if n.shape != (3,):
+        raise ValueError(f"n must have shape (3,), got {n.shape}")
+    if origin is None:
+        return n
+    origin = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
+    if origin.shape != (3,):
+        raise ValueError(f"origin must have shape (3,), got {origin.shape}")
+    return n, origin
+
+
+def edt_workspace_bytes(n) -> int:
+    """bytes of device workspace a distance transform on a grid of n (3,) samples needs (dexr_edt_workspace_bytes)"""
+    n = _edt_grid_args(n)
+    out = C.c_size_t(0)
+    check(load().dexr_edt_workspace_bytes(_ptr(n, C.c_int32), C.byref(out)))
+    return int(out.value)
+
+
+def edt_points_dev(points_ptr: int, N: int, n, origin, h: float, min_points: int, radius: float, max_distance: float, values_ptr: int,
+                   d2_ptr: int = 0, count_ptr: int = 0, workspace_ptr: int = 0, workspace_bytes: int = 0, stream: int = 0):
+    """device pointers (include/dexr_distance_transform.h): points (N, 3) float32 -> values (n) float32, d2 and count (n) int32 or 0.
+    n and origin are host arrays.  Never synchronises, never allocates."""
+    n, origin = _edt_grid_args(n, origin)
+    check(load().dexr_edt_points_dev(points_ptr or None, int(N), _ptr(n, C.c_int32), _ptr(origin, C.c_double), float(h), int(min_points),
+                                     float(radius), float(max_distance), values_ptr or None, d2_ptr or None, count_ptr or None,
+                                     workspace_ptr or None, int(workspace_bytes), stream or None))
+
+
+def edt_occupancy_dev(occ_ptr: int, n, h: float, signed: bool, radius: float, max_distance: float, values_ptr: int, d2_ptr: int = 0,
+                      workspace_ptr: int = 0, workspace_bytes: int = 0, stream: int = 0):
+    """device pointers: occ (n) uint8 -> values (n) float32, d2 (n) int32 or 0 (dexr_edt_occupancy_dev).  Never synchronises, never
+    allocates."""
+    n = _edt_grid_args(n)
+    check(load().dexr_edt_occupancy_dev(occ_ptr or None, _ptr(n, C.c_int32), float(h), int(bool(signed)), float(radius), float(max_distance),
+                                        values_ptr or None, d2_ptr or None, workspace_ptr or None, int(workspace_bytes), stream or None))
+
+
+def _edt_host_outputs(n):
+    ok = n.min() >= SDF_GRID_MIN_DIM and n.max() <= SDF_GRID_MAX_DIM and int(n[0]) * int(n[1]) * int(n[2]) <= SDF_GRID_MAX_SAMPLES
+    shape = tuple(int(k) for k in n) if ok else (1,)  # (a refused shape: the library says why)
+    return np.zeros(shape, dtype=np.float32), np.zeros(shape, dtype=np.int32)
+
+
+def edt_points(points, n, origin, h: float, min_points: int = 1, radius: float = 0.0, max_distance: float = 1.0):
+    """points (N, 3) float32 on the host -> values float32, d2 int32, count int32, each (n) (dexr_edt_points)."""
+    points = np.ascontiguousarray(points, dtype=np.float32)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must have shape (N, 3), got {points.shape}")
+    n, origin = _edt_grid_args(n, origin)
+    values, d2 = _edt_host_outputs(n)
+    count = np.zeros_like(d2)
+    check(load().dexr_edt_points(_ptr(points, C.c_float) if len(points) else None, len(points), _ptr(n, C.c_int32), _ptr(origin, C.c_double),
+                                 float(h), int(min_points), float(radius), float(max_distance), _ptr(values, C.c_float), _ptr(d2, C.c_int32),
+                                 _ptr(count, C.c_int32)))
+    return values, d2, count
+
+
+def edt_occupancy(occ, h: float, signed: bool = True, radius: float = 0.0, max_distance: float = 1.0):
+    """occ (nx, ny, nz) uint8 on the host -> values float32, d2 int32 (to the occupied voxels), each of occ's shape
+    (dexr_edt_occupancy)."""
+    occ = np.ascontiguousarray(occ, dtype=np.uint8)
+    if occ.ndim != 3:
+        raise ValueError(f"occ must have shape (nx, ny, nz), got {occ.shape}")
+    n = np.array(occ.shape, dtype=np.int32)
+    values, d2 = _edt_host_outputs(n)
+    check(load().dexr_edt_occupancy(_ptr(occ, C.c_uint8), _ptr(n, C.c_int32), float(h), int(bool(signed)), float(radius), float(max_distance),
+                                    _ptr(values, C.c_float), _ptr(d2, C.c_int32)))
+    return values, d2
 
 
 def mesh_points_per_launch(n_triangle: int) -> int:

@@ -29,6 +29,12 @@ trilinear lookup per sphere however complex the shape is, the distance continued
 box.  ``SdfGrid.from_obstacles`` samples an ``ObstacleSet``.  ``resolve_grid_collisions`` is ``resolve_collisions`` against a grid
 (include/dexr_resolve_grid.h): a sphere has one contact at most, so nothing is capped.
 
+A grid need not come from a shape known in advance (include/dexr_distance_transform.h, csrc/dexr_distance_transform.hpp):
+``SdfGrid.from_points`` and ``SdfGrid.from_occupancy`` make one from a depth camera's point cloud or a voxel occupancy map by the
+exact Euclidean distance transform on the device, whose cost does not grow with the number of points.  A ``DeviceSdfGrid`` is a
+grid whose samples live on the device and are rewritten in place (``update_from_points``, ``update_from_occupancy``) on the
+current stream: a scene that changes per frame feeds ``grid_penalty`` and ``resolve_grid_collisions`` without a host copy.
+
 The other robot is the one obstacle that has its own q per frame (include/dexr_cross.h, csrc/dexr_cross.hpp): the other hand of a
 two-handed recording, a second gripper, the arm beside the hand.  ``cross_distances`` and ``cross_penalty`` take two optimisers,
 two q, two ``SphereSet`` and a base pose per robot and frame (``pos_a``, ``rot_a``, ``pos_b``, ``rot_b``), and give the distance of
@@ -975,6 +981,18 @@ class SdfGrid:
                 values = buf.cpu().numpy()
         return cls(values, o, h)
 
+    @classmethod
+    def from_points(cls, points, origin, spacing, shape, min_points=1, radius=None, max_distance=None, signed=False):
+        """the unsigned distance to a point cloud (include/dexr_distance_transform.h): `DeviceSdfGrid.from_points` computed on the
+        device of `points` and returned as a host-owned, immutable grid, as `from_mesh(precision="float32")` does."""
+        return DeviceSdfGrid.from_points(points, origin, spacing, shape, min_points, radius, max_distance, signed).to_host()
+
+    @classmethod
+    def from_occupancy(cls, occ, origin, spacing, signed=True, radius=None, max_distance=None):
+        """the distance to the occupied voxels of a uint8 occupancy map, signed by default: `DeviceSdfGrid.from_occupancy`
+        computed on the device of `occ` and returned as a host-owned, immutable grid."""
+        return DeviceSdfGrid.from_occupancy(occ, origin, spacing, signed, radius, max_distance).to_host()
+
     @property
     def shape(self):
         return self.values.shape
@@ -993,6 +1011,206 @@ class SdfGrid:
 
     def __repr__(self):
         return f"SdfGrid({'x'.join(str(k) for k in self.shape)} samples, origin {self.origin.tolist()}, spacing {self.spacing.tolist()})"
+
+
+def _edt_grid_rules(shape, origin, spacing):
+    """the grid rules of include/dexr_distance_transform.h -> (n (3 ints), origin (3,) float64, h float): ONE spacing"""
+    try:
+        ns = np.broadcast_to(np.asarray(shape), (3,))
+        o = np.array(np.broadcast_to(np.asarray(origin, dtype=np.float64), (3,)))
+        hs = np.array(np.broadcast_to(np.asarray(spacing, dtype=np.float64), (3,)))
+    except (ValueError, TypeError):
+        raise ValueError("shape, origin and spacing must each be a scalar or have shape (3,)") from None
+    if ns.dtype.kind not in "iu":
+        raise ValueError(f"shape must be integers, got {np.asarray(shape).tolist()}")
+    n = tuple(int(k) for k in ns)
+    if min(n) < _lib.SDF_GRID_MIN_DIM or max(n) > _lib.SDF_GRID_MAX_DIM or n[0] * n[1] * n[2] > _lib.SDF_GRID_MAX_SAMPLES:
+        raise ValueError(f"every dimension of a grid is {_lib.SDF_GRID_MIN_DIM}..{_lib.SDF_GRID_MAX_DIM} samples and there are at most "
+                         f"{_lib.SDF_GRID_MAX_SAMPLES}, got {n}")
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        inv_ok = np.isfinite(1.0 / hs).all()
+    if not (np.isfinite(hs).all() and (hs > 0).all() and inv_ok):
+        raise ValueError(f"spacing must be finite and > 0, got {hs.tolist()}")
+    if not (hs[0] == hs[1] == hs[2]):
+        raise ValueError(f"a distance transform needs ONE spacing for the three axes, got {hs.tolist()}")
+    if not np.isfinite(o).all():
+        raise ValueError(f"origin must be finite, got {o.tolist()}")
+    return n, o, float(hs[0])
+
+
+def _edt_scalars(n, h, min_points, radius, max_distance, signed, cloud):
+    """the scalar rules -> (min_points, radius, max_distance) with the defaults filled in"""
+    if cloud and signed:
+        raise ValueError("signed=True needs an occupancy map: a point cloud has no inside")
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or min_points < 1:
+        raise ValueError(f"min_points must be an integer >= 1, got {min_points!r}")
+    if signed:
+        if radius is not None:
+            raise ValueError("the signed form has no radius: its surface sits h / 2 from the voxel centres")
+        radius = 0.0
+    elif radius is None:
+        radius = h * math.sqrt(3.0) / 2.0
+    if max_distance is None:
+        max_distance = h * math.sqrt(sum((k - 1) ** 2 for k in n))  # the diagonal of the grid's box
+    try:
+        radius, max_distance = float(radius), float(max_distance)
+    except (TypeError, ValueError):
+        raise ValueError("radius and max_distance must be numbers") from None
+    if not (math.isfinite(radius) and radius >= 0):
+        raise ValueError(f"radius must be finite and >= 0, got {radius}")
+    if not (math.isfinite(max_distance) and max_distance > 0):
+        raise ValueError(f"max_distance must be finite and > 0, got {max_distance}")
+    return int(min_points), radius, max_distance
+
+
+def _edt_tensor_rules(t, name, dtype, shape_text, shape_ok):
+    """type, dtype, shape, layout, and last the device"""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if not shape_ok(tuple(t.shape)):
+        raise ValueError(f"{name} must have shape {shape_text}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be a CUDA tensor, got one on {t.device}")
+
+
+def _edt_points_rules(points):
+    import torch
+
+    _edt_tensor_rules(points, "points", torch.float32, "(N, 3)", lambda s: len(s) == 2 and s[1] == 3 and s[0] <= _lib.EDT_MAX_POINTS)
+
+
+class DeviceSdfGrid(SdfGrid):
+    """An `SdfGrid` whose samples live on ONE CUDA device and may be rewritten in place: the grid of a scene that changes per frame
+    (include/dexr_sdf_grid_dev.h, include/dexr_distance_transform.h).  `grid_distances`, `grid_penalty`, `autograd.grid_penalty`,
+    `resolve_grid_collisions` and a `SceneBody` of `resolve_scene_collisions` take it like any SdfGrid, through `device_grid`, with
+    their kernels unchanged; `fit_spheres` refuses it, because it reads the samples on the host.
+
+    It has `shape`, `origin` (3,) and `spacing` (3,; one value three times), is hashed and compared by IDENTITY (its content
+    changes), and is bound to the device it was made on: `device_grid(i)` for another device is a ValueError.  `.values` raises;
+    `to_host()` returns an ordinary immutable SdfGrid of the samples as they are after the work enqueued so far on the current
+    stream, and is the only method that synchronises.
+
+    `empty` makes a grid of zeros on the current CUDA device, `from_points` and `from_occupancy` one on the device of their
+    tensor; all of them and the in-place `update_from_points` / `update_from_occupancy` run on the current stream of that device,
+    allocate the workspace of the transform once, and make no host copy.  Updates and consumers are ordered by the stream they
+    are enqueued on: on one stream an update followed by `grid_penalty` needs no synchronise; across streams the ordering is the
+    caller's.  A consumer reads the samples when its kernel RUNS: in particular the backward of `autograd.grid_penalty` reads
+    whatever the grid holds when backward runs, not what it held at the forward.
+
+    The fields are those of include/dexr_distance_transform.h.  A cloud (points (N, 3) float32 CUDA, contiguous) gives the unsigned
+    distance to the voxels that hold at least `min_points` points, minus `radius` (default h sqrt(3) / 2: never larger than the
+    true distance to the nearest kept point; 0: the raw distance between voxel centres), clamped at `max_distance` (default the
+    diagonal of the grid's box).  An occupancy map (nx, ny, nz) uint8 CUDA gives, with signed=True, a field that is negative
+    inside the occupied voxels with its surface halfway between a free and an occupied voxel, and with signed=False the
+    unsigned form.  Every sample is finite whatever the input."""
+
+    def __init__(self, shape, origin, spacing, device=None):
+        n, o, h = _edt_grid_rules(shape, origin, spacing)
+        import torch
+
+        self._shape, self._h = n, h
+        self.origin, self.spacing = o, np.full(3, h)
+        for a in (self.origin, self.spacing):
+            a.setflags(write=False)
+        self._device = torch.cuda.current_device() if device is None else torch.device(device).index
+        self._workspace = None
+        with torch.cuda.device(self._device):
+            self._grid = _lib.DeviceSdfGrid(n, o, self.spacing, 0, torch.cuda.current_stream().cuda_stream)
+
+    @classmethod
+    def empty(cls, shape, origin, spacing):
+        """a grid of zeros on the current CUDA device"""
+        return cls(shape, origin, spacing)
+
+    @classmethod
+    def from_points(cls, points, origin, spacing, shape, min_points=1, radius=None, max_distance=None, signed=False):
+        n, _, h = _edt_grid_rules(shape, origin, spacing)
+        _edt_scalars(n, h, min_points, radius, max_distance, signed, cloud=True)
+        _edt_points_rules(points)
+        g = cls(shape, origin, spacing, device=points.device)
+        g.update_from_points(points, min_points, radius, max_distance)
+        return g
+
+    @classmethod
+    def from_occupancy(cls, occ, origin, spacing, signed=True, radius=None, max_distance=None):
+        import torch
+
+        shape = tuple(occ.shape) if isinstance(occ, torch.Tensor) and occ.ndim == 3 else (2, 2, 2)  # (not a map: refused below)
+        n, _, h = _edt_grid_rules(shape, origin, spacing)
+        _edt_scalars(n, h, 1, radius, max_distance, signed, cloud=False)
+        _edt_tensor_rules(occ, "occ", torch.uint8, "(nx, ny, nz)", lambda s: len(s) == 3)
+        g = cls(shape, origin, spacing, device=occ.device)
+        g.update_from_occupancy(occ, signed, radius, max_distance)
+        return g
+
+    def _launch(self, t, what, run):
+        import torch
+
+        if t.device.index != self._device:
+            raise ValueError(f"{what} is on cuda:{t.device.index}, this DeviceSdfGrid lives on cuda:{self._device}")
+        with torch.cuda.device(self._device):
+            if self._workspace is None:
+                self._workspace = torch.empty(_lib.edt_workspace_bytes(self._shape), dtype=torch.uint8, device="cuda")
+            ws = self._workspace
+            run(self._grid.values_ptr, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+
+    def update_from_points(self, points, min_points=1, radius=None, max_distance=None, signed=False):
+        """re-run the transform of a cloud into the same samples, on the current stream"""
+        min_points, radius, max_distance = _edt_scalars(self._shape, self._h, min_points, radius, max_distance, signed, cloud=True)
+        _edt_points_rules(points)
+        self._launch(points, "points", lambda v, ws, nb, st: _lib.edt_points_dev(
+            points.data_ptr() if points.shape[0] else 0, points.shape[0], self._shape, self.origin, self._h, min_points, radius, max_distance, v,
+            workspace_ptr=ws, workspace_bytes=nb, stream=st))
+
+    def update_from_occupancy(self, occ, signed=True, radius=None, max_distance=None):
+        """re-run the transform of an occupancy map of the grid's shape into the same samples, on the current stream"""
+        import torch
+
+        _, radius, max_distance = _edt_scalars(self._shape, self._h, 1, radius, max_distance, signed, cloud=False)
+        _edt_tensor_rules(occ, "occ", torch.uint8, str(self._shape), lambda s: s == self._shape)
+        self._launch(occ, "occ", lambda v, ws, nb, st: _lib.edt_occupancy_dev(
+            occ.data_ptr(), self._shape, self._h, signed, radius, max_distance, v, workspace_ptr=ws, workspace_bytes=nb, stream=st))
+
+    def to_host(self) -> SdfGrid:
+        """-> an immutable SdfGrid of the samples as they are after everything enqueued so far on the current stream; synchronises it"""
+        import torch
+
+        with torch.cuda.device(self._device):
+            values = self._grid.download(torch.cuda.current_stream().cuda_stream)
+        return SdfGrid(values, self.origin, self.spacing)
+
+    @property
+    def shape(self):
+        return self._shape
+
+    @property
+    def device_index(self) -> int:
+        return self._device
+
+    @property
+    def values(self):
+        raise AttributeError("a DeviceSdfGrid keeps its samples on the device and they may change: to_host() returns an SdfGrid with .values")
+
+    def device_grid(self, device_index: int = 0) -> _lib.SdfGrid:
+        if device_index != self._device:
+            raise ValueError(f"this DeviceSdfGrid lives on cuda:{self._device} and cannot serve cuda:{device_index}: make one there, or "
+                             "use to_host() for a grid that any device can take")
+        return self._grid
+
+    __hash__ = object.__hash__
+
+    def __eq__(self, other):
+        return self is other
+
+    def __repr__(self):
+        return (f"DeviceSdfGrid({'x'.join(str(k) for k in self.shape)} samples on cuda:{self._device}, origin {self.origin.tolist()}, "
+                f"spacing {self._h})")
 
 
 class SphereFit:
@@ -1040,6 +1258,8 @@ def _fit_rules(grids, max_spheres, min_radius, inflate, coverage):
         raise ValueError("grids must be a collision.SdfGrid or a sequence of them") from None
     if not grids or not all(isinstance(g, SdfGrid) for g in grids):
         raise ValueError("grids must be a collision.SdfGrid or a non-empty sequence of them")
+    if any(isinstance(g, DeviceSdfGrid) for g in grids):
+        raise ValueError("fit_spheres reads the samples on the host: pass DeviceSdfGrid.to_host()")
     if len(grids) > _lib.SPHERE_FIT_MAX_BODIES:
         raise ValueError(f"one call fits at most {_lib.SPHERE_FIT_MAX_BODIES} grids, got {len(grids)}")
     try:
@@ -1797,4 +2017,5 @@ __all__ = ["SphereSet", "default_pairs", "sphere_distances", "self_collision_pen
            "grid_distances", "grid_penalty", "robot_grid_distances", "robot_grid_penalty", "resolve_grid_collisions",
            "robot_resolve_grid_collisions", "TriangleMesh", "mesh_distances", "SceneBody", "resolve_scene_collisions",
            "robot_resolve_scene_collisions", "cross_distances", "cross_penalty", "robot_cross_distances", "robot_cross_penalty",
-           "resolve_cross_collisions", "robot_resolve_cross_collisions", "relative_pose", "resolve_bimanual_collisions", "SphereFit", "fit_spheres", "link_grid"]
+           "resolve_cross_collisions", "robot_resolve_cross_collisions", "relative_pose", "resolve_bimanual_collisions", "SphereFit", "fit_spheres", "link_grid",
+           "DeviceSdfGrid"]

@@ -2064,5 +2064,8 @@ int dexr_link_ik_solve(const dexr_pose_model* m, int64_t B, const double* x0, co
 // ---- include/dexr_sphere_fit.h: a few inscribed spheres per body from its sampled signed-distance field, a greedy cover in bit masks --
 #include "dexr_sphere_fit.hpp"
 
+// ---- include/dexr_distance_transform.h, include/dexr_sdf_grid_dev.h: distance grids from clouds and occupancy, grids that live on the device
+#include "dexr_distance_transform.hpp"
+
 // ---- include/dexr_mesh_sdf.h: signed distances of points and grid samples to a triangle mesh, the sampler in front of the grids ----
 #include "dexr_mesh_sdf.hpp"
