@@ -931,7 +931,7 @@ extern "C" {
 
 const char* dexr_last_error(void) { return g_err.c_str(); }
 
-const char* dexr_version(void) { return "dexr 0.4 (gfx950; table v5 + generic tables)"; }
+const char* dexr_version(void) { return "dexr 0.4 (gfx950; table v6 + generic tables)"; }
 
 int dexr_device_count(void) {
   int n = 0;

@@ -307,7 +307,8 @@ struct LaneSolver {
 
   // ---- forward kinematics of the component's joint list ---------------------------------------------------
   // Writes ax/og for every joint and the world position of every frame to LDS  P[(f*3+c)*64 + lane].
-  template <typename TB>
+  // FINE (the float64 objective evaluation): kinematic constants = float32 field + its rounding residue (table v6, *_lo)
+  template <bool FINE = false, typename TB>
   __device__ __forceinline__ void fk(const TB& tb, int nj, real* P, int lane) {
     constexpr bool LOCAL = TabTraits<TB>::LOCAL;  // LOCAL tables exist only for CHAIN kernels
     real R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
@@ -341,20 +342,25 @@ struct LaneSolver {
             }
         }
         const float* X = tb.X[k];
+        auto XV = [&](int i) -> real {
+          if constexpr (FINE) return (real)X[i] + (real)tb.X_lo[k][i];
+          else return (real)X[i];
+        };
         // p += R * Xp ; R = R * Xr
 #pragma unroll
-        for (int i = 0; i < 3; ++i) p[i] += R[3 * i] * (real)X[9] + R[3 * i + 1] * (real)X[10] + R[3 * i + 2] * (real)X[11];
+        for (int i = 0; i < 3; ++i) p[i] += R[3 * i] * XV(9) + R[3 * i + 1] * XV(10) + R[3 * i + 2] * XV(11);
         real Rn[9];
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
           for (int j = 0; j < 3; ++j)
-            Rn[3 * i + j] = R[3 * i] * (real)X[j] + R[3 * i + 1] * (real)X[3 + j] + R[3 * i + 2] * (real)X[6 + j];
+            Rn[3 * i + j] = R[3 * i] * XV(j) + R[3 * i + 1] * XV(3 + j) + R[3 * i + 2] * XV(6 + j);
         real q = x[k];
         bool revolute = true;
         if constexpr (!CHAIN) {
           if (tb.src_kind[k] == DEXR_SRC_MIMIC) {  // kinematics_adaptor.py:102-105
-            q = (real)tb.mult[k] * pick(x, tb.src_idx[k]) + (real)tb.off[k];
+            if constexpr (FINE) q = ((real)tb.mult[k] + (real)tb.mult_lo[k]) * pick(x, tb.src_idx[k]) + ((real)tb.off[k] + (real)tb.off_lo[k]);
+            else q = (real)tb.mult[k] * pick(x, tb.src_idx[k]) + (real)tb.off[k];
             x[k] = q;
           }
           revolute = (revmask >> k) & 1u;
@@ -406,7 +412,12 @@ struct LaneSolver {
         } else {
 #pragma clang loop unroll(disable) vectorize(disable)
           for (int f = fb; f < fe; ++f) {
-            const real o0 = (real)tb.frame_off[f][0], o1 = (real)tb.frame_off[f][1], o2 = (real)tb.frame_off[f][2];
+            real o0 = (real)tb.frame_off[f][0], o1 = (real)tb.frame_off[f][1], o2 = (real)tb.frame_off[f][2];
+            if constexpr (FINE) {
+              o0 += (real)tb.frame_off_lo[f][0];
+              o1 += (real)tb.frame_off_lo[f][1];
+              o2 += (real)tb.frame_off_lo[f][2];
+            }
 #pragma unroll
             for (int i = 0; i < 3; ++i)
               P[(f * 3 + i) * 64 + lane] = p[i] + R[3 * i] * o0 + R[3 * i + 1] * o1 + R[3 * i + 2] * o2;
@@ -790,7 +801,10 @@ __global__ void __launch_bounds__((TIP && sizeof(real) == 4) ? DEXR_TIP_BLOCK_MA
           S.xl[k] = l;
           S.x[k] = v;
         } else if (sk == DEXR_SRC_FIXED) {
-          S.x[k] = (real)tb.mult[k] * (real)kp.fixed[it * kp.ldf + tb.src_idx[k]] + (real)tb.off[k];
+          if constexpr (MODE == MODE_EVAL)
+            S.x[k] = ((real)tb.mult[k] + (real)tb.mult_lo[k]) * (real)kp.fixed[it * kp.ldf + tb.src_idx[k]] + ((real)tb.off[k] + (real)tb.off_lo[k]);
+          else
+            S.x[k] = (real)tb.mult[k] * (real)kp.fixed[it * kp.ldf + tb.src_idx[k]] + (real)tb.off[k];
         } else if (sk == DEXR_SRC_DIRECT) {
           S.x[k] = (real)kp.xin[it * kp.n_q + tb.src_idx[k]];
         }
@@ -867,7 +881,8 @@ __global__ void __launch_bounds__((TIP && sizeof(real) == 4) ? DEXR_TIP_BLOCK_MA
 #pragma clang loop unroll(disable) vectorize(disable)
   for (int f = 0; f < tb.n_base_frame; ++f) {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) P[(f * 3 + i) * 64 + lane] = (real)tb.frame_off[f][i];
+    for (int i = 0; i < 3; ++i)
+      P[(f * 3 + i) * 64 + lane] = MODE == MODE_EVAL ? (real)tb.frame_off[f][i] + (real)tb.frame_off_lo[f][i] : (real)tb.frame_off[f][i];
   }
 
   uint32_t nst_out = 0;  // written back at the very end: no global store may precede the (invariant) table loads
@@ -888,7 +903,7 @@ __global__ void __launch_bounds__((TIP && sizeof(real) == 4) ? DEXR_TIP_BLOCK_MA
   const real delta = (real)kp.norm_delta;
 
   if (MODE == MODE_EVAL) {  // objective(x, grad): value without, gradient with the regulariser (quirk Q1)
-    S.fk(tb, nj, P, lane);
+    S.template fk<true>(tb, nj, P, lane);
     const real f = S.template residuals<1>(tb, kp, nt, vmask, P, T, W, lane);
     S.template fold_mimic<false>(tb, nj);
     if (valid) {

@@ -32,7 +32,7 @@ class TableOverflow(ValueError):
 
 
 MAXJ, MAXF, MAXT, NSLOT = 32, 16, 16, 3
-MAGIC, VERSION = 0x52584544, 5
+MAGIC, VERSION = 0x52584544, 6
 KIND_VECTOR, KIND_POSITION, KIND_DEXPILOT, KIND_FKONLY = 0, 1, 2, 3
 SRC_OPT, SRC_FIXED, SRC_MIMIC, SRC_DIRECT = 0, 1, 2, 3
 
@@ -46,7 +46,10 @@ COMP_DTYPE = np.dtype([
     ("frame_joint", "<i4", (MAXF,)), ("frame_off", "<f4", (MAXF, 3)), ("frame_anc", "<u4", (MAXF,)),
     ("term_task", "<i4", (MAXT,)), ("term_origin", "<i4", (MAXT,)), ("term_ref", "<i4", (MAXT,)),
     ("n_var", "<i4"), ("var", "<i4", (MAXJ,)), ("vmul", "<f4", (MAXJ,)), ("var_joint", "<i4", (MAXJ,)),
+    # v6: the float32 rounding residue of X / mult / off / frame_off (dexr_eval reads field + field_lo in float64)
+    ("X_lo", "<f4", (MAXJ, 12)), ("mult_lo", "<f4", (MAXJ,)), ("off_lo", "<f4", (MAXJ,)), ("frame_off_lo", "<f4", (MAXF, 3)),
 ])
+
 HEADER_DTYPE = np.dtype([
     ("magic", "<u4"), ("version", "<u4"), ("kind", "<i4"), ("n_opt", "<i4"), ("n_fixed", "<i4"),
     ("n_ref", "<i4"), ("n_comp", "<i4"), ("num_fingers", "<i4"), ("n_q", "<i4"), ("comp_bytes", "<i4"),
@@ -54,6 +57,11 @@ HEADER_DTYPE = np.dtype([
     ("project_dist", "<f4"), ("escape_dist", "<f4"), ("eta1", "<f4"), ("eta2", "<f4"),
     ("n_keypoints", "<i4"), ("human_origin", "<i4", (MAXT,)), ("human_task", "<i4", (MAXT,)),
 ])
+
+
+def _residue(value, stored):
+    """float64 `value` minus its float32 rounding `stored`: the *_lo fields of the component record"""
+    return np.asarray(value, dtype=np.float64) - np.asarray(stored, dtype=np.float64)
 
 
 def _align_z_to(axis: np.ndarray) -> np.ndarray:
@@ -205,6 +213,7 @@ def _build_component(model: KinematicModel, joint_set: Sequence[int], frames: Li
         t = Ap.T @ T[:3, 3]
         rec["X"][k, :9] = R.reshape(-1)
         rec["X"][k, 9:] = t
+        rec["X_lo"][k] = _residue(np.concatenate([R.reshape(-1), t]), rec["X"][k])
         rec["jtype"][k] = 0 if j.type == "revolute" else 1
         s = src[p]
         rec["src_kind"][k] = s[0]
@@ -222,6 +231,8 @@ def _build_component(model: KinematicModel, joint_set: Sequence[int], frames: Li
         else:
             rec["src_idx"][k], rec["api"][k] = s[1], -1
             rec["mult"][k], rec["off"][k] = 1.0, 0.0
+        if s[0] in (SRC_FIXED, SRC_MIMIC):
+            rec["mult_lo"][k], rec["off_lo"][k] = _residue(s[2], rec["mult"][k]), _residue(s[3], rec["off"][k])
     rec["restore"][:nj] = restore
     rec["save"][:nj] = save
     # reduced variables: optimised joints in joint order; mimic joints ride on their source's variable
@@ -252,6 +263,7 @@ def _build_component(model: KinematicModel, joint_set: Sequence[int], frames: Li
         rec["frame_joint"][new] = lj
         if lj >= 0:
             rec["frame_off"][new] = A[lj].T @ offv
+            rec["frame_off_lo"][new] = _residue(A[lj].T @ offv, rec["frame_off"][new])
             anc = 0
             a = lj
             while a >= 0:
@@ -260,6 +272,7 @@ def _build_component(model: KinematicModel, joint_set: Sequence[int], frames: Li
             rec["frame_anc"][new] = anc
         else:
             rec["frame_off"][new] = offv
+            rec["frame_off_lo"][new] = _residue(offv, rec["frame_off"][new])
             rec["frame_anc"][new] = 0
             nbase += 1
     rec["n_base_frame"] = nbase

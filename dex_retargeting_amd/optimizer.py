@@ -40,7 +40,7 @@ class _OptHandle:
         p = getattr(self, "_pending", None)
         if p is not None:
             delta, q, last, fval = p
-            self._last = float(fval[0]) - delta * float(((q.astype(np.float64) - last.astype(np.float64)) ** 2).sum())
+            self._last = fval - delta * float(((q.astype(np.float64) - last.astype(np.float64)) ** 2).sum())
             self._pending = None
         return self._last
 
@@ -290,13 +290,15 @@ class Optimizer:
         self._state_out(state)
         if self.last_info["status"][0] == 2:  # non-finite: same fallback as the reference's RuntimeError path
             print("dexr: solver produced non-finite values, returning last_qpos")
+            self.opt._pending, self.opt._last = None, float("nan")  # no optimum of THIS frame: not the previous frame's value
             return np.array(last_qpos, dtype=np.float32)
         # nlopt's last_optimum_value() is the closure's return value, i.e. the data term WITHOUT the regulariser
         # (optimizer.py:198,304,575; printed by SeqRetargeting.verbose as "Last distance"); the kernels report
         # F = f + norm_delta |x - last|^2
         # (formed when somebody asks -- SeqRetargeting.verbose() -- not on every frame: three float64 numpy operations per call
-        # of the one-frame-per-call loop)
-        self.opt._pending = (float(self.norm_delta), q[0], last[0], self.last_info["fval"])
+        # of the one-frame-per-call loop).  COPIES: q[0] is the array handed to the caller and last[0] may be a view of the caller's
+        # last_qpos -- both are the caller's to overwrite before anybody asks
+        self.opt._pending = (float(self.norm_delta), q[0].copy(), last[0].copy(), float(self.last_info["fval"][0]))
         return q[0]
 
     def get_objective_function(self, ref_value: np.ndarray, fixed_qpos: np.ndarray, last_qpos: np.ndarray):

@@ -22,7 +22,7 @@
 #include <stdint.h>
 
 #define DEXR_MAGIC 0x52584544u /* "DEXR" */
-#define DEXR_TABLE_VERSION 5u
+#define DEXR_TABLE_VERSION 6u
 
 #define DEXR_MAXJ 32  /* joints per component (bitmask width) */
 #define DEXR_MAXF 16  /* frames (target links) per component  */
@@ -74,6 +74,13 @@ typedef struct dexr_comp_table {
   int32_t var[DEXR_MAXJ];
   float vmul[DEXR_MAXJ];
   int32_t var_joint[DEXR_MAXJ];
+  /* Table v6: what the float32 rounding of the kinematic constants above dropped, value = (double)field + (double)field_lo.
+   * Read by the float64 objective evaluation (dexr_eval) only, whose value and gradient are compared with float64 closures
+   * at residuals as small as that rounding (~5e-9 m of link position); the solve kernels keep the float32 fields. */
+  float X_lo[DEXR_MAXJ][12];
+  float mult_lo[DEXR_MAXJ];
+  float off_lo[DEXR_MAXJ];
+  float frame_off_lo[DEXR_MAXF][3];
 } dexr_comp_table;
 
 typedef struct dexr_model_header {

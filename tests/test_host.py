@@ -81,6 +81,7 @@ def test_table_struct_sizes_match_header():
     assert int(re.search(r"#define DEXR_MAXT (\d+)", h).group(1)) == mc.MAXT
     assert int(re.search(r"#define DEXR_TABLE_VERSION (\d+)u", h).group(1)) == mc.VERSION
     words = 4 + mc.MAXJ * 12 + 8 * mc.MAXJ + 4 * mc.MAXJ + mc.MAXF * 5 + 3 * mc.MAXT + 1 + 3 * mc.MAXJ
+    words += mc.MAXJ * 12 + 2 * mc.MAXJ + mc.MAXF * 3  # v6: X_lo, mult_lo, off_lo, frame_off_lo
     assert mc.COMP_DTYPE.itemsize == 4 * words
     assert mc.HEADER_DTYPE.itemsize == 4 * (18 + 1 + 2 * mc.MAXT)
 
